@@ -8,6 +8,10 @@ that is resident in HBM before the timed region starts.  Rank 0 prints ONE JSON 
     python bench.py --gpus 1 --steps 50 --warmup 10
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run times exactly --steps steps of the selected workload and nothing else.  --full adds the per-kernel
+roofline pass, the secondary workloads and the CPU baseline to the line; --dump-outputs DIR writes what the last
+timed step computed (loss, a fixed sample of the updated parameters and of the gradient) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -122,10 +126,27 @@ def flops_per_qa_actual(w, ragged):
     return full - 3 * per_tok * (w["T"] - mean_len(w, True))
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of each dumped vector: two float32 samples of 16 MB, well inside 64 MB in all
+
+
+def dump_outputs(tr, out_dir):
+    """What a caller of the timed path receives after its last step: the loss, the parameters after RMSprop and the
+    clamped gradient (VQATrainer.JdJ's return).  The vectors are reduced to the same seeded, sorted sample of indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = tr.get_params()
+    grads = tr.ctx.get_grads(tr.clamp)
+    n = params.size
+    idx = np.sort(np.random.default_rng(0).permutation(n)[:DUMP_SAMPLE]) if n > DUMP_SAMPLE else slice(None)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([tr.ctx.get_loss()], np.float64))
+    np.save(os.path.join(out_dir, "params.npy"), np.ascontiguousarray(params[idx], np.float32))
+    np.save(os.path.join(out_dir, "grads.npy"), np.ascontiguousarray(grads[idx], np.float32))
+
+
 def bench_one(pkg, w, args, rank, local_rank, world, dist, steps, warmup, ragged=False, bf16=False, roofline=True,
-              host_batches=False):
+              host_batches=False, dump_dir=None):
     """One configuration: warmup, `steps` timed steps between barriers, optional per-kernel pass.  host_batches: the
-    JdJ-shaped nvqa_step entry (host batch in, three synchronous copies per call) instead of nvqa_step_indices."""
+    JdJ-shaped nvqa_step entry (host batch in, three synchronous copies per call) instead of nvqa_step_indices.
+    dump_dir: rank 0 writes the outputs of the last timed step there (dump_outputs)."""
     import torch
     dims = pkg.binding.Dims(*[w[k] for k in ("arch", "B", "T", "V", "E", "R", "L", "I", "C", "A")])
     try:
@@ -172,14 +193,17 @@ def bench_one(pkg, w, args, rank, local_rank, world, dist, steps, warmup, ragged
     persistent = tr.ctx.persistent_state()   # does this shape take the persistent LSTM kernels? (reported in the line)
     for _ in range(warmup):
         one_step()
-    # `blocks` timed regions of EXACTLY `steps` steps each, every one bracketed by barrier + device synchronisation on
-    # both sides, MAX over ranks per region; ms_per_step / value come from the MEDIAN region and the line carries the
-    # spread (a single 20-step region of a 3 ms step is 61 ms: one number, no error bar -- VERDICT r3)
-    dts = []
-    for _ in range(max(1, args.blocks)):
+    # the `steps` timed steps run as `blocks` regions (sizes differ by at most one step), every one bracketed by barrier +
+    # device synchronisation on both sides, MAX over ranks per region; ms_per_step / value come from the MEDIAN region's
+    # time per step and the line carries the spread (a single 20-step region of a 3 ms step is 61 ms: one number, no error
+    # bar -- VERDICT r3)
+    nb = max(1, min(args.blocks, steps))
+    sizes = [steps // nb + (1 if i < steps % nb else 0) for i in range(nb)]
+    per_step = []
+    for n_b in sizes:
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(n_b):
             one_step()
         barrier()
         dt_b = time.perf_counter() - t0
@@ -187,16 +211,18 @@ def bench_one(pkg, w, args, rank, local_rank, world, dist, steps, warmup, ragged
             t = torch.tensor([dt_b], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt_b = float(t[0])
-        dts.append(dt_b)
-    dt = float(np.median(dts))
+        per_step.append(dt_b / n_b)
+    dt = float(np.median(per_step))  # seconds per step
+    if dump_dir and rank == 0:
+        dump_outputs(tr, dump_dir)
     loss = tr.ctx.get_loss()
 
     fl_qa = flops_per_qa_actual(w, ragged)
     peak = BF16_MFMA_PEAK_TFLOPS if bf16 else FP32_MFMA_PEAK_TFLOPS
-    value = w["B"] * world * steps / dt
-    out = {"value": round(value, 1), "ms_per_step": round(1e3 * dt / steps, 4),
-           "timed_blocks": {"blocks": len(dts), "steps_per_block": steps, "statistic": "median",
-                            "ms_per_step_min": round(1e3 * min(dts) / steps, 4), "ms_per_step_max": round(1e3 * max(dts) / steps, 4)},
+    value = w["B"] * world / dt
+    out = {"value": round(value, 1), "ms_per_step": round(1e3 * dt, 4),
+           "timed_blocks": {"blocks": nb, "steps_per_block": sizes, "statistic": "median",
+                            "ms_per_step_min": round(1e3 * min(per_step), 4), "ms_per_step_max": round(1e3 * max(per_step), 4)},
            "flop_per_qa": round(fl_qa), "persistent": persistent,
            "step_mfma_frac": round(value * fl_qa / (world * peak * 1e12), 4), "final_loss": round(loss, 5)}
     if roofline:
@@ -342,13 +368,17 @@ def bench_vgg(pkg, n=32, iters=4, bf16=False):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps in all (split over --blocks)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--blocks", type=int, default=5,
-                    help="timed regions of --steps steps each; ms_per_step is their median, min / max are reported")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (N = 1 only)")
+                    help="timed regions the --steps steps are split into; ms_per_step is the median region's, min / max are reported")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (loss, samples of parameters and gradient)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel roofline pass, the secondary workloads (N = 1) and the CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline pass")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads (N = 1 only)")
     ap.add_argument("--ragged", action="store_true", help="secondary case: question lengths ~ U{3..26}")
     ap.add_argument("--arch", type=int, default=1, choices=(1, 2),
                     help="2 = secondary case: arch2 deeper LSTM + Inception feats (BASELINE configs[3])")
@@ -356,6 +386,8 @@ def main():
                     help="secondary case: nvqa_set_precision(1), dense products on the bf16 matrix cores "
                          "(operands rounded to bf16, f32 accumulate); the headline metric is the f32 run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher (it never touches the GPU) and starts
@@ -395,7 +427,7 @@ def main():
     pkg = ge.load_package()
     w = WORKLOAD if args.arch == 1 else WORKLOAD_ARCH2
     res = bench_one(pkg, w, args, rank, local_rank, world, dist, args.steps, args.warmup, ragged=args.ragged,
-                    bf16=args.bf16, roofline=not args.no_roofline)
+                    bf16=args.bf16, roofline=args.full and not args.no_roofline, dump_dir=args.dump_outputs)
     out = {
         "metric": "QA-pairs/sec training step (batch 512, seq 26)" + ("" if args.arch == 1 else " [arch2, secondary]"), "value": res["value"],
         "unit": "QA-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -414,7 +446,7 @@ def main():
     if dist:
         dist.barrier()
     headline = args.arch == 1 and not args.ragged and not args.bf16
-    if rank == 0 and world == 1 and headline and not args.no_secondary:
+    if rank == 0 and world == 1 and headline and args.full and not args.no_secondary:
         # the other BASELINE.json configurations that fit one GPU, each with its own roofline fraction (same --steps / --warmup
         # as the headline: with 10 steps the one un-overlapped host enqueue behind the opening barrier weighed 5 % in the host-batch case)
         sec = {}
@@ -439,7 +471,7 @@ def main():
         sec["arch1_end_to_end_vgg16"] = bench_end_to_end(pkg, WORKLOAD, local_rank)
         sec["arch1_end_to_end_vgg16_bf16_extractor"] = bench_end_to_end(pkg, WORKLOAD, local_rank, bf16_vgg=True)
         out["secondary"] = sec
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w)
     if rank == 0:
         print(json.dumps(out), flush=True)

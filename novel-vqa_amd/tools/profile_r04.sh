@@ -1,14 +1,14 @@
 #!/bin/bash
 # Round-4 profile set (run on the GPU box from the repo root): kernel statistics, HBM traffic (FETCH_SIZE / WRITE_SIZE in
-# separate passes, MI355X_MICROARCH.md), matrix-pipe busy cycles, wave-cycle shares.  Results -> gpurun_out/prof_r04/,
+# separate passes, MI355X_MICROARCH.md), matrix-pipe busy cycles, wave-cycle shares.  Results -> out/prof_r04/,
 # summaries -> profiles/r04_*.  The program after `--` is python3 itself (no env / bash hop under rocprofv3).
 # usage: profile_r04.sh [tag [bench flags]]   e.g.  profile_r04.sh bf16_arch2 "--arch 2 --bf16"
 set -e
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-O=$R/gpurun_out/prof_r04${1:+_$1}
+O=$R/out/prof_r04${1:+_$1}
 mkdir -p $O
-B="python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $2"
+B="python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $2"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B > $O/bench_under_rocprof.json 2> $O/stats.log
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- $B > /dev/null 2> $O/fetch.log
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- $B > /dev/null 2> $O/write.log

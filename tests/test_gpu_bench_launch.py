@@ -25,7 +25,7 @@ def _launch(extra_env, gpus=2, extra_args=()):
     env.update(extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1",
            "--master-port", "29613", os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "2",
-           "--blocks", "2"] + list(extra_args)
+           "--blocks", "2", "--full"] + list(extra_args)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, f"rc {r.returncode}\n--- stdout\n{r.stdout[-3000:]}\n--- stderr\n{r.stderr[-6000:]}"
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -70,3 +70,30 @@ def test_gpus2_real_rccl():
     out, err = _launch({k: "" for k in ()})
     _check_line(out, 2)
     assert "librccl" in out["collective_library"]
+
+
+def test_plain_run_times_exactly_steps_and_dumps_outputs(tmp_path):
+    """A plain one-GPU run: --steps is the number of timed steps, the line carries the headline only, and
+    --dump-outputs leaves the last timed step's outputs as float .npy files within 64 MB."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "1",
+                        "--blocks", "3", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, f"rc {r.returncode}\n--- stdout\n{r.stdout[-3000:]}\n--- stderr\n{r.stderr[-6000:]}"
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 7 and out["timed_blocks"]["blocks"] == 3 and sum(out["timed_blocks"]["steps_per_block"]) == 7
+    assert abs(out["value"] - 512 / (out["ms_per_step"] * 1e-3)) < 1e-3 * out["value"]
+    for k in ("roofline", "phases", "kernel_ms_per_step", "secondary", "cpu_baseline"):
+        assert k not in out, k   # behind --full
+    files = sorted(p.name for p in d.iterdir())
+    assert files == ["grads.npy", "loss.npy", "params.npy"], files
+    assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+    arrs = {p.stem: np.load(p) for p in d.iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+    assert arrs["params"].size == arrs["grads"].size > 0 and np.abs(arrs["grads"]).max() <= 10.0   # clamped gradient
+    assert abs(arrs["loss"][0] - out["final_loss"]) < 1e-4
