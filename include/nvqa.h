@@ -42,10 +42,12 @@ extern "C" {
 
 #define NVQA_ARCH1 1 /* 002_train_vqa_arch1: Linear(V,E) embedding, n-layer LSTM, AxB fusion */
 #define NVQA_ARCH2 2 /* 003_train_vqa_arch2: image-as-first-token nn.Encoder, Linear(R,A) head */
+#define NVQA_ARCH_AE1 3 /* 001_train_autoencoder/001_train_arch1_text_autoencoder.lua: LSTM text auto-encoder
+                         * (misc/AutoEncoder_text_nostart.lua); dims T = seq_length D, I = C = A = 0 */
 
 /* Model dimensions (SURVEY.md symbol table). */
 typedef struct nvqa_dims {
-    int32_t arch; /* NVQA_ARCH1 | NVQA_ARCH2 */
+    int32_t arch; /* NVQA_ARCH1 | NVQA_ARCH2 | NVQA_ARCH_AE1 */
     int32_t B;    /* minibatch (QA pairs) per device             -batch_size          */
     int32_t T;    /* question buffer length (columns of ques_*)  buffer_size_q        */
     int32_t V;    /* question vocabulary size                    vocabulary_size_q    */
@@ -85,7 +87,10 @@ int nvqa_sync(nvqa_ctx *ctx); /* wait for all enqueued work (loss_out becomes va
  *  arch1 multimodal: W_q[C x 2RL], b_q[C], W_v[C x I], b_v[C], W_o[A x C], b_o[A]
  *  arch2 cnn       : W_p[E x I], b_p[E]
  *  arch2 encoder   : LSTM layers as above, then lookup W_lk[(V+1) x E]
- *  arch2 multimodal: W_o[A x R], b_o[A]                                         */
+ *  arch2 multimodal: W_o[A x R], b_o[A]
+ *  ae1 encoder     : LSTM layers as above (AutoEncoder_text_nostart.lua:89-110 parameters() order)
+ *  ae1 decoder     : LSTM layers as above, then W_proj[(V+1) x R], b_proj[V+1]
+ *  ae1 lookup      : W_lk[(V+1) x E] (row V+1 = the START / END token)                */
 size_t nvqa_param_count(const nvqa_ctx *ctx);
 int nvqa_segments(const nvqa_ctx *ctx, size_t sizes_out[3]);
 int nvqa_init_params(nvqa_ctx *ctx, uint64_t seed, float lo, float hi);
@@ -227,6 +232,24 @@ int nvqa_vgg16_preprocess(nvqa_vgg *vgg, const float *rgb, int n, int H, int W, 
 int nvqa_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const float *images, const int32_t *tokens,
                      const int32_t *lengths, const int32_t *labels, const nvqa_dropout *dropout,
                      float *loss_out);
+
+/* ---- text auto-encoder (NVQA_ARCH_AE1 contexts) ---- */
+/* On an auto-encoder context nvqa_step*, nvqa_forward, nvqa_evaluate, nvqa_set_fusion, nvqa_set_ref_quirks,
+ * nvqa_dataset_load, nvqa_comm_init and nvqa_set_precision(ctx, 1) return an error.
+ * One training forward + LanguageModelCriterion + backward (lossFun of 001_train_arch1_text_autoencoder.lua:212-245):
+ * tokens [B x D] left-aligned, 1..V, 0 = null.  Gradients stay on the device (nvqa_get_grads, nvqa_adam_update,
+ * nvqa_rmsprop_update); *loss_out (may be NULL) = the criterion's mean over the positions that carry a loss. */
+int nvqa_ae_step(nvqa_ctx *ctx, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out);
+/* Evaluate-mode (dropout = identity) loss of n <= B rows (eval_split, :148-194) and, if samples_out [n x D] is not NULL,
+ * greedy decoding (sample() with sample_max = 1, AutoEncoder_text_nostart.lua:134-210): 1-based tokens, V+1 = END.
+ * The encoder sees the tokens as the training forward does (0 -> 1, up to the batch's last non-null column). */
+int nvqa_ae_evaluate(nvqa_ctx *ctx, int32_t n, const int32_t *tokens, float *loss_out, int32_t *samples_out);
+/* Valid on every context.  One pass over the flat vector: g = clamp(g, -clamp, clamp) (clamp > 0), g += wd * x, then
+ * adam() of misc/optim_updates.lua:78-111 (step counter held by the context, reset by nvqa_init_params).
+ * stats_out (may be NULL; synchronises) = {||x||_2, count(|lr g| >= 0.01 |x|)} of x before the update, g after clamp + wd
+ * (the log line of 001_train_arch1_text_autoencoder.lua:266-268). */
+int nvqa_adam_update(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
+                     float stats_out[2]);
 
 /* ---- measurement ------------------------------------------------------ */
 /* HIP-event timing of kernel groups on the stream they are launched on.

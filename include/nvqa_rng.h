@@ -16,6 +16,11 @@
  *   NVQA_SITE_Q    question vector        idx = b*(2RL) + j   (arch2: b*R + j, head dropout)
  *   NVQA_SITE_V    image feature          idx = b*I + j
  *   NVQA_SITE_Z    fused vector           idx = b*C + j
+ * Text auto-encoder (NVQA_ARCH_AE1; D = seq_length, s = decoder step 0..D, k = 0 encoder / 1 decoder):
+ *   NVQA_SITE_AE_ENC_LK   encoder lookup        idx = (b*D + t)*E + e
+ *   NVQA_SITE_AE_DEC_LK   decoder lookup        idx = (b*(D+1) + s)*E + e
+ *   NVQA_SITE_AE_TOP      decoder top h         idx = (b*(D+1) + s)*R + j
+ *   NVQA_SITE_AE_LSTM     input of layer l >= 1 idx = (((k*L + l)*B + b)*(D+1) + t)*R + j
  */
 #ifndef NVQA_RNG_H
 #define NVQA_RNG_H
@@ -33,6 +38,10 @@
 #define NVQA_SITE_Q 2u
 #define NVQA_SITE_V 3u
 #define NVQA_SITE_Z 4u
+#define NVQA_SITE_AE_ENC_LK 5u
+#define NVQA_SITE_AE_DEC_LK 6u
+#define NVQA_SITE_AE_TOP 7u
+#define NVQA_SITE_AE_LSTM 8u
 
 NVQA_HD uint32_t nvqa_hash32(uint64_t seed, uint64_t step, uint32_t site, uint64_t idx)
 {

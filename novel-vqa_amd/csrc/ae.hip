@@ -1,0 +1,905 @@
+// ae.hip -- the text auto-encoder of the reference's first stage (NVQA_ARCH_AE1): training forward, LanguageModelCriterion,
+// backward, evaluate-mode loss and greedy decoding, and the fused clamp / weight-decay / Adam update (any context).
+//
+// Reference: 001_train_autoencoder/001_train_arch1_text_autoencoder.lua (lossFun :212-245, update :349-362, log line
+// :266-268, eval_split :148-194) with misc/AutoEncoder_text_nostart.lua (model :26-31, forward :215-343, backward :348-393,
+// criterion :399-455, sample :134-210) and misc/optim_updates.lua:78-111 (adam).  The decoder module is the one whose
+// signature the auto-encoder calls: 003_train_vqa_arch2/misc/LSTM_decoder.lua (001's copy has only lstm_conventional and no
+// LogSoftMax).
+//
+// Layout of one step (B rows, tmax = last column of the batch with a non-null token, Q = 2 tmax + 1 chain steps):
+//   chain step q < tmax      : encoder step q                 (input: lookup of tok[:, q], 0 -> 1)
+//   chain step q = tmax + s  : decoder step s, s = 0 .. tmax   (input: START, then lookup of tok[:, s-1], 0 -> 1)
+// Per layer, one array of states over the whole chain (slot 0 = the zero initial state, slot q+1 = after chain step q):
+// the decoder's initial state IS the encoder's final slot, and in the backward pass the decoder's state gradient at its
+// step 0 flows into the encoder's last step through the ordinary recurrent product, with the encoder's W_h2h replaced by
+// the decoder's at the boundary.  Each layer runs its whole chain before the layer above it starts (the decoder of layer l
+// needs the encoder of layer l only); the backward pass runs the layers top-down.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "gemm_f32.h"
+#include "nvqa_ctx.h"
+#include "prof.h"
+
+using namespace nvqa;
+
+namespace nvqa {
+
+struct AeState {
+    int D = 0, QM = 0;   // seq_length; chain steps the buffers hold (2 D + 1)
+    int ldl = 0;         // leading dimension of the logits (V + 1 rounded up to 4 floats; the padding columns stay zero)
+    int tmax = 0;        // last step's tmax
+    int32_t *tok = nullptr;     // [B x D] tokens of the current batch (device)
+    int32_t *nrows = nullptr;   // device int = B (every row of the chain is active)
+    int32_t *cur = nullptr;     // [B] greedy decoding: token fed at the next decoder step
+    int32_t *samples = nullptr; // [B x D] greedy decoding output
+    // lookup gradient: distinct tokens, their chunk ranges, the chunks' row ranges, the rows (grouped by token, row order)
+    int32_t *lk_tok = nullptr, *lk_tc = nullptr, *lk_start = nullptr, *lk_pos = nullptr;
+    int32_t *h_lk = nullptr;    // pinned staging: {nu, nchunks, the four arrays above}
+    float *lk_part = nullptr;   // [chunks][E] partial sums
+    int32_t *h_tok = nullptr;   // pinned staging of the tokens
+    float *X0 = nullptr;        // [QM B][E] lookup outputs (tanh), the layer-0 inputs
+    float *Gt[NVQA_MAX_LAYERS] = {};  // [QM B][4R] activated gates (forward) / d(pre-activations) (backward)
+    float *Hs[NVQA_MAX_LAYERS] = {};  // [(QM + 1) B][R]
+    float *Cs[NVQA_MAX_LAYERS] = {};  // [(QM + 1) B][R]
+    float *U[NVQA_MAX_LAYERS] = {};   // [QM B][R] Dropout(h of the layer below), l >= 1
+    float *dX = nullptr;        // [QM B][max(E, R)] time-batched d(input)
+    float *dHx = nullptr;       // [QM B][R] dL/dh from outside the recurrence (projection, layer above)
+    float *dc = nullptr;        // [B][R] carried cell gradient
+    float *Htd = nullptr;       // [(D + 1) B][R] Dropout(top h) of the decoder steps
+    float *logits = nullptr;    // [(D + 1) B][ldl] logits, then d(logits) in place
+    float *rowloss = nullptr;   // [(D + 1) B]
+    float *loss = nullptr;      // device scalar
+    float *h_loss = nullptr;    // pinned
+    float *slabs = nullptr;     // split-K partials of the weight gradients
+    size_t slab_floats = 0;
+    float *colpart = nullptr;   // column-sum partials
+    size_t colpart_floats = 0;
+};
+
+static int ae_alloc(void **p, size_t bytes)
+{
+    NVQA_HIP(hipMalloc(p, std::max<size_t>(bytes, 16)));
+    NVQA_HIP(hipMemset(*p, 0, std::max<size_t>(bytes, 16)));
+    return 0;
+}
+#define AE_ALLOC(ptr, count) NVQA_TRY(ae_alloc((void **)&(ptr), (size_t)(count) * sizeof(*(ptr))))
+
+static GemmArgs ae_args(const float *A, int lda, const float *B, int ldb, int M, int N, int K, int kslice = 0)
+{
+    GemmArgs g = {};
+    g.xcd = 1;
+    g.A = A; g.B = B; g.lda = lda; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
+    g.kslice = kslice > 0 ? kslice : (K > 0 ? K : 1);
+    return g;
+}
+
+static Drop ae_drop(const nvqa_dropout *dr, bool train)
+{
+    Drop d;
+    if (!train || !dr || dr->mode == 0) {
+        d.mode = 0; d.p = 0.f; d.inv_keep = 1.f; d.seed = 0; d.step = 0;
+    } else {
+        d.mode = 1; d.p = dr->p; d.inv_keep = 1.0f / (1.0f - dr->p); d.seed = dr->seed; d.step = dr->step;
+    }
+    return d;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// kernels
+// ------------------------------------------------------------------------------------------------------------------
+// token fed at chain step q of row b (1-based): encoder tok[b][q], decoder START (V+1) at s = 0, then tok[b][s-1]; 0 -> 1
+// (AutoEncoder_text_nostart.lua:249-262, :302-319).  `direct` (greedy decoding): the decoder's token comes from it.
+__device__ __forceinline__ int ae_token(const int32_t *tok, const int32_t *direct, int b, int q, int tmax, int D, int V)
+{
+    int v;
+    if (q < tmax) v = tok[(size_t)b * D + q];
+    else {
+        const int s = q - tmax;
+        v = s == 0 ? V + 1 : (direct ? direct[b] : tok[(size_t)b * D + s - 1]);
+    }
+    return v == 0 ? 1 : v;
+}
+__device__ __forceinline__ uint64_t ae_lk_idx(int b, int q, int tmax, int D, int E, int e, uint32_t *site)
+{
+    if (q < tmax) { *site = NVQA_SITE_AE_ENC_LK; return ((uint64_t)b * D + q) * E + e; }
+    *site = NVQA_SITE_AE_DEC_LK;
+    return ((uint64_t)b * (D + 1) + (q - tmax)) * E + e;
+}
+
+// LookupTable -> Dropout -> Tanh (AutoEncoder_text_nostart.lua:28-31) for chain steps [q0, q0 + nq): one workgroup per row
+__global__ void k_ae_embed(const int32_t *tok, const int32_t *direct, int B, int D, int V, int E, int tmax, int q0,
+                           const float *Wlk, Drop dr, float *X0)
+{
+    const int r = q0 * B + blockIdx.x, q = r / B, b = r % B;
+    const int v = ae_token(tok, direct, b, q, tmax, D, V);
+    const float *w = Wlk + (size_t)(v - 1) * E;
+    for (int e = threadIdx.x; e < E; e += blockDim.x) {
+        uint32_t site;
+        const uint64_t idx = ae_lk_idx(b, q, tmax, D, E, e, &site);
+        X0[(size_t)r * E + e] = tanhf(dr.scale(site, idx) * w[e]);
+    }
+}
+
+// inter-layer / top-h dropout (forward: out = scale * in; backward: the same scale on the gradient).
+// kind 0: input of layer l >= 1 at chain rows [r0, r0 + n): src row r is the output of chain step r / B (slot + 1 is added
+//         by the caller's pointer), site NVQA_SITE_AE_LSTM; kind 1: top h of decoder step s = row / B, site NVQA_SITE_AE_TOP.
+__global__ void k_ae_drop(const float *src, float *dst, size_t n, int R, int B, int D, int L, int l, int tmax, int r0, int kind,
+                          Drop dr)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int r = r0 + (int)(i / R), j = (int)(i % R), q = r / B, b = r % B;
+        float s = 1.f;
+        if (dr.mode) {
+            if (kind == 0) {
+                const int k = q < tmax ? 0 : 1, t = q < tmax ? q : q - tmax;
+                s = dr.scale(NVQA_SITE_AE_LSTM, ((((uint64_t)k * L + l) * B + b) * (D + 1) + t) * R + j);
+            } else {
+                s = dr.scale(NVQA_SITE_AE_TOP, ((uint64_t)b * (D + 1) + q) * R + j);
+            }
+        }
+        dst[i] = s * src[i];
+    }
+}
+
+// d(Dropout(top h)) from the projection's d(input) product, into dHx at the decoder's chain rows
+struct EpiAeTop {
+    float *dst; // dHx + tmax * B * R
+    int R, B, D;
+    Drop dr;
+    __device__ __forceinline__ void operator()(int, int m, int n, float v) const
+    {
+        const int s = m / B, b = m % B;
+        dst[(size_t)m * R + n] = dr.scale(NVQA_SITE_AE_TOP, ((uint64_t)b * (D + 1) + s) * R + n) * v;
+    }
+};
+
+// logits = x W^T + b into a padded row
+struct EpiAeBias {
+    float *C;
+    int ldc;
+    const float *b;
+    __device__ __forceinline__ void operator()(int, int m, int n, float v) const { C[(size_t)m * ldc + n] = v + b[n]; }
+};
+
+__device__ __forceinline__ void ae_lse_combine(float &m, float &s, float m2, float s2)
+{
+    if (m2 == -INFINITY) return;
+    if (m == -INFINITY) { m = m2; s = s2; return; }
+    if (m2 > m) { s = s * expf(m - m2) + s2; m = m2; }
+    else s += s2 * expf(m2 - m);
+}
+
+// LanguageModelCriterion (AutoEncoder_text_nostart.lua:416-450) over LogSoftMax (LSTM_decoder.lua of 003, :60-61):
+// one workgroup per row (s, b) of the logits.  The target is found here from the token matrix: tok[b][s] if non-null, END
+// (= V+1) at the first null (or s = D), nothing after it.  Statistics with an online max / sum-exp (one read of the row);
+// target rows then get (softmax - onehot) / n in place, rows without a target zeros (grad != 0).  nvalid: rows b >= nvalid
+// carry no loss (nvqa_ae_evaluate with n < B).  Row losses go to rowloss; their sum is taken by k_ae_loss in a fixed order.
+__global__ __launch_bounds__(256) void k_ae_softmax(float *logits, int ldl, int Vp1, const int32_t *tok, int B, int D, int nvalid,
+                                                    float inv_n, int grad, float *rowloss)
+{
+    __shared__ float sm[8], ss[8];
+    __shared__ float sh_lse;
+    const int row = blockIdx.x, s = row / B, b = row % B;
+    float *x = logits + (size_t)row * ldl;
+    int tgt = -1;
+    if (b < nvalid) {
+        const int32_t *t = tok + (size_t)b * D;
+        const int v = s < D ? t[s] : 0;
+        if (v != 0) tgt = v - 1;
+        else {
+            bool earlier = false;
+            for (int k = 0; k < s; ++k) earlier |= t[k] == 0;
+            if (!earlier) tgt = Vp1 - 1;
+        }
+    }
+    if (tgt < 0) {
+        if (threadIdx.x == 0) rowloss[row] = 0.f;
+        if (grad) {
+            float4 *x4 = reinterpret_cast<float4 *>(x);
+            for (int i = threadIdx.x; i < ldl / 4; i += blockDim.x) x4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+    }
+    float m = -INFINITY, sum = 0.f;
+    const float4 *x4 = reinterpret_cast<const float4 *>(x);
+    const int n4 = ldl / 4;
+    for (int i = threadIdx.x; i < n4; i += blockDim.x) {
+        const float4 v = x4[i];
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (4 * i + k >= Vp1) continue;
+            if (e[k] > m) { sum = sum * expf(m - e[k]) + 1.f; m = e[k]; }
+            else sum += expf(e[k] - m);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(sum, o, 64);
+        ae_lse_combine(m, sum, m2, s2);
+    }
+    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sm[w] = m; ss[w] = sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float M = sm[0], S = ss[0];
+        for (int k = 1; k < nw; ++k) ae_lse_combine(M, S, sm[k], ss[k]);
+        const float lse = M + logf(S);
+        sh_lse = lse;
+        rowloss[row] = lse - x[tgt];
+    }
+    __syncthreads();
+    if (!grad) return;
+    const float lse = sh_lse;
+    float4 *y4 = reinterpret_cast<float4 *>(x);
+    for (int i = threadIdx.x; i < n4; i += blockDim.x) {
+        const float4 v = y4[i];
+        float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = 4 * i + k;
+            e[k] = c < Vp1 ? (expf(e[k] - lse) - (c == tgt ? 1.f : 0.f)) * inv_n : 0.f;
+        }
+        y4[i] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+}
+
+// sum of the row losses in a fixed order (256 strided partials, then a tree) / n
+__global__ __launch_bounds__(256) void k_ae_loss(const float *rowloss, int nrows, float inv_n, float *out)
+{
+    __shared__ float sh[256];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nrows; i += 256) s += rowloss[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = sh[0] * inv_n;
+}
+
+// greedy decoding: argmax of one decoder step's logits (first maximum, as torch.max on the CPU), 1-based; recorded as the
+// sample of step s - 1 (sample() records the token fed at t >= 2) and fed to the next step
+__global__ __launch_bounds__(256) void k_ae_argmax(const float *logits, int ldl, int Vp1, int D, int s, int32_t *cur, int32_t *samples)
+{
+    __shared__ float bm[4];
+    __shared__ int bi[4];
+    const int b = blockIdx.x;
+    const float *x = logits + (size_t)b * ldl;
+    float m = -INFINITY;
+    int am = 0x7fffffff;
+    for (int c = threadIdx.x; c < Vp1; c += blockDim.x) {
+        const float v = x[c];
+        if (v > m) { m = v; am = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o, 64);
+        const int a2 = __shfl_xor(am, o, 64);
+        if (m2 > m || (m2 == m && a2 < am)) { m = m2; am = a2; }
+    }
+    if ((threadIdx.x & 63) == 0) { bm[threadIdx.x >> 6] = m; bi[threadIdx.x >> 6] = am; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k)
+            if (bm[k] > m || (bm[k] == m && bi[k] < am)) { m = bm[k]; am = bi[k]; }
+        cur[b] = am + 1;
+        samples[(size_t)b * D + s] = am + 1;
+    }
+}
+
+// column sums of X [M][ld] (first N columns), deterministic: stripes of rows -> part[S][N], then the S partials in order
+__global__ void k_ae_colsum_part(const float *X, int M, int N, int ld, int rps, float *part)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const int m0 = blockIdx.y * rps, m1 = min(M, m0 + rps);
+    float s0 = 0.f, s1 = 0.f;
+    int m = m0;
+    for (; m + 1 < m1; m += 2) { s0 += X[(size_t)m * ld + n]; s1 += X[(size_t)(m + 1) * ld + n]; }
+    if (m < m1) s0 += X[(size_t)m * ld + n];
+    part[(size_t)blockIdx.y * N + n] = s0 + s1;
+}
+__global__ void k_ae_colsum_final(const float *part, int S, int N, float *out, float *out2)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    float s = 0.f;
+    for (int i = 0; i < S; ++i) s += part[(size_t)i * N + n];
+    out[n] = s;
+    if (out2) out2[n] = s;
+}
+
+// split-K slabs [Z][n] -> out[n], fixed order
+__global__ void k_ae_slab_sum(const float *slabs, int Z, size_t n, float *out)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float s = 0.f;
+        for (int z = 0; z < Z; ++z) s += slabs[(size_t)z * n + i];
+        out[i] = s;
+    }
+}
+
+// lookup-table gradient (LookupTable:backward of both clone sets, :366-367 / :385-386), deterministic in two passes: the rows
+// of each distinct token (encoder and decoder positions, in row order) come in chunks of at most NVQA_AE_LK_CHUNK; pass 1
+// sums each chunk through the backward of Tanh and Dropout, pass 2 adds a token's chunks in order.  (One workgroup per
+// token summing all its rows serially took 13 ms at the default shape: the START token alone has B rows, the padding
+// token 1 thousands.)  Rows of tokens absent from the batch were zeroed by the caller.
+#define NVQA_AE_LK_CHUNK 16
+__global__ void k_ae_lk_part(const int32_t *lk_start, const int32_t *lk_pos, const float *X0, const float *dX, int B, int D,
+                             int E, int tmax, Drop dr, float *part)
+{
+    const int p0 = lk_start[blockIdx.x], p1 = lk_start[blockIdx.x + 1];
+    for (int e = threadIdx.x; e < E; e += blockDim.x) {
+        float s = 0.f;
+        for (int p = p0; p < p1; ++p) {
+            const int r = lk_pos[p], q = r / B, b = r % B;
+            const float y = X0[(size_t)r * E + e];
+            uint32_t site;
+            const uint64_t idx = ae_lk_idx(b, q, tmax, D, E, e, &site);
+            s += dX[(size_t)r * E + e] * (1.f - y * y) * dr.scale(site, idx);
+        }
+        part[(size_t)blockIdx.x * E + e] = s;
+    }
+}
+__global__ void k_ae_lk_sum(const int32_t *lk_tok, const int32_t *lk_tc, const float *part, int E, float *dW)
+{
+    const int u = lk_tok[blockIdx.x], c0 = lk_tc[blockIdx.x], c1 = lk_tc[blockIdx.x + 1];
+    for (int e = threadIdx.x; e < E; e += blockDim.x) {
+        float s = 0.f;
+        for (int k = c0; k < c1; ++k) s += part[(size_t)k * E + e];
+        dW[(size_t)(u - 1) * E + e] = s;
+    }
+}
+
+// clamp -> + wd x -> adam (misc/optim_updates.lua:78-111) in one pass, with the log line's statistics of x before the update:
+// part[2 blk] = sum x^2, part[2 blk + 1] = count(|lr g| >= 0.01 |x|).  Per-segment gradient scales (data-parallel mean,
+// -lr_scale) are applied before the clamp as k_rmsprop does; the step-skip words are honoured like there.
+struct AdamArgs {
+    float *x, *m, *v;
+    const float *g;
+    size_t n, seg0, seg1; // segment ends: [0, seg0) scale gs[0], [seg0, seg1) gs[1], rest gs[2]
+    float gs[3];
+    float lr, b1, b2, eps, wd, clamp, step;
+    const unsigned *skip;
+    const float *dp_skip;
+    float *h_dp, *dp_next;
+    double *part;
+};
+__device__ __forceinline__ void adam_one(const AdamArgs &a, size_t i, float &x, float &m, float &v, float g, double &sq, double &cnt)
+{
+    g *= i < a.seg0 ? a.gs[0] : (i < a.seg1 ? a.gs[1] : a.gs[2]);
+    if (a.clamp > 0.f) g = fminf(fmaxf(g, -a.clamp), a.clamp);
+    if (a.wd != 0.f) g += a.wd * x;
+    sq += (double)x * (double)x;
+    cnt += fabsf(g * a.lr) >= fabsf(x) * 0.01f ? 1.0 : 0.0;
+    m = a.b1 * m + (1.f - a.b1) * g;
+    v = a.b2 * v + (1.f - a.b2) * g * g;
+    x -= a.step * (m / (sqrtf(v) + a.eps));
+}
+__global__ __launch_bounds__(256) void k_adam(AdamArgs a)
+{
+    __shared__ double sh[2][256];
+    if (a.dp_next && blockIdx.x == 0 && threadIdx.x == 0) *a.dp_next = 0.f;
+    bool skip = a.skip && (a.skip[0] | a.skip[4]) != 0u;
+    if (a.dp_skip && a.dp_skip[0] != 0.f) {
+        if (a.h_dp && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.h_dp + 1, a.dp_skip[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        skip = true;
+    }
+    double sq = 0, cnt = 0;
+    if (!skip) {
+        const size_t n4 = a.n / 4, stride = (size_t)gridDim.x * blockDim.x;
+        float4 *x4 = reinterpret_cast<float4 *>(a.x), *m4 = reinterpret_cast<float4 *>(a.m), *v4 = reinterpret_cast<float4 *>(a.v);
+        const float4 *g4 = reinterpret_cast<const float4 *>(a.g);
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+            float4 xv = x4[i], mv = m4[i], vv = v4[i];
+            const float4 gv = g4[i];
+            adam_one(a, 4 * i + 0, xv.x, mv.x, vv.x, gv.x, sq, cnt);
+            adam_one(a, 4 * i + 1, xv.y, mv.y, vv.y, gv.y, sq, cnt);
+            adam_one(a, 4 * i + 2, xv.z, mv.z, vv.z, gv.z, sq, cnt);
+            adam_one(a, 4 * i + 3, xv.w, mv.w, vv.w, gv.w, sq, cnt);
+            x4[i] = xv; m4[i] = mv; v4[i] = vv;
+        }
+        const size_t t = 4 * n4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; // the < 4 trailing elements
+        if (t < a.n) adam_one(a, t, a.x[t], a.m[t], a.v[t], a.g[t], sq, cnt);
+    }
+    if (!a.part) return;
+    sh[0][threadIdx.x] = sq;
+    sh[1][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { a.part[2 * blockIdx.x] = sh[0][0]; a.part[2 * blockIdx.x + 1] = sh[1][0]; }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// GEMM configurations (gemm_f32.h).  Projection and time-batched products: 128 x 128 tiles (16x16x4 MFMA, 8 waves) for
+// the short-K forms, the 4-wave 32x32x2 form for the long-K weight gradients (the choice nvqa_api.hip measured for the same
+// product shapes); recurrent steps: the VQA per-level configurations.
+// ------------------------------------------------------------------------------------------------------------------
+typedef Cfg<16, 128, 128, 32, 4, 2, 1, 1> AeCfgWide;
+typedef Cfg<32, 128, 128, 32, 2, 2, 1, 1> AeCfgLongK;
+typedef Cfg<16, 64, 64, 64, 4, 1, 2, 1> AeCfgGates;  // = CfgLstmFwd
+typedef Cfg<16, 64, 32, 64, 4, 2, 1, 1> AeCfgStepBwd; // = CfgNarrow
+
+#define AE_LAUNCH(CFG, AM, BM, GATES, EPI, SEG, g, e) NVQA_HIP((launch_gemm<CFG, AM, BM, GATES, EPI, SEG>(c->s, g, e)))
+
+static int colsum(nvqa_ctx *c, const float *X, int M, int N, int ld, float *out, float *out2)
+{
+    AeState &a = *c->ae;
+    int S = std::min(64, std::max(1, M / 256));
+    const int rps = (M + S - 1) / S;
+    S = (M + rps - 1) / rps;
+    if ((size_t)S * N > a.colpart_floats) { set_error("ae: column-sum scratch too small"); return -1; }
+    hipLaunchKernelGGL(k_ae_colsum_part, dim3((N + 255) / 256, S), dim3(256), 0, c->s, X, M, N, ld, rps, a.colpart);
+    hipLaunchKernelGGL(k_ae_colsum_final, dim3((N + 255) / 256), dim3(256), 0, c->s, a.colpart, S, N, out, out2);
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
+
+// out [M x N] = A^T B summed over K rows: A stored [K][M] (lda), B stored [K][N] (ldb); split-K into slabs, fixed-order sum
+static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb, int M, int N, int K, float *out)
+{
+    AeState &a = *c->ae;
+    if (K <= 0) {
+        NVQA_HIP(hipMemsetAsync(out, 0, (size_t)M * N * 4, c->s));
+        return 0;
+    }
+    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
+    int Z = std::max(1, std::min(16, 512 / std::max(tiles, 1)));
+    while (Z > 1 && (size_t)Z * M * N > a.slab_floats) --Z;
+    const int kslice = ((K + Z - 1) / Z + 31) / 32 * 32;
+    Z = (K + kslice - 1) / kslice;
+    GemmArgs g = ae_args(A, lda, Bm, ldb, M, N, K, kslice);
+    const EpiStore e{Z > 1 ? a.slabs : out, N, (size_t)M * N};
+    AE_LAUNCH(AeCfgLongK, A_MC, B_NC, false, EpiStore, 0, g, e);
+    if (Z > 1) {
+        hipLaunchKernelGGL(k_ae_slab_sum, dim3(1024), dim3(256), 0, c->s, a.slabs, Z, (size_t)M * N, out);
+        NVQA_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// lifetime
+// ------------------------------------------------------------------------------------------------------------------
+int ae_create(nvqa_ctx *c)
+{
+    const nvqa_dims &d = c->d;
+    NVQA_HIP(hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking));
+    c->ae = new AeState();
+    AeState &a = *c->ae;
+    const size_t B = d.B, D = d.T, E = d.E, R = d.R, L = d.L, V = d.V;
+    a.D = (int)D;
+    a.QM = (int)(2 * D + 1);
+    a.ldl = (int)((V + 1 + 3) / 4 * 4);
+    const size_t QM = a.QM, total4 = (c->lo.total + 3) / 4 * 4; // (padding: nvqa_rmsprop_update runs over whole float4s)
+    AE_ALLOC(c->P, total4);
+    AE_ALLOC(c->G, total4);
+    AE_ALLOC(c->M2, total4);
+    AE_ALLOC(a.tok, B * D);
+    AE_ALLOC(a.nrows, 1);
+    {
+        const int32_t nb = d.B;
+        NVQA_HIP(hipMemcpy(a.nrows, &nb, 4, hipMemcpyHostToDevice));
+    }
+    AE_ALLOC(a.cur, B);
+    AE_ALLOC(a.samples, B * D);
+    AE_ALLOC(a.lk_tok, QM * B);
+    AE_ALLOC(a.lk_tc, QM * B + 1);
+    AE_ALLOC(a.lk_start, QM * B + 1);
+    AE_ALLOC(a.lk_pos, QM * B);
+    AE_ALLOC(a.lk_part, QM * B * E);
+    NVQA_HIP(hipHostMalloc((void **)&a.h_lk, (4 * QM * B + 4) * 4, hipHostMallocDefault));
+    NVQA_HIP(hipHostMalloc((void **)&a.h_tok, B * D * 4, hipHostMallocDefault));
+    NVQA_HIP(hipHostMalloc((void **)&a.h_loss, 16, hipHostMallocDefault));
+    AE_ALLOC(a.X0, QM * B * E);
+    for (size_t l = 0; l < L; ++l) {
+        AE_ALLOC(a.Gt[l], QM * B * 4 * R);
+        AE_ALLOC(a.Hs[l], (QM + 1) * B * R);
+        AE_ALLOC(a.Cs[l], (QM + 1) * B * R);
+        if (l > 0) AE_ALLOC(a.U[l], QM * B * R);
+    }
+    AE_ALLOC(a.dX, QM * B * std::max(E, R));
+    AE_ALLOC(a.dHx, QM * B * R);
+    AE_ALLOC(a.dc, B * R);
+    AE_ALLOC(a.Htd, (D + 1) * B * R);
+    AE_ALLOC(a.logits, (D + 1) * B * (size_t)a.ldl);
+    AE_ALLOC(a.rowloss, (D + 1) * B);
+    AE_ALLOC(a.loss, 4);
+    a.slab_floats = (size_t)8 * 4 * R * std::max(E, R);
+    AE_ALLOC(a.slabs, a.slab_floats);
+    a.colpart_floats = (size_t)64 * std::max<size_t>(4 * R, V + 1);
+    AE_ALLOC(a.colpart, a.colpart_floats);
+    return 0;
+}
+
+void ae_destroy(nvqa_ctx *c)
+{
+    if (!c->ae) return;
+    AeState &a = *c->ae;
+    void *ptrs[] = {a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
+                    a.logits, a.rowloss, a.loss, a.slabs, a.colpart};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    for (int l = 0; l < NVQA_MAX_LAYERS; ++l)
+        for (void *p : {(void *)a.Gt[l], (void *)a.Hs[l], (void *)a.Cs[l], (void *)a.U[l]})
+            if (p) (void)hipFree(p);
+    for (void *p : {(void *)a.h_lk, (void *)a.h_tok, (void *)a.h_loss})
+        if (p) (void)hipHostFree(p);
+    delete c->ae;
+    c->ae = nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// forward / backward
+// ------------------------------------------------------------------------------------------------------------------
+// weights of chain step q: the encoder's below tmax, the decoder's from tmax on
+static inline size_t w_i2h_of(const nvqa_ctx *c, int l, bool dec) { return dec ? c->lo.d_w_i2h[l] : c->lo.w_i2h[l]; }
+static inline size_t w_h2h_of(const nvqa_ctx *c, int l, bool dec) { return dec ? c->lo.d_w_h2h[l] : c->lo.w_h2h[l]; }
+
+// time-batched input projection of layer l for chain steps [q0, q1) (all of one phase) + both biases
+static int ae_i2h(nvqa_ctx *c, int l, int q0, int q1, bool dec)
+{
+    AeState &a = *c->ae;
+    const int B = c->d.B, R = c->d.R, in = l == 0 ? c->d.E : R;
+    if (q1 <= q0) return 0;
+    const float *X = (l == 0 ? a.X0 : a.U[l]) + (size_t)q0 * B * in;
+    const int M = (q1 - q0) * B;
+    ProfScope ps(c, PF_AE_I2H, 2.0 * M * 4 * R * in);
+    GemmArgs g = ae_args(X, in, c->P + w_i2h_of(c, l, dec), in, M, 4 * R, in);
+    const EpiBias2 e{a.Gt[l] + (size_t)q0 * B * 4 * R, 4 * R, c->P + (dec ? c->lo.d_b_i2h[l] : c->lo.b_i2h[l]),
+                     c->P + (dec ? c->lo.d_b_h2h[l] : c->lo.b_h2h[l])};
+    AE_LAUNCH(AeCfgWide, A_KC, B_KC, false, EpiBias2, 0, g, e);
+    return 0;
+}
+
+// recurrent step q of layer l: gates = (projection in Gt) + h_{q-1} W_h2h^T, fused cell (epilogues.h EpiLstmFwd)
+static int ae_fwd_step(nvqa_ctx *c, int l, int q, const Drop &dr)
+{
+    AeState &a = *c->ae;
+    const int B = c->d.B, R = c->d.R;
+    const bool dec = q >= a.tmax;
+    ProfScope ps(c, PF_AE_LSTM_FWD, q > 0 ? 2.0 * B * 4 * R * R : 0.0);
+    EpiLstmFwd e = {};
+    e.gx = a.Gt[l] + (size_t)q * B * 4 * R;
+    e.c_prev = a.Cs[l] + (size_t)q * B * R;
+    e.c = a.Cs[l] + (size_t)(q + 1) * B * R;
+    e.h = a.Hs[l] + (size_t)(q + 1) * B * R;
+    e.nrows = a.nrows;
+    e.R = R; e.B = B; e.T = a.QM; e.t = q; e.lnext_m1 = l;
+    e.dr = dr;
+    const float *hprev = a.Hs[l] + (size_t)q * B * R;
+    GemmArgs g = ae_args(hprev, R, c->P + w_h2h_of(c, l, dec), R, B, R, 0);
+    g.R = R;
+    g.A2 = hprev; g.lda2 = R; g.B2 = c->P + w_h2h_of(c, l, dec); g.ldb2 = R; g.K2 = q > 0 ? R : 0; // h_{-1} = 0
+    AE_LAUNCH(AeCfgGates, A_KC, B_KC, true, EpiLstmFwd, 1, g, e);
+    return 0;
+}
+
+// input of layer l >= 1 for chain steps [q0, q1): Dropout(h of layer l-1) (LSTM_encoder.lua / LSTM_decoder.lua drop_L)
+static int ae_layer_input(nvqa_ctx *c, int l, int q0, int q1, const Drop &dr)
+{
+    AeState &a = *c->ae;
+    const int B = c->d.B, R = c->d.R;
+    const size_t n = (size_t)(q1 - q0) * B * R;
+    hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s,
+                       a.Hs[l - 1] + (size_t)(q0 + 1) * B * R, a.U[l] + (size_t)q0 * B * R, n, R, B, a.D, c->d.L, l, a.tmax,
+                       q0 * B, 0, dr);
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
+
+// logits of decoder steps [s0, s1): Dropout(top h) -> Linear(R, V+1)
+static int ae_project(nvqa_ctx *c, int s0, int s1, const Drop &dr)
+{
+    AeState &a = *c->ae;
+    const int B = c->d.B, R = c->d.R, L = c->d.L, Vp1 = c->d.V + 1;
+    const size_t n = (size_t)(s1 - s0) * B * R;
+    hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s,
+                       a.Hs[L - 1] + (size_t)(a.tmax + 1 + s0) * B * R, a.Htd + (size_t)s0 * B * R, n, R, B, a.D, L, 0, 0,
+                       s0 * B, 1, dr);
+    NVQA_HIP(hipGetLastError());
+    const int M = (s1 - s0) * B;
+    ProfScope ps(c, PF_AE_PROJ_FWD, 2.0 * M * (double)Vp1 * R);
+    GemmArgs g = ae_args(a.Htd + (size_t)s0 * B * R, R, c->P + c->lo.w_proj, R, M, Vp1, R);
+    const EpiAeBias e{a.logits + (size_t)s0 * B * a.ldl, a.ldl, c->P + c->lo.b_proj};
+    AE_LAUNCH(AeCfgWide, A_KC, B_KC, false, EpiAeBias, 0, g, e);
+    return 0;
+}
+
+static int ae_embed(nvqa_ctx *c, int q0, int q1, const int32_t *direct, const Drop &dr)
+{
+    AeState &a = *c->ae;
+    const nvqa_dims &d = c->d;
+    if (q1 <= q0) return 0;
+    ProfScope ps(c, PF_AE_EMB, 0, (double)(q1 - q0) * d.B * d.E * 8);
+    hipLaunchKernelGGL(k_ae_embed, dim3((unsigned)((q1 - q0) * d.B)), dim3(std::min(256, (d.E + 63) / 64 * 64)), 0, c->s, a.tok,
+                       direct, d.B, a.D, d.V, d.E, a.tmax, q0, c->P + c->lo.w_lk, dr, a.X0);
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
+
+// teacher-forced forward of the whole chain (training and evaluate mode) + the criterion; grad: d(logits) in place
+static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool grad)
+{
+    AeState &a = *c->ae;
+    const nvqa_dims &d = c->d;
+    const int B = d.B, L = d.L, Q = 2 * a.tmax + 1, Vp1 = d.V + 1;
+    NVQA_TRY(ae_embed(c, 0, Q, nullptr, dr));
+    for (int l = 0; l < L; ++l) {
+        if (l > 0) NVQA_TRY(ae_layer_input(c, l, 0, Q, dr));
+        NVQA_TRY(ae_i2h(c, l, 0, a.tmax, false));
+        NVQA_TRY(ae_i2h(c, l, a.tmax, Q, true));
+        for (int q = 0; q < Q; ++q) NVQA_TRY(ae_fwd_step(c, l, q, dr));
+    }
+    NVQA_TRY(ae_project(c, 0, a.tmax + 1, dr));
+    const int rows = (a.tmax + 1) * B;
+    {
+        ProfScope ps(c, PF_AE_SOFTMAX, 0, (double)rows * a.ldl * 4 * (grad ? 3 : 1));
+        hipLaunchKernelGGL(k_ae_softmax, dim3(rows), dim3(256), 0, c->s, a.logits, a.ldl, Vp1, a.tok, B, a.D, nvalid,
+                           1.0f / (float)ncount, grad ? 1 : 0, a.rowloss);
+        hipLaunchKernelGGL(k_ae_loss, dim3(1), dim3(256), 0, c->s, a.rowloss, rows, 1.0f / (float)ncount, a.loss);
+        NVQA_HIP(hipGetLastError());
+    }
+    NVQA_HIP(hipMemcpyAsync(a.h_loss, a.loss, 4, hipMemcpyDeviceToHost, c->s));
+    return 0;
+}
+
+static int ae_backward(nvqa_ctx *c, const Drop &dr)
+{
+    AeState &a = *c->ae;
+    const nvqa_dims &d = c->d;
+    const int B = d.B, R = d.R, E = d.E, L = d.L, Vp1 = d.V + 1, T = a.tmax, Q = 2 * T + 1;
+    const int rows = (T + 1) * B;
+    // projection: dH_top (through drop_final) into the decoder rows of dHx, dW_proj, db_proj
+    NVQA_HIP(hipMemsetAsync(a.dHx, 0, (size_t)T * B * R * 4, c->s)); // the encoder's rows: no loss reaches them directly
+    {
+        ProfScope ps(c, PF_AE_PROJ_BWD, 4.0 * rows * (double)Vp1 * R);
+        GemmArgs g = ae_args(a.logits, a.ldl, c->P + c->lo.w_proj, R, rows, R, Vp1);
+        const EpiAeTop e{a.dHx + (size_t)T * B * R, R, B, a.D, dr};
+        AE_LAUNCH(AeCfgLongK, A_KC, B_NC, false, EpiAeTop, 0, g, e);
+        NVQA_TRY(wgrad(c, a.logits, a.ldl, a.Htd, R, Vp1, R, rows, c->G + c->lo.w_proj));
+        NVQA_TRY(colsum(c, a.logits, rows, Vp1, a.ldl, c->G + c->lo.b_proj, nullptr));
+    }
+    for (int l = L - 1; l >= 0; --l) {
+        const int in = l == 0 ? E : R;
+        NVQA_HIP(hipMemsetAsync(a.dc, 0, (size_t)B * R * 4, c->s));
+        for (int q = Q - 1; q >= 0; --q) {
+            // dh_q = dG_{q+1} W_h2h (of the phase of step q+1) + dHx_q; cell backward (epilogues.h EpiLstmBwd)
+            const bool last = q == Q - 1, dec_next = q + 1 >= T;
+            ProfScope ps(c, PF_AE_LSTM_BWD, last ? 0.0 : 2.0 * B * 4 * R * R);
+            EpiLstmBwd e = {};
+            e.gates = a.Gt[l] + (size_t)q * B * 4 * R;
+            e.c_prev = a.Cs[l] + (size_t)q * B * R;
+            e.c = a.Cs[l] + (size_t)(q + 1) * B * R;
+            e.dc = a.dc;
+            e.dh_ext = a.dHx + (size_t)q * B * R;
+            e.nrows = a.nrows;
+            e.R = R; e.B = B; e.T = a.QM; e.s = q; e.lm1 = 0; e.dr = dr; e.has_upper = 0;
+            GemmArgs g = ae_args(last ? a.Gt[l] : a.Gt[l] + (size_t)(q + 1) * B * 4 * R, 4 * R, c->P + w_h2h_of(c, l, dec_next), R,
+                                 B, R, last ? 0 : 4 * R);
+            AE_LAUNCH(AeCfgStepBwd, A_KC, B_NC, false, EpiLstmBwd, 0, g, e);
+        }
+        {   // d(input) of both phases
+            ProfScope ps(c, PF_AE_DGRAD, 2.0 * Q * B * 4.0 * R * in);
+            for (int ph = 0; ph < 2; ++ph) {
+                const int q0 = ph ? T : 0, q1 = ph ? Q : T;
+                if (q1 <= q0) continue;
+                GemmArgs g = ae_args(a.Gt[l] + (size_t)q0 * B * 4 * R, 4 * R, c->P + w_i2h_of(c, l, ph == 1), in, (q1 - q0) * B, in, 4 * R);
+                const EpiStore e{a.dX + (size_t)q0 * B * in, in, 0};
+                AE_LAUNCH(AeCfgWide, A_KC, B_NC, false, EpiStore, 0, g, e);
+            }
+        }
+        {   // weight and bias gradients of both phases
+            ProfScope ps(c, PF_AE_WGRAD, 4.0 * Q * B * 4.0 * R * (in + R));
+            for (int ph = 0; ph < 2; ++ph) {
+                const int q0 = ph ? T : 0, q1 = ph ? Q : T, K = (q1 - q0) * B;
+                const float *dG = a.Gt[l] + (size_t)q0 * B * 4 * R;
+                const float *X = (l == 0 ? a.X0 : a.U[l]) + (size_t)q0 * B * in;
+                NVQA_TRY(wgrad(c, dG, 4 * R, X, in, 4 * R, in, K, c->G + w_i2h_of(c, l, ph == 1)));
+                NVQA_TRY(wgrad(c, dG, 4 * R, a.Hs[l] + (size_t)q0 * B * R, R, 4 * R, R, K, c->G + w_h2h_of(c, l, ph == 1)));
+                NVQA_TRY(colsum(c, dG, K, 4 * R, 4 * R, c->G + (ph ? c->lo.d_b_i2h[l] : c->lo.b_i2h[l]),
+                                c->G + (ph ? c->lo.d_b_h2h[l] : c->lo.b_h2h[l])));
+            }
+        }
+        if (l > 0) { // d(h of layer l-1) through the inter-layer Dropout: the external term of layer l-1's chain
+            const size_t n = (size_t)Q * B * R;
+            hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s, a.dX, a.dHx,
+                               n, R, B, a.D, L, l, T, 0, 0, dr);
+            NVQA_HIP(hipGetLastError());
+        }
+    }
+    {   // lookup table: both token streams into one gradient
+        ProfScope ps(c, PF_AE_EMB_BWD, 0, (double)Q * B * E * 12);
+        NVQA_HIP(hipMemsetAsync(c->G + c->lo.w_lk, 0, (size_t)Vp1 * E * 4, c->s));
+        const int nu = a.h_lk[0], nch = a.h_lk[1], nt = std::min(256, (E + 63) / 64 * 64);
+        hipLaunchKernelGGL(k_ae_lk_part, dim3(nch), dim3(nt), 0, c->s, a.lk_start, a.lk_pos, a.X0, a.dX, B, a.D, E, T, dr, a.lk_part);
+        hipLaunchKernelGGL(k_ae_lk_sum, dim3(nu), dim3(nt), 0, c->s, a.lk_tok, a.lk_tc, a.lk_part, E, c->G + c->lo.w_lk);
+        NVQA_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// host side of a batch: tokens -> device, tmax, the criterion's n, and (training) the token -> rows index of the lookup
+// gradient (a counting sort: deterministic row order per token)
+static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, bool index, int *ncount)
+{
+    AeState &a = *c->ae;
+    const nvqa_dims &d = c->d;
+    const int B = d.B, D = a.D, V = d.V;
+    NVQA_HIP(hipStreamSynchronize(c->s)); // the staging buffers may still feed the previous step's copies
+    int tmax = 0, cnt = 0;
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < D; ++t) {
+            const int v = b < n ? tokens[(size_t)b * D + t] : 0;
+            if (v < 0 || v > V) { set_error("ae: token %d at (%d, %d) outside 0..%d", v, b, t, V); return -1; }
+            a.h_tok[(size_t)b * D + t] = v;
+            if (v) tmax = std::max(tmax, t + 1);
+        }
+    if (tmax == 0) { set_error("ae: the batch holds no token (every row is null)"); return -1; }
+    for (int b = 0; b < n; ++b) { // LanguageModelCriterion's n (:425-445)
+        bool first = true;
+        for (int t = 0; t <= D; ++t) {
+            const int v = t < D ? a.h_tok[(size_t)b * D + t] : 0;
+            if (v) ++cnt;
+            else if (first) { ++cnt; first = false; }
+        }
+    }
+    a.tmax = tmax;
+    *ncount = cnt;
+    NVQA_HIP(hipMemcpyAsync(a.tok, a.h_tok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
+    if (index) {
+        const int Q = 2 * tmax + 1, NP = Q * B;
+        std::vector<int> ofs(V + 2, 0), tokr(NP);
+        for (int r = 0; r < NP; ++r) {
+            const int q = r / B, b = r % B;
+            int v;
+            if (q < tmax) v = a.h_tok[(size_t)b * D + q];
+            else v = q == tmax ? V + 1 : a.h_tok[(size_t)b * D + q - tmax - 1];
+            tokr[r] = v == 0 ? 1 : v;
+            ++ofs[tokr[r]];
+        }
+        int32_t *ut = a.h_lk + 2, *tc = ut + NP, *cs = tc + NP + 1, *pos = cs + NP + 1;
+        int nu = 0, nch = 0, acc = 0;
+        std::vector<int> at(V + 2, 0);
+        for (int v = 1; v <= V + 1; ++v) {
+            if (!ofs[v]) continue;
+            ut[nu] = v;
+            tc[nu] = nch;
+            for (int k = 0; k < ofs[v]; k += NVQA_AE_LK_CHUNK) cs[nch++] = acc + k;
+            at[v] = acc;
+            acc += ofs[v];
+            ++nu;
+        }
+        tc[nu] = nch;
+        cs[nch] = acc;
+        for (int r = 0; r < NP; ++r) pos[at[tokr[r]]++] = r;
+        a.h_lk[0] = nu;
+        a.h_lk[1] = nch;
+        NVQA_HIP(hipMemcpyAsync(a.lk_tok, ut, (size_t)nu * 4, hipMemcpyHostToDevice, c->s));
+        NVQA_HIP(hipMemcpyAsync(a.lk_tc, tc, (size_t)(nu + 1) * 4, hipMemcpyHostToDevice, c->s));
+        NVQA_HIP(hipMemcpyAsync(a.lk_start, cs, (size_t)(nch + 1) * 4, hipMemcpyHostToDevice, c->s));
+        NVQA_HIP(hipMemcpyAsync(a.lk_pos, pos, (size_t)NP * 4, hipMemcpyHostToDevice, c->s));
+    }
+    return 0;
+}
+
+float ae_last_loss(const nvqa_ctx *c) { return c->ae ? *c->ae->h_loss : 0.f; }
+
+static int ae_check(nvqa_ctx *c)
+{
+    if (!c) { set_error("ctx is NULL"); return -1; }
+    if (c->d.arch != NVQA_ARCH_AE1 || !c->ae) { set_error("not an auto-encoder context (arch %d, NVQA_ARCH_AE1 = 3)", c->d.arch); return -1; }
+    NVQA_HIP(hipSetDevice(c->device));
+    return 0;
+}
+
+} // namespace nvqa
+
+extern "C" int nvqa_ae_step(nvqa_ctx *c, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out)
+{
+    NVQA_TRY(ae_check(c));
+    if (!tokens) { set_error("tokens is NULL"); return -1; }
+    const Drop dr = ae_drop(dropout, true);
+    int ncount = 0;
+    NVQA_TRY(ae_upload(c, c->d.B, tokens, true, &ncount));
+    NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
+    NVQA_TRY(ae_backward(c, dr));
+    c->have_grads = true;
+    if (loss_out) {
+        NVQA_HIP(hipStreamSynchronize(c->s));
+        *loss_out = *c->ae->h_loss;
+    }
+    return 0;
+}
+
+extern "C" int nvqa_ae_evaluate(nvqa_ctx *c, int32_t n, const int32_t *tokens, float *loss_out, int32_t *samples_out)
+{
+    NVQA_TRY(ae_check(c));
+    if (!tokens) { set_error("tokens is NULL"); return -1; }
+    if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
+    AeState &a = *c->ae;
+    const Drop dr = ae_drop(nullptr, false);
+    int ncount = 0;
+    NVQA_TRY(ae_upload(c, n, tokens, false, &ncount));
+    NVQA_TRY(ae_forward(c, dr, n, ncount, false));
+    if (samples_out) {
+        // sample(): the encoder state is the one just computed (slot tmax); the decoder is fed START, then its own argmax
+        const nvqa_dims &d = c->d;
+        const int B = d.B, L = d.L, T = a.tmax;
+        for (int s = 0; s < a.D; ++s) {
+            const int q = T + s;
+            NVQA_TRY(ae_embed(c, q, q + 1, s == 0 ? nullptr : a.cur, dr));
+            for (int l = 0; l < L; ++l) {
+                if (l > 0) NVQA_TRY(ae_layer_input(c, l, q, q + 1, dr));
+                NVQA_TRY(ae_i2h(c, l, q, q + 1, true));
+                NVQA_TRY(ae_fwd_step(c, l, q, dr));
+            }
+            NVQA_TRY(ae_project(c, s, s + 1, dr));
+            hipLaunchKernelGGL(k_ae_argmax, dim3(B), dim3(256), 0, c->s, a.logits + (size_t)s * B * a.ldl, a.ldl, d.V + 1, a.D, s,
+                               a.cur, a.samples);
+            NVQA_HIP(hipGetLastError());
+        }
+        NVQA_HIP(hipMemcpyAsync(samples_out, a.samples, (size_t)n * a.D * 4, hipMemcpyDeviceToHost, c->s));
+    }
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    if (loss_out) *loss_out = *a.h_loss;
+    return 0;
+}
+
+extern "C" int nvqa_adam_update(nvqa_ctx *c, float lr, float beta1, float beta2, float eps, float wd, float clamp,
+                                float stats_out[2])
+{
+    if (!c) { set_error("ctx is NULL"); return -1; }
+    if (!c->have_grads) { set_error("nvqa_adam_update before any step"); return -1; }
+    NVQA_HIP(hipSetDevice(c->device));
+    const size_t n = c->lo.total;
+    const int NB = 1024;
+    if (!c->adam_m) {
+        NVQA_HIP(hipMalloc((void **)&c->adam_m, n * 4 + 16));
+        NVQA_HIP(hipMalloc((void **)&c->adam_v, n * 4 + 16));
+        NVQA_HIP(hipMemsetAsync(c->adam_m, 0, n * 4, c->s));
+        NVQA_HIP(hipMemsetAsync(c->adam_v, 0, n * 4, c->s));
+        NVQA_HIP(hipMalloc((void **)&c->adam_part, 2 * NB * sizeof(double)));
+        c->adam_t = 0;
+    }
+    c->adam_t += 1;
+    ProfScope ps(c, PF_ADAM, 0, 28.0 * n);
+    AdamArgs a = {};
+    a.x = c->P; a.m = c->adam_m; a.v = c->adam_v; a.g = c->G; a.n = n;
+    a.seg0 = c->lo.seg[0]; a.seg1 = c->lo.seg[0] + c->lo.seg[1];
+    const float inv_world = 1.0f / (float)c->world;
+    for (int i = 0; i < 3; ++i) a.gs[i] = c->gscale[i] * inv_world;
+    const double t = (double)c->adam_t;
+    a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = wd; a.clamp = clamp;
+    a.step = (float)(lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
+    a.skip = c->comm ? nullptr : c->pf_sticky;
+    a.dp_skip = c->comm ? c->dp_status + c->dp_slot : nullptr;
+    a.h_dp = c->comm ? c->h_dp_status : nullptr;
+    a.dp_next = c->comm ? c->dp_status + (c->dp_slot ^ 1) : nullptr;
+    a.part = stats_out ? c->adam_part : nullptr;
+    hipLaunchKernelGGL(k_adam, dim3(NB), dim3(256), 0, c->s, a);
+    NVQA_HIP(hipGetLastError());
+    if (c->comm) c->dp_clean[c->dp_slot ^ 1] = true;
+    if (stats_out) {
+        std::vector<double> h(2 * NB);
+        NVQA_HIP(hipMemcpyAsync(h.data(), c->adam_part, 2 * NB * sizeof(double), hipMemcpyDeviceToHost, c->s));
+        NVQA_HIP(hipStreamSynchronize(c->s));
+        double sq = 0, cnt = 0;
+        for (int b = 0; b < NB; ++b) { sq += h[2 * b]; cnt += h[2 * b + 1]; }
+        stats_out[0] = (float)sqrt(sq);
+        stats_out[1] = (float)cnt;
+    }
+    return 0;
+}

@@ -46,7 +46,9 @@ static const char *kProfNames[PF_COUNT] = {
     "assemble",      "emb_fwd",       "gemm_i2h_fwd", "lstm_step_fwd", "head_prep", "gemm_head_fwd",
     "softmax_ce",    "gemm_head_bwd", "lstm_step_bwd", "gemm_dgrad",   "gemm_wgrad", "reduce_slabs",
     "colsum",        "emb_bwd",       "rmsprop",       "allreduce",    "gather_batch", "lstm_bwd_finish",
-    "ride_gemm"};
+    "ride_gemm",
+    "ae_emb_fwd",    "ae_gemm_i2h",   "ae_lstm_step_fwd", "ae_gemm_proj_fwd", "ae_softmax_ce", "ae_gemm_proj_bwd",
+    "ae_lstm_step_bwd", "ae_gemm_dgrad", "ae_gemm_wgrad", "ae_emb_bwd",      "adam"};
 
 
 static void prof_collect(nvqa_ctx *c)
@@ -144,6 +146,16 @@ static inline Drop mkdrop(const nvqa_dropout *dr, bool train)
 
 static void comm_destroy(nvqa_ctx *c); // with the RCCL loader, below
 
+// entry points of the VQA step refuse an auto-encoder context (its step is nvqa_ae_step, ae.hip)
+static int reject_ae(const nvqa_ctx *c, const char *fn)
+{
+    if (c && c->d.arch == NVQA_ARCH_AE1) {
+        set_error("%s: not available on an auto-encoder context (NVQA_ARCH_AE1: nvqa_ae_step / nvqa_ae_evaluate)", fn);
+        return -1;
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------
 // lifetime
 // ------------------------------------------------------------------------------------
@@ -161,7 +173,15 @@ template <class T> static int dalloc(T **p, size_t n)
 static int check_dims(const nvqa_dims *d)
 {
     if (!d) { set_error("dims is NULL"); return -1; }
-    if (d->arch != NVQA_ARCH1 && d->arch != NVQA_ARCH2) { set_error("arch must be 1 or 2"); return -1; }
+    if (d->arch == NVQA_ARCH_AE1) { // text auto-encoder: B, T = seq_length, V, E, R, L; no image, fusion or answers
+        if (d->B < 1 || d->T < 1 || d->V < 1 || d->E < 4 || d->R < 4 || d->L < 1 || d->L > NVQA_MAX_LAYERS || d->I || d->C || d->A) {
+            set_error("auto-encoder: bad dims (B=%d T=%d V=%d E=%d R=%d L=%d; I, C, A must be 0)", d->B, d->T, d->V, d->E, d->R, d->L);
+            return -1;
+        }
+        if (d->E % 4 || d->R % 4) { set_error("auto-encoder: E, R must be multiples of 4 (got E=%d R=%d)", d->E, d->R); return -1; }
+        return 0;
+    }
+    if (d->arch != NVQA_ARCH1 && d->arch != NVQA_ARCH2) { set_error("arch must be 1, 2 or 3"); return -1; }
     if (d->B < 1 || d->T < 1 || d->V < 1 || d->L < 1 || d->L > NVQA_MAX_LAYERS) {
         set_error("bad dims (B=%d T=%d V=%d L=%d)", d->B, d->T, d->V, d->L);
         return -1;
@@ -202,7 +222,7 @@ extern "C" int nvqa_create(const nvqa_dims *dims, int device, nvqa_ctx **out)
     c->d = *dims;
     c->device = device;
     if (nvqa_layout_init(dims, &c->lo)) { delete c; set_error("layout"); return -1; }
-    const int rc = create_impl(c);
+    const int rc = dims->arch == NVQA_ARCH_AE1 ? ae_create(c) : create_impl(c);
     if (rc != 0) { // a failure half-way (out of memory, ...) releases whatever was acquired; the message survives
         const std::string keep = nvqa_last_error();
         nvqa_destroy(c);
@@ -383,6 +403,9 @@ extern "C" int nvqa_destroy(nvqa_ctx *c)
     for (hipEvent_t e : c->prof_pool) (void)hipEventDestroy(e);
     c->prof_pool.clear();
     comm_destroy(c);
+    ae_destroy(c);
+    for (void *q : {(void *)c->adam_m, (void *)c->adam_v, (void *)c->adam_part})
+        if (q) (void)hipFree(q);
     if (c->hset[0].tok) { // two device sets + pinned staging of the host-batch entries
         for (int p = 0; p < 2; ++p) {
             for (void *q : {(void *)c->bset[p].tok, (void *)c->bset[p].len, (void *)c->bset[p].lab, (void *)c->bset[p].img})
@@ -548,6 +571,7 @@ extern "C" int nvqa_sync(nvqa_ctx *c)
 extern "C" int nvqa_persistent_state(const nvqa_ctx *c, int out[2])
 {
     if (!c || !out) { set_error("NULL argument"); return -1; }
+    if (c->d.arch == NVQA_ARCH_AE1) { out[0] = out[1] = 0; return 0; }
     int RB = 0;
     out[0] = persist_rows(c) > 0 ? 1 : 0;
     out[1] = persist_bwd_rows(c, &RB) > 0 ? 1 : 0;
@@ -652,6 +676,11 @@ extern "C" int nvqa_init_params(nvqa_ctx *c, uint64_t seed, float lo, float hi)
     }
     NVQA_TRY(nvqa_set_params(c, p.data()));
     NVQA_HIP(hipMemset(c->M2, 0, c->lo.total * 4));
+    if (c->adam_m) { // a fresh start of nvqa_adam_update too
+        NVQA_HIP(hipMemset(c->adam_m, 0, c->lo.total * 4));
+        NVQA_HIP(hipMemset(c->adam_v, 0, c->lo.total * 4));
+        c->adam_t = 0;
+    }
     return 0;
 }
 
@@ -1563,6 +1592,7 @@ extern "C" int nvqa_step(nvqa_ctx *c, const int32_t *tokens, const int32_t *leng
                          const int32_t *labels, const nvqa_dropout *dropout, float *loss_out)
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
+    NVQA_TRY(reject_ae(c, "nvqa_step"));
     if (!labels || !img) { set_error("labels / img is NULL"); return -1; }
     NVQA_HIP(hipSetDevice(c->device));
     NVQA_TRY(upload_batch(c, c->d.B, tokens, lengths, img, labels));
@@ -1580,6 +1610,7 @@ extern "C" int nvqa_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const float *images,
                                 float *loss_out)
 {
     if (!c || !vgg || !images || !labels) { set_error("NULL argument"); return -1; }
+    NVQA_TRY(reject_ae(c, "nvqa_step_images"));
     NVQA_HIP(hipSetDevice(c->device));
     // tokens / lengths / labels go through the usual validated upload; the image slot is filled below
     NVQA_TRY(upload_batch(c, c->d.B, tokens, lengths, nullptr, labels));
@@ -1600,6 +1631,7 @@ extern "C" int nvqa_forward(nvqa_ctx *c, int32_t n, const int32_t *tokens, const
                             const float *img, float *scores_out, int32_t *argmax_out)
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
+    NVQA_TRY(reject_ae(c, "nvqa_forward"));
     NVQA_HIP(hipSetDevice(c->device));
     NVQA_TRY(upload_batch(c, n, tokens, lengths, img, nullptr));
     const Drop dr = mkdrop(nullptr, false);
@@ -1620,6 +1652,7 @@ extern "C" int nvqa_evaluate(nvqa_ctx *c, int32_t n, const int32_t *tokens, cons
                              int32_t *argmax_out, int32_t *mc_argmax_out, float *loss_out)
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
+    NVQA_TRY(reject_ae(c, "nvqa_evaluate"));
     if (mc_ans && (n_mc < 1 || n_mc > 64)) { set_error("n_mc=%d outside 1..64", n_mc); return -1; }
     if ((loss_out && !labels) || (mc_argmax_out && !mc_ans)) { set_error("loss_out needs labels, mc_argmax_out needs mc_ans"); return -1; }
     NVQA_HIP(hipSetDevice(c->device));
@@ -1655,6 +1688,7 @@ extern "C" int nvqa_evaluate(nvqa_ctx *c, int32_t n, const int32_t *tokens, cons
 // model variants of the reference's other training scripts
 extern "C" int nvqa_set_fusion(nvqa_ctx *c, int askip)
 {
+    NVQA_TRY(reject_ae(c, "nvqa_set_fusion"));
     if (!c || c->d.arch != NVQA_ARCH1 || askip < 0 || askip > 2) { set_error("nvqa_set_fusion: arch1 context and mode 0 (AxB) / 1 (AskipB) / 2 (A_B) expected"); return -1; }
     if ((askip == 2) != (c->fusion_askip == 2)) {
         // netdef.A_B changes the classifier to Linear(2C, A): another parameter vector.  Only on a context that holds no
@@ -1668,6 +1702,7 @@ extern "C" int nvqa_set_fusion(nvqa_ctx *c, int askip)
 extern "C" int nvqa_set_ref_quirks(nvqa_ctx *c, int flags)
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
+    NVQA_TRY(reject_ae(c, "nvqa_set_ref_quirks"));
     if (c->d.arch != NVQA_ARCH2 || (flags & ~(NVQA_QUIRK_H0 | NVQA_QUIRK_LOOKUP))) {
         set_error("nvqa_set_ref_quirks: arch2 context and flags within %d expected", NVQA_QUIRK_H0 | NVQA_QUIRK_LOOKUP);
         return -1;
@@ -1684,6 +1719,7 @@ extern "C" int nvqa_set_precision(nvqa_ctx *c, int bf16)
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
     if (bf16 != 0 && bf16 != 1) { set_error("precision must be 0 (f32) or 1 (bf16 operands)"); return -1; }
+    if (bf16) NVQA_TRY(reject_ae(c, "nvqa_set_precision(ctx, 1)"));
     c->bf16 = bf16 != 0;
     return 0;
 }
@@ -1700,6 +1736,7 @@ extern "C" int nvqa_get_loss(nvqa_ctx *c, float *loss_out)
     if (!c || !loss_out) { set_error("NULL argument"); return -1; }
     NVQA_HIP(hipSetDevice(c->device));
     NVQA_HIP(hipStreamSynchronize(c->s));
+    if (c->d.arch == NVQA_ARCH_AE1) { *loss_out = ae_last_loss(c); return 0; }
     *loss_out = loss_mean_host(c);
     return check_persist(c);
 }
@@ -1711,8 +1748,14 @@ extern "C" int nvqa_rmsprop_update(nvqa_ctx *c, float lr, float alpha, float eps
     NVQA_HIP(hipSetDevice(c->device));
     ProfScope ps(c, PF_RMSPROP, 0, 20.0 * c->lo.total);
     const float inv_world = 1.0f / (float)c->world;
+    if (c->d.arch == NVQA_ARCH_AE1 && !(c->gscale[0] == c->gscale[1] && c->gscale[1] == c->gscale[2])) {
+        set_error("nvqa_rmsprop_update: per-segment gradient scales are not supported on an auto-encoder context");
+        return -1;
+    }
     if (c->gscale[0] == c->gscale[1] && c->gscale[1] == c->gscale[2]) {
-        const size_t n4 = c->lo.total / 4; // every tensor size is a multiple of 4 (check_dims)
+        // every VQA tensor size is a multiple of 4 (check_dims); an auto-encoder vector (b_proj has V+1 entries) is padded to
+        // whole float4s with zeros (ae.hip), which the update leaves at zero
+        const size_t n4 = c->d.arch == NVQA_ARCH_AE1 ? (c->lo.total + 3) / 4 : c->lo.total / 4;
         hipLaunchKernelGGL(k_rmsprop, dim3(2048), dim3(256), 0, c->s, reinterpret_cast<float4 *>(c->P),
                            reinterpret_cast<const float4 *>(c->G), reinterpret_cast<float4 *>(c->M2), n4, lr, alpha,
                            eps, wd, clamp, inv_world * c->gscale[0], c->comm ? (const unsigned *)nullptr : c->pf_sticky,
@@ -1743,6 +1786,7 @@ extern "C" int nvqa_dataset_load(nvqa_ctx *c, int64_t n_q, const int32_t *questi
                                  const float *feats, int l2_normalize)
 {
     if (!c || !questions || !img_pos || !answers || !feats) { set_error("NULL argument"); return -1; }
+    NVQA_TRY(reject_ae(c, "nvqa_dataset_load"));
     if (n_q < 1 || n_img < 1) { set_error("empty dataset"); return -1; }
     const nvqa_dims &d = c->d;
     if (d.arch == NVQA_ARCH1 && !lengths) { set_error("arch1 needs lengths"); return -1; }
@@ -1805,6 +1849,7 @@ extern "C" int nvqa_dataset_load(nvqa_ctx *c, int64_t n_q, const int32_t *questi
 extern "C" int nvqa_step_indices(nvqa_ctx *c, const int64_t *qinds, const nvqa_dropout *dropout, float *loss_out)
 {
     if (!c || !qinds) { set_error("NULL argument"); return -1; }
+    NVQA_TRY(reject_ae(c, "nvqa_step_indices"));
     if (c->ds.n_q == 0) { set_error("nvqa_step_indices before nvqa_dataset_load"); return -1; }
     const nvqa_dims &d = c->d;
     for (int b = 0; b < d.B; ++b)
@@ -1943,6 +1988,7 @@ extern "C" const char *nvqa_comm_library(void)
 extern "C" int nvqa_comm_init(nvqa_ctx *c, int rank, int world, const void *id)
 {
     if (!c || !id) { set_error("NULL argument"); return -1; }
+    NVQA_TRY(reject_ae(c, "nvqa_comm_init"));
     if (world < 1 || rank < 0 || rank >= world) { set_error("bad rank/world %d/%d", rank, world); return -1; }
     if (c->comm) { set_error("nvqa_comm_init: the context already has a communicator"); return -1; }
     NVQA_HIP(hipSetDevice(c->device));

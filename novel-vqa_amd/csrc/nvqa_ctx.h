@@ -13,6 +13,9 @@
 namespace nvqa {
 
 void set_error(const char *fmt, ...);
+int ae_create(nvqa_ctx *c);  // ae.hip: the buffers of an NVQA_ARCH_AE1 context (instead of the VQA step's)
+void ae_destroy(nvqa_ctx *c);
+float ae_last_loss(const nvqa_ctx *c); // loss of the last nvqa_ae_step / nvqa_ae_evaluate (after a synchronisation)
 
 #define NVQA_HIP(expr)                                                                           \
     do {                                                                                         \
@@ -50,6 +53,18 @@ enum ProfId {
     PF_GATHER,
     PF_LSTM_BWD_FIN, // slab sum + fused cell backward of one BPTT level
     PF_RIDE,         // FLOPs of the head products that ride in the persistent BPTT launch's idle workgroups (no time of their own: inside PF_LSTM_BWD's launch)
+    // text auto-encoder (ae.hip)
+    PF_AE_EMB,       // lookup gather + dropout + tanh (both token streams)
+    PF_AE_I2H,       // time-batched input projections of both LSTMs
+    PF_AE_LSTM_FWD,  // recurrent steps (h2h product + fused cell), encoder then decoder
+    PF_AE_PROJ_FWD,  // logits = H_top W_proj^T + b
+    PF_AE_SOFTMAX,   // vocabulary log-softmax / NLL / d(logits)
+    PF_AE_PROJ_BWD,  // dH_top, dW_proj, db_proj
+    PF_AE_LSTM_BWD,  // BPTT steps (dG W_h2h product + fused cell backward)
+    PF_AE_DGRAD,     // time-batched d(input) products
+    PF_AE_WGRAD,     // time-batched weight gradients + bias sums
+    PF_AE_EMB_BWD,   // lookup-table gradient
+    PF_ADAM,         // nvqa_adam_update
     PF_COUNT
 };
 
@@ -72,6 +87,8 @@ struct ProfEntry {
     int64_t launches = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
+
+struct AeState; // ae.hip: buffers of the text auto-encoder (NVQA_ARCH_AE1)
 
 struct Dataset {
     int64_t n_q = 0, n_img = 0;
@@ -187,6 +204,12 @@ struct nvqa_ctx {
     double *norm_part = nullptr; // nvqa_param_norms: per-workgroup sums of squares, allocated on first use
 
     nvqa::Dataset ds;
+
+    // text auto-encoder (arch NVQA_ARCH_AE1, ae.hip) and the Adam state of nvqa_adam_update (any arch, allocated on first use)
+    nvqa::AeState *ae = nullptr;
+    float *adam_m = nullptr, *adam_v = nullptr;
+    double *adam_part = nullptr; // per-workgroup {sum x^2, update count} of the log-line statistics
+    int64_t adam_t = 0;
 
     // data parallel
     void *comm = nullptr;

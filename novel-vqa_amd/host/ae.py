@@ -1,0 +1,158 @@
+"""Text auto-encoder pre-training (the reference's first stage, 001_train_autoencoder/001_train_arch1_text_autoencoder.lua)
+on the library's NVQA_ARCH_AE1 context: the data loader, the training loop with its log line and learning-rate decay,
+eval_split, and the export that VQATrainer.init_from_autoencoder reads (002_convert_text_model_arch1.lua:27-39)."""
+import json
+
+import numpy as np
+
+from . import binding, h5, t7
+
+
+class DataLoader:
+    """misc/DataLoader.lua: sentences of `labels/<split>` ([N x D], 0 = null), iterated in order.
+    `labels` may be given directly as {split: array} instead of an h5 file; ix_to_word comes from the json file."""
+
+    def __init__(self, h5_file=None, json_file=None, labels=None, ix_to_word=None):
+        if labels is None:
+            with h5.File(h5_file) as f:
+                labels = {s: np.asarray(f.read(f"labels/{s}")) for s in ("train", "val", "test") if self._has(f, s)}
+        self.labels = {k: np.asarray(v).astype(np.int32) for k, v in labels.items()}
+        if ix_to_word is None and json_file is not None:
+            with open(json_file) as fh:
+                ix_to_word = json.load(fh)["ix_to_word"]
+        self.ix_to_word = ix_to_word or {}
+        self.seq_length = next(iter(self.labels.values())).shape[1]
+        self.iterators = {k: 1 for k in self.labels}
+
+    @staticmethod
+    def _has(f, split):
+        try:
+            f.shape(f"labels/{split}")
+            return True
+        except Exception:
+            return False
+
+    def vocab_size(self):
+        return len(self.ix_to_word)
+
+    def reset_iterator(self, split):
+        self.iterators[split] = 1
+
+    def get_batch(self, split, batch_size):
+        """getBatch (:58-89).  Returns (labels [batch_size x D], bounds dict(it_pos_now, it_max, wrapped)).
+        On a wrap the rows up to the split's end are followed by the split's first rows and the iterator goes back to 1,
+        so the next batch starts with those first rows again (the reference's behaviour, kept)."""
+        data = self.labels[split]
+        max_index = data.shape[0]
+        it = self.iterators[split]
+        wrapped = False
+        if it + batch_size - 1 > max_index:
+            wrapped = True
+            if it < max_index:
+                num_left = max_index - it + 1
+                batch = np.concatenate([data[it - 1:max_index], data[0:batch_size - num_left]])
+            else:
+                batch = data[0:batch_size].copy()
+            self.iterators[split] = 1
+        else:
+            batch = data[it - 1:it - 1 + batch_size].copy()
+            self.iterators[split] = it + batch_size
+        return batch, {"it_pos_now": self.iterators[split], "it_max": max_index, "wrapped": wrapped}
+
+
+def decode_sequence(ix_to_word, seq, end_token):
+    """net_utils.decode_sequence: words up to the first END (or null) token, joined by spaces."""
+    out = []
+    for row in np.asarray(seq):
+        words = []
+        for ix in row:
+            ix = int(ix)
+            if ix == 0 or ix == end_token:
+                break
+            words.append(ix_to_word.get(str(ix), ix_to_word.get(ix, "UNK")))
+        out.append(" ".join(words))
+    return out
+
+
+class AETrainer:
+    """The training script's loop on the library: ae_step (lossFun), the log line, the learning-rate decay and the
+    Adam (or RMSprop) update.  dims: binding.Dims with arch = ARCH_AE1, T = seq_length, I = C = A = 0."""
+
+    def __init__(self, dims, device=0, learning_rate=1e-5, learning_rate_decay_start=-1, learning_rate_decay_every=50000,
+                 optim="adam", optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6, grad_clip=0.1,
+                 drop_prob=0.5, seed=123):
+        if dims.arch != binding.ARCH_AE1:
+            raise ValueError("AETrainer needs dims.arch = ARCH_AE1 (3)")
+        if optim not in ("adam", "rmsprop"):
+            raise ValueError("optim: adam or rmsprop (the other optimisers of misc/optim_updates.lua are not provided)")
+        self.dims = dims
+        self.ctx = binding.Context(dims, device)
+        self.learning_rate = learning_rate
+        self.decay_start, self.decay_every = learning_rate_decay_start, learning_rate_decay_every
+        self.optim = optim
+        self.alpha, self.beta, self.eps = optim_alpha, optim_beta, optim_epsilon
+        self.weight_decay, self.grad_clip = weight_decay, grad_clip
+        self.drop_prob, self.seed = drop_prob, seed
+        self.iter = 1
+        self.ctx.init_params(seed, -0.08, 0.08)
+
+    def current_lr(self):
+        """:342-347"""
+        lr = self.learning_rate
+        if self.decay_start >= 0 and self.iter > self.decay_start:
+            lr *= 0.5 ** ((self.iter - self.decay_start) / self.decay_every)
+        return lr
+
+    def train_step(self, tokens):
+        """lossFun + log line + update of one iteration; returns (loss, # updates, paramsNorm, the log line)."""
+        dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.seed, self.iter)
+        loss = self.ctx.ae_step(tokens, dr)
+        lr = self.current_lr()
+        if self.optim == "adam":
+            norm, count = self.ctx.adam_update(lr, self.alpha, self.beta, self.eps, self.weight_decay, self.grad_clip, stats=True)
+        else:  # the statistics of the log line, then the same clamp / wd in nvqa_rmsprop_update
+            x = self.ctx.get_params()
+            g = np.clip(self.ctx.get_grads(), -self.grad_clip, self.grad_clip) + np.float32(self.weight_decay) * x
+            norm = float(np.sqrt((x.astype(np.float64) ** 2).sum()))
+            count = int((np.abs(g * np.float32(lr)) >= np.abs(x) * np.float32(0.01)).sum())
+            self.ctx.rmsprop_update(lr, self.alpha, self.eps, self.weight_decay, self.grad_clip)
+        line = "iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f" % (self.iter, loss, count, norm)
+        self.iter += 1
+        return loss, count, norm, line
+
+    def train(self, loader, iters, log=print):
+        losses = []
+        for _ in range(iters):
+            batch, _ = loader.get_batch("train", self.dims.B)
+            loss, _, _, line = self.train_step(batch)
+            losses.append(loss)
+            if log:
+                log(line)
+        return losses
+
+    def eval_split(self, loader, split="val", val_sentences_use=-1):
+        """eval_split (:148-194): mean of the per-batch evaluate-mode losses, stopping when the split wraps or (when
+        val_sentences_use > 0) once that many sentences were used; predictions are the greedy decodes through ix_to_word.
+        (The reference's counter `n` is never incremented there, so only the wrap ends its loop.)"""
+        loader.reset_iterator(split)
+        losses, preds, used = [], [], 0
+        end = self.dims.V + 1
+        while True:
+            batch, bounds = loader.get_batch(split, self.dims.B)
+            loss, samples = self.ctx.ae_evaluate(batch, samples=True)
+            losses.append(loss)
+            for p, a in zip(decode_sequence(loader.ix_to_word, samples, end), decode_sequence(loader.ix_to_word, batch, end)):
+                used += 1
+                preds.append({"seqNo": used, "prediction": p, "actual": a})
+            if bounds["wrapped"] or (val_sentences_use > 0 and used >= val_sentences_use):
+                break
+        return float(np.mean(losses)), preds
+
+    def export_for_vqa(self, path):
+        """002_convert_text_model_arch1.lua:27-39: {lookup = W_lk^T [E x (V+1)], encoder = the encoder segment} plus
+        layout = 'nvqa' (the LSTM tensors are in include/nvqa_layout.h order), readable by init_from_autoencoder."""
+        d = self.dims
+        x = self.ctx.get_params()
+        seg = self.ctx.segments()
+        w_lk = x[seg[0] + seg[1]:].reshape(d.V + 1, d.E)
+        t7.save(path, {"lookup": np.ascontiguousarray(w_lk.T), "encoder": x[:seg[0]].copy(), "layout": t7.LAYOUT_MARK})

@@ -15,6 +15,9 @@ LIB_PATH = os.path.join(_PKG, "libnvqa.so")
 COMM_ID_BYTES = 128
 
 
+ARCH1, ARCH2, ARCH_AE1 = 1, 2, 3
+
+
 class NvqaError(RuntimeError):
     pass
 
@@ -73,6 +76,9 @@ SYMBOLS = {
     "nvqa_vgg16_set_precision": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_vgg16_preprocess": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p]),
     "nvqa_step_images": (ctypes.c_int, [_vp, _vp, _f32p, _i32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
+    "nvqa_ae_step": (ctypes.c_int, [_vp, _i32p, ctypes.POINTER(Dropout), _f32p]),
+    "nvqa_ae_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _i32p]),
+    "nvqa_adam_update": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_profile_reset": (ctypes.c_int, [_vp]),
     "nvqa_profile_count": (ctypes.c_int, [_vp]),
@@ -243,6 +249,32 @@ class Context:
 
     def rmsprop_update(self, lr, alpha=0.99, eps=1e-8, wd=0.0, clamp=10.0):
         self._check(self.lib.nvqa_rmsprop_update(self._h, lr, alpha, eps, wd, clamp))
+
+    # ---- text auto-encoder (arch ARCH_AE1) and Adam ---------------------------------
+    def ae_step(self, tokens, dropout=None, want_loss=True):
+        """nvqa_ae_step: tokens [B x D] left-aligned, 0 = null.  Returns the criterion's loss (or None)."""
+        d = self.dims
+        tokens = np.ascontiguousarray(tokens, np.int32).reshape(d.B, d.T)
+        loss = ctypes.c_float(0)
+        dr = ctypes.byref(dropout) if dropout is not None else None
+        self._check(self.lib.nvqa_ae_step(self._h, _i32(tokens), dr, ctypes.byref(loss) if want_loss else None))
+        return float(loss.value) if want_loss else None
+
+    def ae_evaluate(self, tokens, samples=False):
+        """nvqa_ae_evaluate: (evaluate-mode loss, greedy samples [n x D] 1-based with V+1 = END, or None)."""
+        d = self.dims
+        tokens = np.ascontiguousarray(tokens, np.int32).reshape(-1, d.T)
+        n = tokens.shape[0]
+        out = np.empty((n, d.T), np.int32) if samples else None
+        loss = ctypes.c_float(0)
+        self._check(self.lib.nvqa_ae_evaluate(self._h, n, _i32(tokens), ctypes.byref(loss), _i32(out)))
+        return float(loss.value), out
+
+    def adam_update(self, lr, beta1=0.8, beta2=0.999, eps=1e-8, wd=0.0, clamp=0.0, stats=False):
+        """clamp -> + wd x -> adam in one pass; stats=True returns (paramsNorm, # updates) of the log line."""
+        out = np.zeros(2, np.float32) if stats else None
+        self._check(self.lib.nvqa_adam_update(self._h, lr, beta1, beta2, eps, wd, clamp, _f32(out)))
+        return (float(out[0]), int(out[1])) if stats else None
 
     def set_fusion(self, mode):
         """0 netdef.AxB, 1 netdef.AskipB, 2 netdef.A_B (W_o becomes [A x 2C]: right after creation only)."""

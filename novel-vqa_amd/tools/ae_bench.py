@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""ae_bench.py -- the text auto-encoder's training step (nvqa_ae_step + nvqa_adam_update) at the reference's default
+shape (001_train_arch1_text_autoencoder.lua: B = 1000, seq_length D = 16, E = R = 512, 1 layer, dropout 0.5, Adam) with
+the VQA vocabulary (V = 14773), on random sentences of lengths U{3..16}.  Prints ONE JSON line: ms per step and
+sentences/s (median over timed blocks after warm-up), the per-group profile of a separate profiled pass, and the
+step's fraction of the f32 MFMA roofline (FLOPs computed from the shape, 3 x forward).
+
+    python novel-vqa_amd/tools/ae_bench.py [--blocks 5 --steps 10 --warmup 5] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+import __graft_entry__ as ge  # noqa: E402
+
+FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md "Peak FP32 (matrix)"
+
+
+def step_flops(B, T, V, E, R, L):
+    """3 x forward of a batch whose tmax is T: T encoder + T+1 decoder LSTM steps, T+1 projections"""
+    lstm = sum(2 * B * 4 * R * ((E if l == 0 else R) + R) for l in range(L))
+    fwd = (2 * T + 1) * lstm + (T + 1) * 2.0 * B * R * (V + 1)
+    return 3 * fwd
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=1000)
+    ap.add_argument("--D", type=int, default=16)
+    ap.add_argument("--V", type=int, default=14773)
+    ap.add_argument("--E", type=int, default=512)
+    ap.add_argument("--R", type=int, default=512)
+    ap.add_argument("--L", type=int, default=1)
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    pkg = ge.load_package()
+    b = pkg.binding
+    dims = b.Dims(b.ARCH_AE1, a.B, a.D, a.V, a.E, a.R, a.L, 0, 0, 0)
+    ctx = b.Context(dims, 0)
+    ctx.init_params(123, -0.08, 0.08)
+    rng = np.random.default_rng(0)
+    batches = []
+    for _ in range(8):
+        lens = rng.integers(3, a.D + 1, a.B)
+        tok = np.zeros((a.B, a.D), np.int32)
+        for i, n in enumerate(lens):
+            tok[i, :n] = rng.integers(1, a.V + 1, n)
+        batches.append(tok)
+    it = [0]
+
+    def one_step():
+        it[0] += 1
+        ctx.ae_step(batches[it[0] % len(batches)], b.Dropout(1, 0.5, 123, it[0]), want_loss=False)
+        ctx.adam_update(1e-5, 0.8, 0.999, 1e-8, 1e-6, 0.1)
+
+    for _ in range(a.warmup):
+        one_step()
+    ctx.sync()
+    block_ms = []
+    for _ in range(a.blocks):
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            one_step()
+        ctx.sync()
+        block_ms.append((time.perf_counter() - t0) * 1e3 / a.steps)
+    ms = float(np.median(block_ms))
+    loss = ctx.ae_step(batches[0], b.Dropout(1, 0.5, 123, 0))
+    # profiled pass (events around every launch group: slower, reported per group only)
+    ctx.profile_enable(True)
+    for _ in range(3):
+        one_step()
+    ctx.sync()
+    ctx.profile_reset()
+    nprof = 5
+    for _ in range(nprof):
+        one_step()
+    ctx.sync()
+    prof = {k: {"ms_per_step": v["ms"] / nprof, "launches_per_step": v["launches"] / nprof,
+                "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["flops"] > 0 and v["ms"] > 0 else None,
+                "gb_s": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["bytes"] > 0 and v["ms"] > 0 else None}
+            for k, v in ctx.profile().items() if v["launches"] > 0}
+    ctx.profile_enable(False)
+    ctx.close()
+    tmaxes = [int(np.nonzero(t.any(0))[0][-1]) + 1 for t in batches]
+    fl = float(np.mean([step_flops(a.B, T, a.V, a.E, a.R, a.L) for T in tmaxes]))
+    line = {"workload": "ae_arch1_text", "B": a.B, "D": a.D, "V": a.V, "E": a.E, "R": a.R, "L": a.L,
+            "ms_per_step": round(ms, 4), "block_ms": [round(x, 4) for x in block_ms],
+            "sentences_per_s": round(a.B / (ms * 1e-3), 1), "loss": loss,
+            "tflop_per_step": round(fl / 1e12, 4), "achieved_tflops": round(fl / (ms * 1e-3) / 1e12, 2),
+            "fraction_of_f32_mfma_peak": round(fl / (ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
+            "profile": prof}
+    s = json.dumps(line)
+    print(s)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
+if __name__ == "__main__":
+    main()
