@@ -845,17 +845,6 @@ __global__ void k_lstm_bwd_finish(BwdFinish a)
 // misc/rmsprop_lrscale.lua:16-34).  gscale = 1/world for the data-parallel mean.
 // 20 B/parameter of HBM traffic (read g,m,x; write m,x).
 // ---------------------------------------------------------------------------------
-// LSTM bias gradients from the row blocks' partial column sums (fixed order); both bias vectors of a layer receive the sum
-__global__ void k_bias_sum(const float *part /*[RB][N]*/, int RB, int N, float *out, float *out2)
-{
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    float s = 0.f;
-    for (int r = 0; r < RB; ++r) s += part[(size_t)r * N + n];
-    out[n] = s;
-    out2[n] = s;
-}
-
 // skip (single process): the sticky err records of the persistent LSTM kernels (8 words, persist_fwd.hip: k_err_latch).
 // dp_skip (data parallel): the number of ranks whose kernel gave up in THIS step, all-reduced -- the same number on every
 // rank.  With a communicator it is the ONLY thing consulted (the launcher passes skip = nullptr): a rank-local sticky record

@@ -607,7 +607,7 @@ __global__ __launch_bounds__(NVQA_PF_THREADS, 1) void k_lstm_fwd_persist(Persist
     if constexpr (BF && KA == KR) {
         // bf16, E = R (arch2): layer 0 reads its input chunks from the bf16 image of X0 (a.Ub[0], left by the embedding kernel)
         // and is the SAME instance as the layers above -- one copy of the unrolled step loop fewer in the instruction cache;
-        // without the image (NVQA_X0_B16=0) it stages and rounds the f32 rows as before
+        // without the image (none is made where E % 8 != 0) it stages and rounds the f32 rows as before
         if (l == 0 && !a.Ub[0]) persist_fwd_layer<G0A, GR, MT, BF, false, RAG>(a, l, rb, ut, pf_smem);
         else persist_fwd_layer<GR, GR, MT, BF, BF, RAG>(a, l, rb, ut, pf_smem);
     } else {

@@ -115,18 +115,11 @@ static int gemm_med(nvqa_ctx *c, const GemmArgs &g, const Epi &e, hipStream_t st
     return 0;
 }
 
-// NVQA_XCD=0 keeps the natural tile order (for A/B measurements of the XCD-aware order)
-static int xcd_order()
-{
-    static const int v = [] { const char *e = getenv("NVQA_XCD"); return (e && e[0] == '0') ? 0 : 1; }();
-    return v;
-}
-
 static GemmArgs mkargs(const float *A, int lda, const float *B, int ldb, int M, int N, int K,
                        int kslice = 0, int R = 0, const int *mlimit = nullptr)
 {
     GemmArgs g = {};
-    g.xcd = xcd_order();
+    g.xcd = 1; // XCD-folded tile order
     g.A = A; g.B = B; g.lda = lda; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
     g.kslice = kslice > 0 ? kslice : (K > 0 ? K : 1);
     g.R = R; g.mlimit = mlimit;
@@ -236,11 +229,8 @@ extern "C" int nvqa_create(const nvqa_dims *dims, int device, nvqa_ctx **out)
 // NVQA_FAIL_ALLOC=n makes the n-th device allocation of nvqa_create fail (tests: the failure path frees the context)
 static int create_impl(nvqa_ctx *c)
 {
-    {
-        const char *e = getenv("NVQA_FAIL_ALLOC");
-        g_alloc_fail = e ? atoi(e) : -1;
-        g_alloc_count = 0;
-    }
+    g_alloc_fail = env_int("NVQA_FAIL_ALLOC", -1);
+    g_alloc_count = 0;
     const nvqa_dims &d = c->d;
     c->TS = d.arch == NVQA_ARCH1 ? d.T : d.T + 2;
     const size_t B = d.B, R = d.R, E = d.E, L = d.L, TS = c->TS, TB = TS * B;
@@ -277,10 +267,7 @@ static int create_impl(nvqa_ctx *c)
     NVQA_TRY(dalloc(&c->ptok, TB));
     NVQA_TRY(dalloc(&c->tinfo, 2));
     { // token-segment index for the embedding gradient (kernels.h: k_tok_index)
-        const char *e = getenv("NVQA_EMB_SEG");
-        c->tok_seg = !(e && e[0] == '0');
-        e = getenv("NVQA_WGRAD_TR"); // 0: bf16 weight gradients through gemm_f32.h's BF mode (A/B runs)
-        c->wgrad_tr = !(e && e[0] == '0');
+        c->tok_seg = env_on("NVQA_EMB_SEG");
         const size_t VT = d.V + 1, slots = TB / NVQA_ES_SHORT + 2;
         NVQA_TRY(dalloc(&c->seg_start, VT + 1));
         NVQA_HIP(hipMemsetAsync(c->seg_start, 0, (VT + 1) * 4, c->s));
@@ -327,16 +314,12 @@ static int create_impl(nvqa_ctx *c)
     c->slab_floats = 8 * 4 * R * std::max<size_t>(std::max(R, E), 128);
     NVQA_TRY(dalloc(&c->slabs, c->slab_floats));
     NVQA_TRY(dalloc(&c->chain_slabs, (size_t)L * 2 * NVQA_BWD_ZMAX * ((B + 63) / 64 * 64) * ((R + 63) / 64 * 64)));
-    {   // NVQA_FOLD_I2H=0: layer 0's input projection as a separate time-batched GEMM (A/B runs of the per-level path)
-        const char *ef = getenv("NVQA_FOLD_I2H");
-        c->fold_i2h = !(ef && ef[0] == '0');
-    }
+    c->fold_i2h = env_on("NVQA_FOLD_I2H"); // 0: layer 0's input projection as a separate time-batched GEMM (A/B runs of the per-level path)
     {   // persistent forward LSTM (lstm_persist.h) where the shape is eligible; NVQA_PERSIST=0: one launch per wavefront level
-        const char *ep = getenv("NVQA_PERSIST");
-        c->persist_on = !(ep && ep[0] == '0');
-        { const char *e = getenv("NVQA_RIDE_GEMM"); c->ride_gemm_on = !(e && e[0] == '0'); }   // A/B switches of the ride-along jobs,
-        { const char *e = getenv("NVQA_TOK_IN_BPTT"); c->tok_in_bptt_on = !(e && e[0] == '0'); } // read here like the other switches
-        { const char *e = getenv("NVQA_RIDE_FWD"); c->ride_fwd_on = !(e && e[0] == '0'); }
+        c->persist_on = env_on("NVQA_PERSIST");
+        c->ride_gemm_on = env_on("NVQA_RIDE_GEMM");     // A/B switches of the ride-along jobs,
+        c->tok_in_bptt_on = env_on("NVQA_TOK_IN_BPTT"); // read here like the other switches
+        c->ride_fwd_on = env_on("NVQA_RIDE_FWD");
         hipDeviceProp_t prop;
         NVQA_HIP(hipGetDeviceProperties(&prop, c->device));
         c->num_cus = prop.multiProcessorCount;
@@ -347,25 +330,22 @@ static int create_impl(nvqa_ctx *c)
         NVQA_HIP(hipMemsetAsync(c->pf_ts, 0, 2048 * 8, c->s));
         NVQA_HIP(hipHostMalloc((void **)&c->h_pf_err, 8 * sizeof(unsigned), hipHostMallocDefault));
         memset(c->h_pf_err, 0, 32);
-        // persistent BPTT (lstm_persist_bwd2.h): default where the shape is eligible; NVQA_PERSIST_BWD=0: the
-        // per-level kernels
+        // persistent BPTT (lstm_persist_bwd2.h): default where the shape is eligible; NVQA_PERSIST_BWD set to a value that
+        // does not start with 1 (0, say): the per-level kernels
         const char *eb = getenv("NVQA_PERSIST_BWD");
-        c->persist_bwd_on = !eb ? -1 : (eb[0] == '1' ? 1 : 0);
+        c->persist_bwd_on = !eb || eb[0] == '1';
         if (d.R == 512 && L <= 2) {
             const size_t rbmax = (B + 63) / 64;
             c->pb_cnt_words = persist_bwd_counter_words(d, (int)TS);
             NVQA_TRY(dalloc(&c->pb_cnt, c->pb_cnt_words));
             NVQA_HIP(hipMemsetAsync(c->pb_cnt, 0, c->pb_cnt_words * 4, c->s));
             NVQA_TRY(dalloc(&c->pb_bias, L * rbmax * 4 * R));
-            const char *ebb = getenv("NVQA_BIAS_IN_BPTT"); // 0: the row blocks' sums are added by k_bias_sum launches (A/B runs)
-            if (!(ebb && ebb[0] == '0')) {
-                NVQA_TRY(dalloc(&c->pb_bias_cnt, L * 32));
-                NVQA_HIP(hipMemsetAsync(c->pb_bias_cnt, 0, L * 32 * 4, c->s));
-            }
+            NVQA_TRY(dalloc(&c->pb_bias_cnt, L * 32));
+            NVQA_HIP(hipMemsetAsync(c->pb_bias_cnt, 0, L * 32 * 4, c->s));
             if (L > 1) NVQA_TRY(dalloc(&c->pb_pup, (L - 1) * TS * B * R));
         }
         { const char *es = getenv("NVQA_PF_SPIN"); c->pf_spin = es ? (unsigned)strtoul(es, nullptr, 0) : 0u; } // 0: the kernels' default
-        { const char *es = getenv("NVQA_PF_SPIN_STEPS"); c->pf_spin_steps = es ? atoi(es) : -1; } // tests: the limit above holds for the first n training steps only
+        c->pf_spin_steps = env_int("NVQA_PF_SPIN_STEPS", -1); // tests: the limit above holds for the first n training steps only
         NVQA_TRY(dalloc(&c->pf_sticky, 8));
         NVQA_HIP(hipMemsetAsync(c->pf_sticky, 0, 32, c->s));
         NVQA_TRY(dalloc(&c->dp_status, 4));
@@ -384,7 +364,7 @@ static int create_impl(nvqa_ctx *c)
         int RB = 0;
         const bool fwd = persist_rows(c) > 0, bwd = persist_bwd_rows(c, &RB) > 0;
         static bool said = false;
-        if ((!fwd || !bwd) && !said && d.R >= 256 && !(getenv("NVQA_QUIET") && atoi(getenv("NVQA_QUIET")))) {
+        if ((!fwd || !bwd) && !said && d.R >= 256 && !env_int("NVQA_QUIET", 0)) {
             fprintf(stderr, "[nvqa] note: R=%d E=%d L=%d B=%d is outside the persistent LSTM kernels' shapes (R = 512, E in {200, 512}%s): "
                             "forward %s, BPTT %s\n", d.R, d.E, d.L, d.B, d.L > 2 ? ", L <= 2 for the BPTT" : "",
                     fwd ? "persistent" : "per-level kernels", bwd ? "persistent" : "per-level kernels");
@@ -483,8 +463,8 @@ static float loss_mean_host(const nvqa_ctx *c)
 
 static int check_persist(nvqa_ctx *c)
 {
-    static const int ts_dbg = [] { const char *a = getenv("NVQA_PF_DBG"), *b = getenv("NVQA_PB_DBG"); return ((a ? atoi(a) : 0) | (b ? atoi(b) : 0)) & 32; }();
-    static const int seg_dbg = [] { const char *a = getenv("NVQA_PF_DBG"); return (a ? atoi(a) : 0) & 128; }();
+    static const int ts_dbg = (env_int("NVQA_PF_DBG", 0) | env_int("NVQA_PB_DBG", 0)) & 32;
+    static const int seg_dbg = env_int("NVQA_PF_DBG", 0) & 128;
     if (seg_dbg && c->pf_ts) { // measurement only (lstm_persist_fwd3.h): shader cycles per chain-step in four segments, per layer, once
         static int left = 3;
         if (left > 0 && --left == 0) {
@@ -538,13 +518,13 @@ static int check_persist(nvqa_ctx *c)
         }
         if (c->h_pf_err[4]) {
             snprintf(bwd, sizeof(bwd), "persistent BPTT kernel: workgroup %u timed out waiting (code 0x%x, value seen %u)", c->h_pf_err[7], c->h_pf_err[4], c->h_pf_err[6]);
-            c->persist_bwd_on = 0;
+            c->persist_bwd_on = false;
         }
         set_error("%s%s%s; results of that step are invalid and were not applied", fwd, fwd[0] && bwd[0] ? "; " : "", bwd);
         memset(c->h_pf_err, 0, 32);
         (void)hipMemsetAsync(c->pf_sticky, 0, 32, c->s); // reported: k_rmsprop may apply gradients again
         if (c->comm) { // the same switches and the same cleared status words as the ranks that only see the exchanged count (below)
-            c->persist_on = false; c->persist_bwd_on = 0;
+            c->persist_on = false; c->persist_bwd_on = false;
             if (c->h_dp_status) c->h_dp_status[0] = c->h_dp_status[1] = 0.f;
         }
         return -3;
@@ -554,7 +534,7 @@ static int check_persist(nvqa_ctx *c)
         set_error("data parallel: the persistent LSTM kernel of %d rank(s) timed out in an earlier step; no rank applied that step's gradients",
                   (int)(c->h_dp_status[0] != 0.f ? c->h_dp_status[0] : c->h_dp_status[1]));
         c->h_dp_status[0] = c->h_dp_status[1] = 0.f;
-        c->persist_on = false; c->persist_bwd_on = 0; // every rank sees the same sum: all of them leave the persistent path together
+        c->persist_on = false; c->persist_bwd_on = false; // every rank sees the same sum: all of them leave the persistent path together
         return -3;
     }
     return 0;
@@ -736,7 +716,6 @@ static int wgrad_bf16(nvqa_ctx *c, const float *A, const unsigned short *A16, in
     const int tiles = ((M + NVQA_WB_BM - 1) / NVQA_WB_BM) * ((N + NVQA_WB_BN - 1) / NVQA_WB_BN);
     int ks = 1;
     while (ks < 16 && tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2; // measured (round 2): 2048 x 512: 8 slices, 2048 x 200: 16
-    { static const int ks_env = [] { const char *e = getenv("NVQA_WB_KS"); return e ? atoi(e) : 0; }(); if (ks_env > 0) ks = ks_env; } // (sweeps)
     if ((size_t)ks * M * N > c->slab_floats) ks = std::max<int>(1, (int)(c->slab_floats / ((size_t)M * N)));
     int kslice = ((K + ks - 1) / ks + NVQA_WB_BK - 1) / NVQA_WB_BK * NVQA_WB_BK;
     ks = (K + kslice - 1) / kslice;
@@ -771,7 +750,7 @@ static int wgrad_bf16(nvqa_ctx *c, const float *A, const unsigned short *A16, in
 static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb, int M, int N, int K,
                  float *dW, float *slabs, hipStream_t st, const unsigned short *A16 = nullptr, const unsigned short *B16 = nullptr)
 {
-    if (c->bf16 && c->wgrad_tr && M % 4 == 0 && N % 4 == 0) return wgrad_bf16(c, A, A16, lda, Bm, B16, ldb, M, N, K, dW, slabs, st);
+    if (c->bf16 && M % 4 == 0 && N % 4 == 0) return wgrad_bf16(c, A, A16, lda, Bm, B16, ldb, M, N, K, dW, slabs, st);
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
     int ks = 1;
     while (ks < 16 && tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2; // tools/kbench11: 2048 x 200 x 13312: 16 slices 115 us, 8 slices 129 us
@@ -807,7 +786,6 @@ static int lstm_forward(nvqa_ctx *c, const Drop &dr)
     const int B = d.B, R = d.R, L = d.L, TS = c->TS, TB = TS * B;
     c->img_fwd_valid = c->img_bwd_valid = false;
     c->pb_bias_rb = 0;
-    c->pb_bias_done = false;
     if (const int MT = persist_rows(c)) { c->img_fwd_valid = c->bf16; return lstm_forward_persist(c, dr, MT); }
     // Layer 0 takes W_i2h x_t as a first K segment inside the level kernel, like the layers above it: the
     // time-batched projection (0.128 ms, a 109 MB write and its re-read by the level epilogues) costs more than
@@ -863,8 +841,7 @@ static int lstm_forward(nvqa_ctx *c, const Drop &dr)
             ++np;
         }
         ProfScope ps(c, PF_LSTM_FWD, flops, bytes);
-        static const int fwd_map = [] { const char *e = getenv("NVQA_FWD_MAP"); return e ? atoi(e) : 0; }();
-        ma.xcd = fwd_map;
+        ma.xcd = 0;
         if (c->bf16) NVQA_HIP((launch_gemm_multi<WithBF<CfgLstmFwd>::type, A_KC, B_KC, true, EpiLstmFwd, 1>(c->s, ma, np)));
         else NVQA_HIP((launch_gemm_multi<CfgLstmFwd, A_KC, B_KC, true, EpiLstmFwd, 1>(c->s, ma, np)));
     }
@@ -886,10 +863,9 @@ static int lstm_backward(nvqa_ctx *c, const Drop &dr)
     }
     // ragged arch1 batches (or lengths known only on the device): the products pick their split-K depth from nrows[s] on
     // the device -- a level with 2 of 8 row tiles active runs 16 short K slices instead of 4 long ones; the launch's workgroups are
-    // re-dealt over (active row tile, column tile, slice).  NVQA_BWD_ZADAPT=0 switches it off.
+    // re-dealt over (active row tile, column tile, slice).
     c->dct_zero = false; // (the per-level finisher carries the cell gradient in dCT, in place)
-    static const bool zad_on = [] { const char *e = getenv("NVQA_BWD_ZADAPT"); return !(e && e[0] == '0'); }();
-    const bool zad = zad_on && d.arch == NVQA_ARCH1 && !c->batch_uniform && (4 * R) % (NVQA_BWD_ZMAX * 32) == 0;
+    const bool zad = d.arch == NVQA_ARCH1 && !c->batch_uniform && (4 * R) % (NVQA_BWD_ZMAX * 32) == 0;
     const int Zl = zad ? NVQA_BWD_ZMAX : NVQA_BWD_Z;
     for (int dg = 0; dg < TS + L - 1; ++dg) {
         // diagonal dg: layer l (from the top: j = L-1-l) at step s = TS-1 - (dg - j).
@@ -945,10 +921,9 @@ static int lstm_backward(nvqa_ctx *c, const Drop &dr)
             ma.zsplit = NVQA_BWD_Z; ma.zadapt = zad ? NVQA_BWD_ZMAX : 0;
             // tile -> XCD map: (row half, column quarter) per XCD where the tile grid allows it (each L2 then sees half of
             // every dG and a quarter of every W: 0.3 % of the step against the natural order, in which every XCD reads all
-            // of dG -- 105 MB of fabric traffic per level, PMC); NVQA_BWD_MAP=0 restores the natural order
-            static const int bmap = [] { const char *e = getenv("NVQA_BWD_MAP"); return e ? atoi(e) : 3; }();
+            // of dG -- 105 MB of fabric traffic per level, PMC); elsewhere the XCD-folded order
             const bool grid2d = ((R + CfgBwdLevel::BN - 1) / CfgBwdLevel::BN) % 4 == 0 && ((B + CfgBwdLevel::BM - 1) / CfgBwdLevel::BM) % 2 == 0;
-            ma.xcd = bmap == 3 && grid2d && !zad ? 3 : xcd_order();
+            ma.xcd = grid2d && !zad ? 3 : 1;
             if (c->bf16) NVQA_HIP((launch_gemm_multi<WithBF<CfgBwdLevel>::type, A_KC, B_NC, false, EpiStore, 0>(c->s, ma, np)));
             else NVQA_HIP((launch_gemm_multi<CfgBwdLevel, A_KC, B_NC, false, EpiStore, 0>(c->s, ma, np)));
         }
@@ -987,16 +962,8 @@ static int lstm_wgrads(nvqa_ctx *c, int l)
                                        : (c->img_fwd_valid ? c->act_b16 + d.L * hs + l * us : nullptr);
     NVQA_TRY(wgrad(c, c->Gt[l], 4 * R, c->Hs[l], R, 4 * R, R, TB, c->G + c->lo.w_h2h[l], c->slabs, c->s, G16, H16));
     NVQA_TRY(wgrad(c, c->Gt[l], 4 * R, Xin, in, 4 * R, in, TB, c->G + c->lo.w_i2h[l], c->slabs, c->s, G16, X16));
-    if (c->pb_bias_rb > 0 && c->pb_bias_done) {
-        // the persistent BPTT kernel of this step wrote both bias gradients of every layer itself (its last workgroup per unit tile)
-    } else if (c->pb_bias_rb > 0) { // ... or left the column sums per row block (lstm_persist_bwd2.h; NVQA_BIAS_IN_BPTT=0)
-        ProfScope ps(c, PF_COLSUM, 0, (double)c->pb_bias_rb * 4 * R * 4);
-        hipLaunchKernelGGL(k_bias_sum, dim3((4 * R + 255) / 256), dim3(256), 0, c->s, c->pb_bias + (size_t)l * c->pb_bias_rb * 4 * R, c->pb_bias_rb,
-                           4 * R, c->G + c->lo.b_i2h[l], c->G + c->lo.b_h2h[l]);
-        NVQA_HIP(hipGetLastError());
-    } else {
-        NVQA_TRY(colsum(c, c->Gt[l], TB, 4 * R, 4 * R, c->G + c->lo.b_i2h[l], c->G + c->lo.b_h2h[l], c->s));
-    }
+    // (pb_bias_rb > 0: the persistent BPTT kernel of this step wrote both bias gradients of every layer itself, its last workgroup per unit tile)
+    if (c->pb_bias_rb == 0) NVQA_TRY(colsum(c, c->Gt[l], TB, 4 * R, 4 * R, c->G + c->lo.b_i2h[l], c->G + c->lo.b_h2h[l], c->s));
     NVQA_TRY(reduce_range(c, c->lo.w_i2h[l], c->lo.b_h2h[l] + 4 * (size_t)R - c->lo.w_i2h[l], 3 + l));
     return 0;
 }
@@ -1017,12 +984,6 @@ __global__ void k_transpose_to_bf16(const float *W, int rows, int cols, __bf16 *
     }
 }
 
-static bool dx0_b2_enabled() // NVQA_DX0_B2=0: d(layer-0 input) in the BF = 1 form (A/B runs)
-{
-    static const bool on = [] { const char *e = getenv("NVQA_DX0_B2"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 // dL/d(layer-0 input) for all steps at once; runs after the LSTM weight gradients so that their
 // all-reduce (data parallel) overlaps it.
 static int lstm_dx0(nvqa_ctx *c, float *dX0)
@@ -1033,8 +994,8 @@ static int lstm_dx0(nvqa_ctx *c, float *dX0)
     // bf16 mode behind the persistent BPTT kernel: dG exists as a bf16 image ([TS*B][4R], K-contiguous); with a transposed
     // bf16 image of W_i2h (made here, per step: the weights move) both operands are K-contiguous bf16 and the product runs
     // in the gfx950 form (BF = 2: bf16 LDS images, v_mfma_f32_16x16x32_bf16) instead of rounding f32 LDS images per MFMA.
-    // Same operand values, f32 accumulate, f32 result.  NVQA_DX0_B2=0: the BF = 1 form (A/B runs).
-    if (c->bf16 && c->img_bwd_valid && dx0_b2_enabled() && (4 * R) % 64 == 0) {
+    // Same operand values, f32 accumulate, f32 result.  (Without the dG image -- the per-level bf16 route -- the BF = 1 form below.)
+    if (c->bf16 && c->img_bwd_valid && (4 * R) % 64 == 0) {
         if (!c->wi2h0_img_step) { // (normally made by the embedding launch of this step: wi2h0_image_job)
             if (!c->wi2h0_t16) NVQA_HIP(hipMalloc((void **)&c->wi2h0_t16, (size_t)d.E * 4 * R * 2));
             hipLaunchKernelGGL(k_transpose_to_bf16, dim3((d.E + 31) / 32, (4 * R + 31) / 32), dim3(32, 8), 0, c->s, c->P + c->lo.w_i2h[0], 4 * R, d.E,
@@ -1045,7 +1006,7 @@ static int lstm_dx0(nvqa_ctx *c, float *dX0)
         g.B = reinterpret_cast<const float *>(c->wi2h0_t16); g.ldb = 4 * R / 2;
         g.M = TB; g.N = d.E; g.K = g.kslice = 4 * R / 2;
         g.mseg_limits = c->nrows; g.seg_rows = d.B;
-        g.xcd = d.arch == NVQA_ARCH1 && !c->batch_uniform ? 0 : xcd_order();
+        g.xcd = d.arch == NVQA_ARCH1 && !c->batch_uniform ? 0 : 1;
         if (d.E > 256) NVQA_HIP((launch_gemm<CfgDx0B, A_KC, B_KC, false, EpiStore>(c->s, g, EpiStore{dX0, d.E, 0})));
         else NVQA_HIP((launch_gemm<CfgDx0B64, A_KC, B_KC, false, EpiStore>(c->s, g, EpiStore{dX0, d.E, 0})));
         return 0;
@@ -1141,8 +1102,7 @@ static int emb_backward(nvqa_ctx *c, int VT, int NP, int T, const float *dX, con
 static int x0_image_begin(nvqa_ctx *c, int TB)
 {
     c->x0_img_valid = false;
-    static const bool on = [] { const char *e = getenv("NVQA_X0_B16"); return !(e && e[0] == '0'); }();
-    if (!c->bf16 || !on || c->d.E % 8) return 0;
+    if (!c->bf16 || c->d.E % 8) return 0;
     if (!c->x0_b16) NVQA_HIP(hipMalloc((void **)&c->x0_b16, (size_t)TB * c->d.E * 2));
     c->x0_img_valid = true;
     return 0;
@@ -1156,7 +1116,7 @@ static int wi2h0_image_job(nvqa_ctx *c, bool train, int first_block, TransposeJo
     c->wi2h0_img_step = false;
     int rb = 0;
     const int R = c->d.R, E = c->d.E;
-    if (!train || !c->bf16 || !dx0_b2_enabled() || (4 * R) % 64 || persist_bwd_rows(c, &rb) == 0) return 0;
+    if (!train || !c->bf16 || (4 * R) % 64 || persist_bwd_rows(c, &rb) == 0) return 0;
     if (!c->wi2h0_t16) NVQA_HIP(hipMalloc((void **)&c->wi2h0_t16, (size_t)E * 4 * R * 2));
     tj->W = c->P + c->lo.w_i2h[0]; tj->out = c->wi2h0_t16; tj->rows = 4 * R; tj->cols = E;
     tj->first_block = first_block; tj->nblocks = ((E + 31) / 32) * ((4 * R + 31) / 32);
@@ -2005,8 +1965,7 @@ extern "C" int nvqa_comm_init(nvqa_ctx *c, int rank, int world, const void *id)
         const char *eo = getenv("NVQA_DP_OVERLAP_BPTT");
         c->dp_overlap_bptt = eo && eo[0] == '1';
         c->comm_cus = 0;
-        const char *e = getenv("NVQA_COMM_CUS");
-        if (c->dp_overlap_bptt) c->comm_cus = e ? atoi(e) : 16;
+        if (c->dp_overlap_bptt) c->comm_cus = env_int("NVQA_COMM_CUS", 16);
         if (c->comm_cus > 0) {
             char buf[16];
             snprintf(buf, sizeof(buf), "%d", c->comm_cus);
@@ -2033,7 +1992,7 @@ extern "C" int nvqa_comm_init(nvqa_ctx *c, int rank, int world, const void *id)
     if (!r) return -1;
     {
         static bool said = false; // once per process: which collective library the data-parallel path runs on
-        if (!said && !(getenv("NVQA_QUIET") && atoi(getenv("NVQA_QUIET")))) {
+        if (!said && !env_int("NVQA_QUIET", 0)) {
             fprintf(stderr, "[nvqa] rank %d/%d: collective library %s\n", rank, world, r->resolved.c_str());
             said = true;
         }

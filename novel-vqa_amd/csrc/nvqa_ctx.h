@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "ride_jobs.h"
 #include <stdint.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -31,6 +32,10 @@ float ae_last_loss(const nvqa_ctx *c); // loss of the last nvqa_ae_step / nvqa_a
         int rc_ = (expr);              \
         if (rc_ != 0) return rc_;      \
     } while (0)
+
+// NVQA_* switches: on unless the value starts with '0' / the value's atoi, dflt when unset
+inline bool env_on(const char *name) { const char *e = getenv(name); return !(e && e[0] == '0'); }
+inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 // Kernel groups timed by HIP events (nvqa_profile_*); one entry per launch site family.
 enum ProfId {
@@ -176,11 +181,10 @@ struct nvqa_ctx {
     size_t pf_cnt_words = 0;
     unsigned long long *pf_ts = nullptr; // debug timestamps of the persistent kernels (NVQA_PF_DBG & 32)
     bool img_fwd_valid = false, img_bwd_valid = false; // this step's persistent bf16 kernels wrote act_b16 / dg_b16
-    bool wgrad_tr = true;              // bf16 weight gradients on the transposed-read kernel (wgrad_bf16.h)
     float *pb_bias = nullptr;     // [L][RB][4R] LSTM bias-gradient partial sums left by the persistent BPTT kernel
-    unsigned *pb_bias_cnt = nullptr; // [L][32] arrivals per (layer, unit tile): the last row block's workgroup writes the bias gradients (NVQA_BIAS_IN_BPTT=0: k_bias_sum)
-    bool pb_bias_done = false;    // this step's persistent BPTT launch wrote b_i2h / b_h2h of every layer itself
-    int pb_bias_rb = 0;           // row blocks of this step's partial sums (0: none: lstm_wgrads runs the column-sum kernels)
+    unsigned *pb_bias_cnt = nullptr; // [L][32] arrivals per (layer, unit tile): the last row block's workgroup writes the bias gradients
+    int pb_bias_rb = 0;           // row blocks of this step's partial sums; > 0: the persistent BPTT launch wrote b_i2h / b_h2h of every
+                                  // layer itself (0: lstm_wgrads runs the column-sum kernels)
     bool wi2h0_img_step = false;         // ... made by this step's embedding launch (else lstm_dx0 makes it)
     unsigned short *wi2h0_t16 = nullptr; // bf16 image of W_i2h[0]^T ([E][4R]) for the gfx950-form d(input) product, remade every step
     unsigned short *dg_b16 = nullptr;  // bf16 image of dG for the persistent BPTT kernel's bf16 instance (lstm_persist_bwd2.h)
@@ -192,7 +196,7 @@ struct nvqa_ctx {
     int pf_spin_steps = -1;       // NVQA_PF_SPIN_STEPS: training steps the NVQA_PF_SPIN limit still applies to (-1: all; a test knob)
     unsigned *pf_sticky = nullptr; // device: first failure of a persistent kernel since the host last looked (persist_fwd.hip: k_err_latch)
     float *dp_status = nullptr, *h_dp_status = nullptr; // data parallel: [0] = ranks whose persistent kernel gave up in this step (summed by the exchange)
-    int persist_bwd_on = -1;       // BPTT as one persistent launch (lstm_persist_bwd2.h)
+    bool persist_bwd_on = true;   // BPTT as one persistent launch (lstm_persist_bwd2.h); NVQA_PERSIST_BWD, read by nvqa_create
     unsigned *pb_cnt = nullptr;   // its counters + err record
     size_t pb_cnt_words = 0;
     float *pb_pup = nullptr;      // [L-1][TS*B][R] products handed from the UP role to the cells of the layer below

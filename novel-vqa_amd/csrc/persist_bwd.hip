@@ -25,9 +25,7 @@ size_t persist_bwd_counter_words(const nvqa_dims &d, int TS)
 int persist_bwd_rows(const nvqa_ctx *c, int *RB)
 {
     const nvqa_dims &d = c->d;
-    // NVQA_PERSIST_BWD: 1 on, 0 off (the per-level kernels); unset: on
-    const bool on = c->persist_bwd_on < 0 ? true : c->persist_bwd_on > 0;
-    if (!persist_rows(c) || !on || d.L > 2 || !c->pb_cnt) return 0;
+    if (!persist_rows(c) || !c->persist_bwd_on || d.L > 2 || !c->pb_cnt) return 0;
     const int mtiles = (d.B + 15) / 16, NU = d.R / (16 * persist_bwd_ntn(c)), MT = d.L == 1 || c->bf16 ? 4 : 7;
     *RB = (mtiles + MT - 1) / MT;
     if ((2 * d.L - 1) * *RB * NU > c->num_cus || c->num_cus < 256 || (2 * d.L - 1) * *RB > 8 * (32 / NU)) return 0;
@@ -80,7 +78,7 @@ int lstm_backward_persist(nvqa_ctx *c, const Drop &dr, int MT, int RB)
         if (!c->dg_b16) NVQA_HIP(hipMalloc((void **)&c->dg_b16, (size_t)L * gs * 2));
     }
     const unsigned lim = c->pf_spin ? c->pf_spin : NVQA_PF_SPIN_LIMIT;
-    static const int dbg = [] { const char *e = getenv("NVQA_PB_DBG"); return e ? atoi(e) : 0; }();
+    static const int dbg = env_int("NVQA_PB_DBG", 0);
     const size_t n_rec = (size_t)L * RB * 2 * TS, n_up = (size_t)L * RB * 2 * NU * TS; // per half
     if (n_rec + n_up + 4 > c->pb_cnt_words) { set_error("persistent BPTT: counter block too small"); return -1; }
     c->pb_bias_rb = c->pb_bias ? RB : 0;
@@ -105,7 +103,7 @@ int lstm_backward_persist(nvqa_ctx *c, const Drop &dr, int MT, int RB)
     const int tiles_wg = ((B + 15) / 16 + RB - 1) / RB;
     const double len_scale = d.arch == NVQA_ARCH1 && !c->batch_uniform ? 0.47 + 0.53 * std::min(1.f, std::max(0.f, c->batch_len_frac)) : 1.0;
     const double bptt_ms = 1e-3 * TS * (c->bf16 ? 16.0 : 31.0) * (L == 1 ? 0.62 : 1.0) * std::min(1.0, tiles_wg / (c->bf16 ? 4.0 : 7.0)) * len_scale;
-    static const double ride_cap = [] { const char *e = getenv("NVQA_RIDE_CAP"); return e ? atof(e) : 3.8; }(); // GFLOP per 0.90 ms and 16 riders
+    constexpr double ride_cap = 3.8; // GFLOP per 0.90 ms and 16 riders
     // (round 4: 3.4 -> 3.8 with the direct-operand kernel: the 3.2 GFLOP of dW_o + dW_q still end before its roles do -- measured: step 2.926 ms with
     // them riding, 2.969 with them behind the launch -- and the launch estimate above shrank with the kernel)
     const double cap_flops = 1e9 * ride_cap * (bptt_ms / 0.90) * (n_idle / 16.0);
@@ -141,10 +139,9 @@ int lstm_backward_persist(nvqa_ctx *c, const Drop &dr, int MT, int RB)
         a.dr = dr; a.spin_limit = lim; a.dbg = dbg;
         a.cnt_rec = c->pb_cnt; a.cnt_up = c->pb_cnt + n_rec; a.err = err;
         a.bias_part = c->pb_bias;
-        if (c->pb_bias && c->pb_bias_cnt) { // the kernel's last workgroup per (layer, unit tile) writes the bias gradients itself
+        if (c->pb_bias) { // the kernel's last workgroup per (layer, unit tile) writes the bias gradients itself
             a.bias_cnt = c->pb_bias_cnt;
             for (int l = 0; l < L; ++l) { a.bias_i[l] = c->G + c->lo.b_i2h[l]; a.bias_h[l] = c->G + c->lo.b_h2h[l]; }
-            c->pb_bias_done = true;
         }
         a.ts = c->pf_ts + 1024;
         if (take_jobs) {
@@ -178,7 +175,7 @@ int lstm_backward_persist(nvqa_ctx *c, const Drop &dr, int MT, int RB)
     } while (0)
         // f32: the direct-operand kernel (0.89 -> 0.81 ms); bf16: round 3's ring kernel is still the faster one (0.46 against 0.54 ms:
         // DESIGN.md section 4.6 says where the direct form loses in that mode).  NVQA_BWD_KERNEL=2 / 3 forces one of them.
-        static const int ver_env = [] { const char *e = getenv("NVQA_BWD_KERNEL"); return e ? atoi(e) : 0; }();
+        static const int ver_env = env_int("NVQA_BWD_KERNEL", 0);
         const int ver = ver_env ? ver_env : (c->bf16 ? 2 : 3);
         if (ver == 2) { // (the ring kernel's instances live in a translation unit of their own: persist_bwd_ring.hip)
             NVQA_TRY(launch_persist_bwd_ring(c, a, grid, MT, rag));

@@ -130,7 +130,7 @@ int lstm_forward_persist(nvqa_ctx *c, const Drop &dr, int MT)
     a.RB = (B + 16 * MT - 1) / (16 * MT); a.NU = R / 16;
     a.h0_top = d.arch == NVQA_ARCH2 && (c->quirks & NVQA_QUIRK_H0) ? 1 : 0;
     a.dr = dr;
-    { static const int dbg = [] { const char *e = getenv("NVQA_PF_DBG"); return e ? atoi(e) : 0; }(); a.dbg = dbg; }
+    { static const int dbg = env_int("NVQA_PF_DBG", 0); a.dbg = dbg; }
     a.spin_limit = c->pf_spin ? c->pf_spin : NVQA_PF_SPIN_LIMIT;
     a.cnt = c->pf_cnt; a.err = c->pf_cnt + c->pf_cnt_words - 4; // the last 16 bytes of the block
     a.ts = c->pf_ts;
@@ -153,7 +153,7 @@ int lstm_forward_persist(nvqa_ctx *c, const Drop &dr, int MT)
     const bool rag = d.arch == NVQA_ARCH1 && !c->batch_uniform;
     // NVQA_FWD_KERNEL: 1 = round 2's LDS-ring kernel (lstm_persist.h), 3 = round 4's direct-operand kernel (lstm_persist_fwd3.h;
     // default where it has an instance: f32, row blocks of 8 row tiles, equal-length batches)
-    static const int fwd_kernel = [] { const char *e = getenv("NVQA_FWD_KERNEL"); return e ? atoi(e) : 0; }();
+    static const int fwd_kernel = env_int("NVQA_FWD_KERNEL", 0);
     if (fwd_kernel != 1 && persist_fwd3_eligible(c, MT, rag)) {
         NVQA_TRY(launch_persist_fwd3(c, a, grid, rag));
         NVQA_TRY(persist_latch_err(c, c->pf_cnt, c->pf_cnt_words, 0));

@@ -40,10 +40,7 @@ static int launch_persist_fwd3_t(nvqa_ctx *c, const PersistFwdArgs &a, int grid)
 //   0  lstm_persist.h's ring kernel, RAG instance (2.25 ms)
 static int ragged_mode()
 {
-    static const int m = [] {
-        const char *e = getenv("NVQA_FWD3_RAGGED");
-        return e ? atoi(e) : NVQA_FWD3_RAGGED_DEFAULT;
-    }();
+    static const int m = env_int("NVQA_FWD3_RAGGED", NVQA_FWD3_RAGGED_DEFAULT);
     return m;
 }
 

@@ -284,7 +284,7 @@ extern "C" int nvqa_vgg16_create(int device, int width_div, int input_hw, int ma
         NVQA_HIP(hipEventCreateWithFlags(&v->evCopy[p], hipEventDisableTiming));
     }
     NVQA_HIP(hipEventCreateWithFlags(&v->evDone, hipEventDisableTiming));
-    { const char *e = getenv("NVQA_VGG_CHUNK"); if (e && atoi(e) > 0) v->chunk = atoi(e); }
+    { const int n = env_int("NVQA_VGG_CHUNK", 0); if (n > 0) v->chunk = n; }
     for (int i = 0; i < 13; ++i) {
         NVQA_HIP(hipMalloc((void **)&v->Wc[i], (size_t)v->cout[i] * 9 * v->cinp[i] * 4));
         NVQA_HIP(hipMalloc((void **)&v->bc[i], (size_t)v->cout[i] * 4));
@@ -379,12 +379,6 @@ extern "C" int nvqa_vgg16_set_weights(nvqa_vgg *v, const float *flat)
     return 0;
 }
 
-static int xcd_order() // NVQA_XCD=0: natural tile order (A/B measurements)
-{
-    static const int v = [] { const char *e = getenv("NVQA_XCD"); return (e && e[0] == '0') ? 0 : 1; }();
-    return v;
-}
-
 // b16: x and W are bf16 arrays (the gfx950 form of fc6); K counts their elements
 static int fc_layer(nvqa_vgg *v, const float *x, int M, int K, const float *W, const float *b, float *out, bool b16 = false)
 {
@@ -396,7 +390,7 @@ static int fc_layer(nvqa_vgg *v, const float *x, int M, int K, const float *W, c
     ks = (K + kslice - 1) / kslice;
     GemmArgs g = {};
     g.A = x; g.lda = K; g.B = W; g.ldb = K; g.M = M; g.N = N; g.K = K; g.kslice = kslice;
-    g.xcd = xcd_order();
+    g.xcd = 1;
     if (b16) NVQA_HIP((launch_gemm<CfgFcB, A_KC, B_KC, false, EpiSlab>(v->s, g, EpiSlab{v->slabs, N, (size_t)M * N})));
     else if (v->bf16) NVQA_HIP((launch_gemm<WithBF<CfgFc>::type, A_KC, B_KC, false, EpiSlab>(v->s, g, EpiSlab{v->slabs, N, (size_t)M * N})));
     else NVQA_HIP((launch_gemm<CfgFc, A_KC, B_KC, false, EpiSlab>(v->s, g, EpiSlab{v->slabs, N, (size_t)M * N})));
@@ -419,7 +413,7 @@ static int vgg_network(nvqa_vgg *v, const float *img, int n, float *out)
         g.A = cur; g.B = v->Wc[i]; g.ldb = 9 * v->cinp[i];
         g.M = n * H * W; g.N = v->cout[i]; g.K = 9 * v->cinp[i]; g.kslice = g.K;
         g.cH = H; g.cW = W; g.cC = v->cinp[i];
-        g.xcd = xcd_order(); // neighbouring pixel-row tiles (shared halo rows) and all C_out tiles of a row tile on one XCD
+        g.xcd = 1; // XCD-folded tile order: neighbouring pixel-row tiles (shared halo rows) and all C_out tiles of a row tile on one XCD
         // output channel stride = padded C_out, so that the next layer reads float4 channels; the pad
         // channels must be zero: they are written by nobody, so clear once when padding exists
         const int ldc = v->coutp[i];

@@ -1,12 +1,12 @@
 #!/bin/bash
-# Round-3 profile set (run on the GPU box from the repo root): kernel statistics, HBM traffic (FETCH_SIZE / WRITE_SIZE in
-# separate passes, MI355X_MICROARCH.md), matrix-pipe busy cycles, wave-cycle shares.  Results -> out/prof_r03/,
-# summaries -> profiles/r03_*.  The program after `--` is python3 itself (no env / bash hop under rocprofv3).
-# usage: profile_r03.sh [tag [bench flags]]   e.g.  profile_r03.sh bf16_arch2 "--arch 2 --bf16"
+# Round-4 profile set (run on the GPU box from the repo root): kernel statistics, HBM traffic (FETCH_SIZE / WRITE_SIZE in
+# separate passes, MI355X_MICROARCH.md), matrix-pipe busy cycles, wave-cycle shares.  Results -> out/prof_r04/,
+# summaries -> profiles/r04_*.  The program after `--` is python3 itself (no env / bash hop under rocprofv3).
+# usage: profile.sh [tag [bench flags]]   e.g.  profile.sh bf16_arch2 "--arch 2 --bf16"
 set -e
+R=$(cd "$(dirname "$0")/../.." && pwd) # the repository root
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
-O=$R/out/prof_r03${1:+_$1}
+O=$R/out/prof_r04${1:+_$1}
 mkdir -p $O
 B="python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $2"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B > $O/bench_under_rocprof.json 2> $O/stats.log

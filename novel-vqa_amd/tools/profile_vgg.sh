@@ -1,10 +1,10 @@
 #!/bin/bash
 # Round-3 extractor profile (GPU box, from the repo root): per-layer durations, matrix-pipe busy cycles, wave-cycle shares and
-# HBM traffic of tools/bench_vgg.py.  usage: profile_vgg_r03.sh [tag [batch [bench_vgg flags]]]
+# HBM traffic of tools/bench_vgg.py.  usage: profile_vgg.sh [tag [batch [bench_vgg flags]]]
 set -e
+R=$(cd "$(dirname "$0")/../.." && pwd) # the repository root
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
-O=$R/gpurun_out/prof_vgg_r03${1:+_$1}
+O=$R/out/prof_vgg_r03${1:+_$1}
 mkdir -p $O
 B="python3 $R/novel-vqa_amd/tools/bench_vgg.py ${2:-32} 2 $3"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B > $O/bench_vgg.json 2> $O/stats.log

@@ -171,3 +171,33 @@ def test_lua_scripts_call_the_abi_with_the_declared_arity_and_balance_their_bloc
         closes = len(re.findall(r"\bend\b", code))
         assert opens == closes, f"{fn}: {opens} block openers, {closes} 'end'"
         assert len(re.findall(r"\brepeat\b", code)) == len(re.findall(r"\buntil\b", code))
+
+
+def test_integration_switch_table_lists_exactly_the_switches_read():
+    """INTEGRATION.md section 5's switch table names every NVQA_* environment variable the library (getenv and its helpers
+    env_on / env_int), the Python host side and bench.py (os.environ) and the Lua binding (os.getenv) read -- and nothing else."""
+    pkg_dir = os.path.join(ROOT, "novel-vqa_amd")
+    name = r"(NVQA_[A-Z0-9_]+)"
+    read = set()
+    csrc = os.path.join(pkg_dir, "csrc")
+    for f in sorted(os.listdir(csrc)):
+        text = re.sub(r"/\*.*?\*/", "", open(os.path.join(csrc, f)).read(), flags=re.S)
+        read |= set(re.findall(r'\b(?:getenv|env_on|env_int)\(\s*"%s"' % name, re.sub(r"//[^\n]*", "", text)))
+    host = os.path.join(pkg_dir, "host")
+    py = [os.path.join(host, f) for f in sorted(os.listdir(host)) if f.endswith(".py")] + [os.path.join(ROOT, "bench.py")]
+    for p in py:
+        read |= set(re.findall(r"""\bos\.environ(?:\.get\(|\[)\s*["']%s["']""" % name, open(p).read()))
+    lua = os.path.join(pkg_dir, "lua")
+    for f in sorted(os.listdir(lua)):
+        if f.endswith(".lua"):
+            read |= set(re.findall(r"""\bos\.getenv\(\s*["']%s["']""" % name, open(os.path.join(lua, f)).read()))
+    assert {"NVQA_PERSIST", "NVQA_BENCH_NPROF", "NVQA_LIB"} <= read  # one of each kind of reader: the patterns still match
+
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read().splitlines()
+    head = next(i for i, l in enumerate(doc) if l.startswith("| env switch"))
+    listed = set()
+    for l in doc[head + 2:]:
+        if not l.startswith("|"):
+            break
+        listed |= set(re.findall(name, l.split("|")[1]))
+    assert listed == read, {"read but not listed": sorted(read - listed), "listed but not read": sorted(listed - read)}

@@ -32,7 +32,7 @@ def test_reference_default_batch_500(pkg, orc, name):
     params = orc.synth_params(d)
     batch = orc.synth_batch(d, seed=21, full_length=full, min_len=3)
     ctx = _ctx(pkg, d)
-    import os   # (the fallback runs of tools/gpu/r4_fallbacks.sh switch the persistent kernels off on purpose)
+    import os   # (the fallback runs of the suite, NVQA_PERSIST=0 / NVQA_PERSIST_BWD=0, switch the persistent kernels off on purpose)
     fwd = os.environ.get("NVQA_PERSIST", "1") != "0"
     assert ctx.persistent_state() == {"fwd": fwd, "bwd": fwd and os.environ.get("NVQA_PERSIST_BWD", "1") != "0"}   # the fast path is what is being held
     ctx.set_params(params)

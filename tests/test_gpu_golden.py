@@ -38,7 +38,7 @@ def test_gpu_matches_golden(pkg, orc, name):
     x = ctx.get_params()
     # (2e-6: the first RMSprop step moves every parameter by lr / sqrt(1 - alpha) = 3e-3 times the SIGN of its gradient, so an entry
     # whose gradient is at f32 noise level moves by a noise-sized fraction of that; measured 1.0005e-6 of the largest parameter on
-    # the per-level BPTT route (NVQA_PERSIST_BWD=0, tools/gpu/r4_fallbacks.sh) with the 1e-6 this line used to ask for)
+    # the per-level BPTT route (NVQA_PERSIST_BWD=0, a fallback run of the suite) with the 1e-6 this line used to ask for)
     assert relmax(x[:64], g["params_after_head"]) < 2e-6 and relmax(x[-64:], g["params_after_tail"]) < 2e-6
     scores, argmax = ctx.forward(tok, lens if d.arch == 1 else None, img)
     ctx.close()
