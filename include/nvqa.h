@@ -44,10 +44,12 @@ extern "C" {
 #define NVQA_ARCH2 2 /* 003_train_vqa_arch2: image-as-first-token nn.Encoder, Linear(R,A) head */
 #define NVQA_ARCH_AE1 3 /* 001_train_autoencoder/001_train_arch1_text_autoencoder.lua: LSTM text auto-encoder
                          * (misc/AutoEncoder_text_nostart.lua); dims T = seq_length D, I = C = A = 0 */
+#define NVQA_ARCH_AE2 4 /* 001_train_autoencoder/001_train_arch2_text_autoencoder.lua: image-first-token LSTM auto-encoder
+                         * (misc/AutoEncoder.lua); dims as NVQA_ARCH_AE1, the image row is E wide */
 
 /* Model dimensions (SURVEY.md symbol table). */
 typedef struct nvqa_dims {
-    int32_t arch; /* NVQA_ARCH1 | NVQA_ARCH2 | NVQA_ARCH_AE1 */
+    int32_t arch; /* NVQA_ARCH1 | NVQA_ARCH2 | NVQA_ARCH_AE1 | NVQA_ARCH_AE2 */
     int32_t B;    /* minibatch (QA pairs) per device             -batch_size          */
     int32_t T;    /* question buffer length (columns of ques_*)  buffer_size_q        */
     int32_t V;    /* question vocabulary size                    vocabulary_size_q    */
@@ -90,7 +92,8 @@ int nvqa_sync(nvqa_ctx *ctx); /* wait for all enqueued work (loss_out becomes va
  *  arch2 multimodal: W_o[A x R], b_o[A]
  *  ae1 encoder     : LSTM layers as above (AutoEncoder_text_nostart.lua:89-110 parameters() order)
  *  ae1 decoder     : LSTM layers as above, then W_proj[(V+1) x R], b_proj[V+1]
- *  ae1 lookup      : W_lk[(V+1) x E] (row V+1 = the START / END token)                */
+ *  ae1 lookup      : W_lk[(V+1) x E] (row V+1 = the START / END token)
+ *  ae2             : as ae1 (AutoEncoder.lua:86-107 parameters() order)                          */
 size_t nvqa_param_count(const nvqa_ctx *ctx);
 int nvqa_segments(const nvqa_ctx *ctx, size_t sizes_out[3]);
 int nvqa_init_params(nvqa_ctx *ctx, uint64_t seed, float lo, float hi);
@@ -233,7 +236,7 @@ int nvqa_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const float *images, const in
                      const int32_t *lengths, const int32_t *labels, const nvqa_dropout *dropout,
                      float *loss_out);
 
-/* ---- text auto-encoder (NVQA_ARCH_AE1 contexts) ---- */
+/* ---- text auto-encoder (NVQA_ARCH_AE1 / NVQA_ARCH_AE2 contexts) ---- */
 /* On an auto-encoder context nvqa_step*, nvqa_forward, nvqa_evaluate, nvqa_set_fusion, nvqa_set_ref_quirks,
  * nvqa_dataset_load, nvqa_comm_init and nvqa_set_precision(ctx, 1) return an error.
  * One training forward + LanguageModelCriterion + backward (lossFun of 001_train_arch1_text_autoencoder.lua:212-245):
@@ -244,6 +247,14 @@ int nvqa_ae_step(nvqa_ctx *ctx, const int32_t *tokens, const nvqa_dropout *dropo
  * greedy decoding (sample() with sample_max = 1, AutoEncoder_text_nostart.lua:134-210): 1-based tokens, V+1 = END.
  * The encoder sees the tokens as the training forward does (0 -> 1, up to the batch's last non-null column). */
 int nvqa_ae_evaluate(nvqa_ctx *ctx, int32_t n, const int32_t *tokens, float *loss_out, int32_t *samples_out);
+/* NVQA_ARCH_AE2 (misc/AutoEncoder.lua): the encoder runs image row, START, then the tokens; the decoder is AE1's.
+ * On an AE2 context nvqa_ae_step / nvqa_ae_evaluate are the calls below with images = NULL (the text script's zero rows);
+ * on an AE1 context the calls below return an error.  images [B x E] (evaluate: [n x E]) or NULL = zeros.
+ * dimages_out [B x E] (may be NULL) = d(loss)/d(images), the encoder's step-1 input gradient (updateGradInput, :405-414). */
+int nvqa_ae_step_images(nvqa_ctx *ctx, const float *images, const int32_t *tokens, const nvqa_dropout *dropout,
+                        float *loss_out, float *dimages_out);
+int nvqa_ae_evaluate_images(nvqa_ctx *ctx, int32_t n, const float *images, const int32_t *tokens, float *loss_out,
+                            int32_t *samples_out);
 /* Valid on every context.  One pass over the flat vector: g = clamp(g, -clamp, clamp) (clamp > 0), g += wd * x, then
  * adam() of misc/optim_updates.lua:78-111 (step counter held by the context, reset by nvqa_init_params).
  * stats_out (may be NULL; synchronises) = {||x||_2, count(|lr g| >= 0.01 |x|)} of x before the update, g after clamp + wd

@@ -21,6 +21,10 @@
  *   NVQA_SITE_AE_DEC_LK   decoder lookup        idx = (b*(D+1) + s)*E + e
  *   NVQA_SITE_AE_TOP      decoder top h         idx = (b*(D+1) + s)*R + j
  *   NVQA_SITE_AE_LSTM     input of layer l >= 1 idx = (((k*L + l)*B + b)*(D+1) + t)*R + j
+ * Image-first-token auto-encoder (NVQA_ARCH_AE2): the encoder runs up to D+2 steps (image, START, tokens), so the
+ * step stride is D+2; the lookup is a plain LookupTable and draws no mask (no ENC_LK / DEC_LK):
+ *   NVQA_SITE_AE_TOP      decoder top h         idx = (b*(D+2) + s)*R + j
+ *   NVQA_SITE_AE_LSTM     input of layer l >= 1 idx = (((k*L + l)*B + b)*(D+2) + t)*R + j   (encoder t = 0..D+1)
  */
 #ifndef NVQA_RNG_H
 #define NVQA_RNG_H

@@ -10,6 +10,13 @@
 // Layout of one step (B rows, tmax = last column of the batch with a non-null token, Q = 2 tmax + 1 chain steps):
 //   chain step q < tmax      : encoder step q                 (input: lookup of tok[:, q], 0 -> 1)
 //   chain step q = tmax + s  : decoder step s, s = 0 .. tmax   (input: START, then lookup of tok[:, s-1], 0 -> 1)
+// The image-first-token auto-encoder (NVQA_ARCH_AE2, misc/AutoEncoder.lua with 001_train_arch2_text_autoencoder.lua) runs
+// the same chain with te = tmax + 2 encoder steps (Q = 2 tmax + 3):
+//   chain step 0             : encoder step 0: the image row [B x E] (zeros in the text script)
+//   chain step 1             : encoder step 1: START
+//   chain step q in [2, te)  : encoder step q: lookup of tok[:, q-2], 0 -> 1
+//   chain step q = te + s    : decoder step s, as above
+// with a plain LookupTable (no Dropout, no Tanh), and d(images) = layer 0's d(input) rows of chain step 0.
 // Per layer, one array of states over the whole chain (slot 0 = the zero initial state, slot q+1 = after chain step q):
 // the decoder's initial state IS the encoder's final slot, and in the backward pass the decoder's state gradient at its
 // step 0 flows into the encoder's last step through the ordinary recurrent product, with the encoder's W_h2h replaced by
@@ -32,9 +39,15 @@ using namespace nvqa;
 namespace nvqa {
 
 struct AeState {
-    int D = 0, QM = 0;   // seq_length; chain steps the buffers hold (2 D + 1)
+    bool ae2 = false;    // NVQA_ARCH_AE2: image row and START in front of the encoder's tokens
+    int D = 0, QM = 0;   // seq_length; chain steps the buffers hold (AE1 2 D + 1, AE2 2 D + 3)
     int ldl = 0;         // leading dimension of the logits (V + 1 rounded up to 4 floats; the padding columns stay zero)
     int tmax = 0;        // last step's tmax
+    int te = 0;          // last step's encoder steps = the chain step of decoder step 0 (AE1 tmax, AE2 tmax + 2)
+    int dstr = 0;        // the D of the dropout counter indices (AE1 D, AE2 D + 1: a step stride of D + 2, nvqa_rng.h)
+    float *img = nullptr;       // AE2: [B x E] image rows of the current batch (device); NULL input -> img_live = false
+    float *h_img = nullptr;     // AE2: pinned staging of the image rows
+    bool img_live = false;
     int32_t *tok = nullptr;     // [B x D] tokens of the current batch (device)
     int32_t *nrows = nullptr;   // device int = B (every row of the chain is active)
     int32_t *cur = nullptr;     // [B] greedy decoding: token fed at the next decoder step
@@ -125,6 +138,32 @@ __global__ void k_ae_embed(const int32_t *tok, const int32_t *direct, int B, int
         const uint64_t idx = ae_lk_idx(b, q, tmax, D, E, e, &site);
         X0[(size_t)r * E + e] = tanhf(dr.scale(site, idx) * w[e]);
     }
+}
+
+// AE2 layer-0 input X0 of chain steps [q0, q0 + gridDim.x / B) in one pass (AutoEncoder.lua:258-291, :318-348): encoder step 0
+// = the image row (img; NULL: zeros), encoder step 1 and decoder step 0 = START (V+1), encoder step q >= 2 = lookup of
+// tok[:, q-2], decoder step s >= 1 = lookup of tok[:, s-1] (greedy decoding: of direct[b]); 0 -> 1.  A plain nn.LookupTable
+// (:28): no dropout, no tanh.  One workgroup per row.
+__global__ void k_ae2_assemble(const int32_t *tok, const int32_t *direct, const float *img, int B, int D, int V, int E, int te,
+                               int q0, const float *Wlk, float *X0)
+{
+    const int r = q0 * B + blockIdx.x, q = r / B, b = r % B;
+    float *x = X0 + (size_t)r * E;
+    const float *w;
+    if (q == 0) {
+        if (!img) {
+            for (int e = threadIdx.x; e < E; e += blockDim.x) x[e] = 0.f;
+            return;
+        }
+        w = img + (size_t)b * E;
+    } else {
+        int v;
+        if (q == 1 || q == te) v = V + 1;
+        else if (q < te) v = tok[(size_t)b * D + q - 2];
+        else v = direct ? direct[b] : tok[(size_t)b * D + q - te - 1];
+        w = Wlk + (size_t)((v == 0 ? 1 : v) - 1) * E;
+    }
+    for (int e = threadIdx.x; e < E; e += blockDim.x) x[e] = w[e];
 }
 
 // inter-layer / top-h dropout (forward: out = scale * in; backward: the same scale on the gradient).
@@ -350,6 +389,16 @@ __global__ void k_ae_lk_part(const int32_t *lk_start, const int32_t *lk_pos, con
         part[(size_t)blockIdx.x * E + e] = s;
     }
 }
+// AE2 (plain LookupTable): pass 1 is the plain sum of the chunk's d(input) rows
+__global__ void k_ae2_lk_part(const int32_t *lk_start, const int32_t *lk_pos, const float *dX, int E, float *part)
+{
+    const int p0 = lk_start[blockIdx.x], p1 = lk_start[blockIdx.x + 1];
+    for (int e = threadIdx.x; e < E; e += blockDim.x) {
+        float s = 0.f;
+        for (int p = p0; p < p1; ++p) s += dX[(size_t)lk_pos[p] * E + e];
+        part[(size_t)blockIdx.x * E + e] = s;
+    }
+}
 __global__ void k_ae_lk_sum(const int32_t *lk_tok, const int32_t *lk_tc, const float *part, int E, float *dW)
 {
     const int u = lk_tok[blockIdx.x], c0 = lk_tc[blockIdx.x], c1 = lk_tc[blockIdx.x + 1];
@@ -480,8 +529,10 @@ int ae_create(nvqa_ctx *c)
     c->ae = new AeState();
     AeState &a = *c->ae;
     const size_t B = d.B, D = d.T, E = d.E, R = d.R, L = d.L, V = d.V;
+    a.ae2 = d.arch == NVQA_ARCH_AE2;
     a.D = (int)D;
-    a.QM = (int)(2 * D + 1);
+    a.QM = (int)(2 * D + (a.ae2 ? 3 : 1));
+    a.dstr = (int)D + (a.ae2 ? 1 : 0);
     a.ldl = (int)((V + 1 + 3) / 4 * 4);
     const size_t QM = a.QM, total4 = (c->lo.total + 3) / 4 * 4; // (padding: nvqa_rmsprop_update runs over whole float4s)
     AE_ALLOC(c->P, total4);
@@ -503,6 +554,10 @@ int ae_create(nvqa_ctx *c)
     NVQA_HIP(hipHostMalloc((void **)&a.h_lk, (4 * QM * B + 4) * 4, hipHostMallocDefault));
     NVQA_HIP(hipHostMalloc((void **)&a.h_tok, B * D * 4, hipHostMallocDefault));
     NVQA_HIP(hipHostMalloc((void **)&a.h_loss, 16, hipHostMallocDefault));
+    if (a.ae2) {
+        AE_ALLOC(a.img, B * E);
+        NVQA_HIP(hipHostMalloc((void **)&a.h_img, B * E * 4, hipHostMallocDefault));
+    }
     AE_ALLOC(a.X0, QM * B * E);
     for (size_t l = 0; l < L; ++l) {
         AE_ALLOC(a.Gt[l], QM * B * 4 * R);
@@ -529,13 +584,13 @@ void ae_destroy(nvqa_ctx *c)
     if (!c->ae) return;
     AeState &a = *c->ae;
     void *ptrs[] = {a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
-                    a.logits, a.rowloss, a.loss, a.slabs, a.colpart};
+                    a.logits, a.rowloss, a.loss, a.slabs, a.colpart, a.img};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (int l = 0; l < NVQA_MAX_LAYERS; ++l)
         for (void *p : {(void *)a.Gt[l], (void *)a.Hs[l], (void *)a.Cs[l], (void *)a.U[l]})
             if (p) (void)hipFree(p);
-    for (void *p : {(void *)a.h_lk, (void *)a.h_tok, (void *)a.h_loss})
+    for (void *p : {(void *)a.h_lk, (void *)a.h_tok, (void *)a.h_loss, (void *)a.h_img})
         if (p) (void)hipHostFree(p);
     delete c->ae;
     c->ae = nullptr;
@@ -544,7 +599,7 @@ void ae_destroy(nvqa_ctx *c)
 // ------------------------------------------------------------------------------------------------------------------
 // forward / backward
 // ------------------------------------------------------------------------------------------------------------------
-// weights of chain step q: the encoder's below tmax, the decoder's from tmax on
+// weights of chain step q: the encoder's below te, the decoder's from te on
 static inline size_t w_i2h_of(const nvqa_ctx *c, int l, bool dec) { return dec ? c->lo.d_w_i2h[l] : c->lo.w_i2h[l]; }
 static inline size_t w_h2h_of(const nvqa_ctx *c, int l, bool dec) { return dec ? c->lo.d_w_h2h[l] : c->lo.w_h2h[l]; }
 
@@ -569,7 +624,7 @@ static int ae_fwd_step(nvqa_ctx *c, int l, int q, const Drop &dr)
 {
     AeState &a = *c->ae;
     const int B = c->d.B, R = c->d.R;
-    const bool dec = q >= a.tmax;
+    const bool dec = q >= a.te;
     ProfScope ps(c, PF_AE_LSTM_FWD, q > 0 ? 2.0 * B * 4 * R * R : 0.0);
     EpiLstmFwd e = {};
     e.gx = a.Gt[l] + (size_t)q * B * 4 * R;
@@ -594,7 +649,7 @@ static int ae_layer_input(nvqa_ctx *c, int l, int q0, int q1, const Drop &dr)
     const int B = c->d.B, R = c->d.R;
     const size_t n = (size_t)(q1 - q0) * B * R;
     hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s,
-                       a.Hs[l - 1] + (size_t)(q0 + 1) * B * R, a.U[l] + (size_t)q0 * B * R, n, R, B, a.D, c->d.L, l, a.tmax,
+                       a.Hs[l - 1] + (size_t)(q0 + 1) * B * R, a.U[l] + (size_t)q0 * B * R, n, R, B, a.dstr, c->d.L, l, a.te,
                        q0 * B, 0, dr);
     NVQA_HIP(hipGetLastError());
     return 0;
@@ -607,7 +662,7 @@ static int ae_project(nvqa_ctx *c, int s0, int s1, const Drop &dr)
     const int B = c->d.B, R = c->d.R, L = c->d.L, Vp1 = c->d.V + 1;
     const size_t n = (size_t)(s1 - s0) * B * R;
     hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s,
-                       a.Hs[L - 1] + (size_t)(a.tmax + 1 + s0) * B * R, a.Htd + (size_t)s0 * B * R, n, R, B, a.D, L, 0, 0,
+                       a.Hs[L - 1] + (size_t)(a.te + 1 + s0) * B * R, a.Htd + (size_t)s0 * B * R, n, R, B, a.dstr, L, 0, 0,
                        s0 * B, 1, dr);
     NVQA_HIP(hipGetLastError());
     const int M = (s1 - s0) * B;
@@ -624,8 +679,12 @@ static int ae_embed(nvqa_ctx *c, int q0, int q1, const int32_t *direct, const Dr
     const nvqa_dims &d = c->d;
     if (q1 <= q0) return 0;
     ProfScope ps(c, PF_AE_EMB, 0, (double)(q1 - q0) * d.B * d.E * 8);
-    hipLaunchKernelGGL(k_ae_embed, dim3((unsigned)((q1 - q0) * d.B)), dim3(std::min(256, (d.E + 63) / 64 * 64)), 0, c->s, a.tok,
-                       direct, d.B, a.D, d.V, d.E, a.tmax, q0, c->P + c->lo.w_lk, dr, a.X0);
+    if (a.ae2)
+        hipLaunchKernelGGL(k_ae2_assemble, dim3((unsigned)((q1 - q0) * d.B)), dim3(std::min(256, (d.E + 63) / 64 * 64)), 0, c->s,
+                           a.tok, direct, a.img_live ? a.img : nullptr, d.B, a.D, d.V, d.E, a.te, q0, c->P + c->lo.w_lk, a.X0);
+    else
+        hipLaunchKernelGGL(k_ae_embed, dim3((unsigned)((q1 - q0) * d.B)), dim3(std::min(256, (d.E + 63) / 64 * 64)), 0, c->s, a.tok,
+                           direct, d.B, a.D, d.V, d.E, a.tmax, q0, c->P + c->lo.w_lk, dr, a.X0);
     NVQA_HIP(hipGetLastError());
     return 0;
 }
@@ -635,12 +694,12 @@ static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool 
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
-    const int B = d.B, L = d.L, Q = 2 * a.tmax + 1, Vp1 = d.V + 1;
+    const int B = d.B, L = d.L, Q = a.te + a.tmax + 1, Vp1 = d.V + 1;
     NVQA_TRY(ae_embed(c, 0, Q, nullptr, dr));
     for (int l = 0; l < L; ++l) {
         if (l > 0) NVQA_TRY(ae_layer_input(c, l, 0, Q, dr));
-        NVQA_TRY(ae_i2h(c, l, 0, a.tmax, false));
-        NVQA_TRY(ae_i2h(c, l, a.tmax, Q, true));
+        NVQA_TRY(ae_i2h(c, l, 0, a.te, false));
+        NVQA_TRY(ae_i2h(c, l, a.te, Q, true));
         for (int q = 0; q < Q; ++q) NVQA_TRY(ae_fwd_step(c, l, q, dr));
     }
     NVQA_TRY(ae_project(c, 0, a.tmax + 1, dr));
@@ -660,14 +719,14 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
-    const int B = d.B, R = d.R, E = d.E, L = d.L, Vp1 = d.V + 1, T = a.tmax, Q = 2 * T + 1;
+    const int B = d.B, R = d.R, E = d.E, L = d.L, Vp1 = d.V + 1, T = a.tmax, TE = a.te, Q = TE + T + 1;
     const int rows = (T + 1) * B;
     // projection: dH_top (through drop_final) into the decoder rows of dHx, dW_proj, db_proj
-    NVQA_HIP(hipMemsetAsync(a.dHx, 0, (size_t)T * B * R * 4, c->s)); // the encoder's rows: no loss reaches them directly
+    NVQA_HIP(hipMemsetAsync(a.dHx, 0, (size_t)TE * B * R * 4, c->s)); // the encoder's rows: no loss reaches them directly
     {
         ProfScope ps(c, PF_AE_PROJ_BWD, 4.0 * rows * (double)Vp1 * R);
         GemmArgs g = ae_args(a.logits, a.ldl, c->P + c->lo.w_proj, R, rows, R, Vp1);
-        const EpiAeTop e{a.dHx + (size_t)T * B * R, R, B, a.D, dr};
+        const EpiAeTop e{a.dHx + (size_t)TE * B * R, R, B, a.dstr, dr};
         AE_LAUNCH(AeCfgLongK, A_KC, B_NC, false, EpiAeTop, 0, g, e);
         NVQA_TRY(wgrad(c, a.logits, a.ldl, a.Htd, R, Vp1, R, rows, c->G + c->lo.w_proj));
         NVQA_TRY(colsum(c, a.logits, rows, Vp1, a.ldl, c->G + c->lo.b_proj, nullptr));
@@ -677,7 +736,7 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
         NVQA_HIP(hipMemsetAsync(a.dc, 0, (size_t)B * R * 4, c->s));
         for (int q = Q - 1; q >= 0; --q) {
             // dh_q = dG_{q+1} W_h2h (of the phase of step q+1) + dHx_q; cell backward (epilogues.h EpiLstmBwd)
-            const bool last = q == Q - 1, dec_next = q + 1 >= T;
+            const bool last = q == Q - 1, dec_next = q + 1 >= TE;
             ProfScope ps(c, PF_AE_LSTM_BWD, last ? 0.0 : 2.0 * B * 4 * R * R);
             EpiLstmBwd e = {};
             e.gates = a.Gt[l] + (size_t)q * B * 4 * R;
@@ -694,7 +753,7 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
         {   // d(input) of both phases
             ProfScope ps(c, PF_AE_DGRAD, 2.0 * Q * B * 4.0 * R * in);
             for (int ph = 0; ph < 2; ++ph) {
-                const int q0 = ph ? T : 0, q1 = ph ? Q : T;
+                const int q0 = ph ? TE : 0, q1 = ph ? Q : TE;
                 if (q1 <= q0) continue;
                 GemmArgs g = ae_args(a.Gt[l] + (size_t)q0 * B * 4 * R, 4 * R, c->P + w_i2h_of(c, l, ph == 1), in, (q1 - q0) * B, in, 4 * R);
                 const EpiStore e{a.dX + (size_t)q0 * B * in, in, 0};
@@ -704,7 +763,7 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
         {   // weight and bias gradients of both phases
             ProfScope ps(c, PF_AE_WGRAD, 4.0 * Q * B * 4.0 * R * (in + R));
             for (int ph = 0; ph < 2; ++ph) {
-                const int q0 = ph ? T : 0, q1 = ph ? Q : T, K = (q1 - q0) * B;
+                const int q0 = ph ? TE : 0, q1 = ph ? Q : TE, K = (q1 - q0) * B;
                 const float *dG = a.Gt[l] + (size_t)q0 * B * 4 * R;
                 const float *X = (l == 0 ? a.X0 : a.U[l]) + (size_t)q0 * B * in;
                 NVQA_TRY(wgrad(c, dG, 4 * R, X, in, 4 * R, in, K, c->G + w_i2h_of(c, l, ph == 1)));
@@ -716,15 +775,18 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
         if (l > 0) { // d(h of layer l-1) through the inter-layer Dropout: the external term of layer l-1's chain
             const size_t n = (size_t)Q * B * R;
             hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s, a.dX, a.dHx,
-                               n, R, B, a.D, L, l, T, 0, 0, dr);
+                               n, R, B, a.dstr, L, l, TE, 0, 0, dr);
             NVQA_HIP(hipGetLastError());
         }
     }
-    {   // lookup table: both token streams into one gradient
-        ProfScope ps(c, PF_AE_EMB_BWD, 0, (double)Q * B * E * 12);
+    {   // lookup table: both token streams into one gradient (AE2: every chain row but the image's)
+        ProfScope ps(c, PF_AE_EMB_BWD, 0, (double)Q * B * E * (a.ae2 ? 4 : 12));
         NVQA_HIP(hipMemsetAsync(c->G + c->lo.w_lk, 0, (size_t)Vp1 * E * 4, c->s));
         const int nu = a.h_lk[0], nch = a.h_lk[1], nt = std::min(256, (E + 63) / 64 * 64);
-        hipLaunchKernelGGL(k_ae_lk_part, dim3(nch), dim3(nt), 0, c->s, a.lk_start, a.lk_pos, a.X0, a.dX, B, a.D, E, T, dr, a.lk_part);
+        if (a.ae2)
+            hipLaunchKernelGGL(k_ae2_lk_part, dim3(nch), dim3(nt), 0, c->s, a.lk_start, a.lk_pos, a.dX, E, a.lk_part);
+        else
+            hipLaunchKernelGGL(k_ae_lk_part, dim3(nch), dim3(nt), 0, c->s, a.lk_start, a.lk_pos, a.X0, a.dX, B, a.D, E, T, dr, a.lk_part);
         hipLaunchKernelGGL(k_ae_lk_sum, dim3(nu), dim3(nt), 0, c->s, a.lk_tok, a.lk_tc, a.lk_part, E, c->G + c->lo.w_lk);
         NVQA_HIP(hipGetLastError());
     }
@@ -732,8 +794,8 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
 }
 
 // host side of a batch: tokens -> device, tmax, the criterion's n, and (training) the token -> rows index of the lookup
-// gradient (a counting sort: deterministic row order per token)
-static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, bool index, int *ncount)
+// gradient (a counting sort: deterministic row order per token).  AE2: images [n x E] (NULL: zeros) -> the device rows.
+static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *images, bool index, int *ncount)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
@@ -757,18 +819,27 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, bool index, int 
         }
     }
     a.tmax = tmax;
+    a.te = a.ae2 ? tmax + 2 : tmax;
     *ncount = cnt;
     NVQA_HIP(hipMemcpyAsync(a.tok, a.h_tok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
+    a.img_live = a.ae2 && images;
+    if (a.img_live) {
+        const size_t E = d.E;
+        memcpy(a.h_img, images, (size_t)n * E * 4);
+        if (n < B) memset(a.h_img + (size_t)n * E, 0, (size_t)(B - n) * E * 4);
+        NVQA_HIP(hipMemcpyAsync(a.img, a.h_img, (size_t)B * E * 4, hipMemcpyHostToDevice, c->s));
+    }
     if (index) {
-        const int Q = 2 * tmax + 1, NP = Q * B;
+        // the rows of chain steps 0 .. Q-1 from r_lo on: AE2's image step (chain step 0) has no token
+        const int TE = a.te, Q = TE + tmax + 1, r_lo = a.ae2 ? B : 0, NP = Q * B - r_lo;
         std::vector<int> ofs(V + 2, 0), tokr(NP);
-        for (int r = 0; r < NP; ++r) {
-            const int q = r / B, b = r % B;
+        for (int i = 0; i < NP; ++i) {
+            const int r = r_lo + i, q = r / B, b = r % B;
             int v;
-            if (q < tmax) v = a.h_tok[(size_t)b * D + q];
-            else v = q == tmax ? V + 1 : a.h_tok[(size_t)b * D + q - tmax - 1];
-            tokr[r] = v == 0 ? 1 : v;
-            ++ofs[tokr[r]];
+            if (q < TE) v = a.ae2 && q == 1 ? V + 1 : a.h_tok[(size_t)b * D + q - (a.ae2 ? 2 : 0)];
+            else v = q == TE ? V + 1 : a.h_tok[(size_t)b * D + q - TE - 1];
+            tokr[i] = v == 0 ? 1 : v;
+            ++ofs[tokr[i]];
         }
         int32_t *ut = a.h_lk + 2, *tc = ut + NP, *cs = tc + NP + 1, *pos = cs + NP + 1;
         int nu = 0, nch = 0, acc = 0;
@@ -784,7 +855,7 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, bool index, int 
         }
         tc[nu] = nch;
         cs[nch] = acc;
-        for (int r = 0; r < NP; ++r) pos[at[tokr[r]]++] = r;
+        for (int i = 0; i < NP; ++i) pos[at[tokr[i]]++] = r_lo + i;
         a.h_lk[0] = nu;
         a.h_lk[1] = nch;
         NVQA_HIP(hipMemcpyAsync(a.lk_tok, ut, (size_t)nu * 4, hipMemcpyHostToDevice, c->s));
@@ -800,46 +871,52 @@ float ae_last_loss(const nvqa_ctx *c) { return c->ae ? *c->ae->h_loss : 0.f; }
 static int ae_check(nvqa_ctx *c)
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
-    if (c->d.arch != NVQA_ARCH_AE1 || !c->ae) { set_error("not an auto-encoder context (arch %d, NVQA_ARCH_AE1 = 3)", c->d.arch); return -1; }
+    if (!is_ae(c->d) || !c->ae) { set_error("not an auto-encoder context (arch %d; NVQA_ARCH_AE1 = 3, NVQA_ARCH_AE2 = 4)", c->d.arch); return -1; }
     NVQA_HIP(hipSetDevice(c->device));
     return 0;
 }
 
-} // namespace nvqa
-
-extern "C" int nvqa_ae_step(nvqa_ctx *c, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out)
+static int ae_check_images(nvqa_ctx *c, const char *fn)
 {
     NVQA_TRY(ae_check(c));
+    if (c->d.arch != NVQA_ARCH_AE2) { set_error("%s: an NVQA_ARCH_AE2 context expected (arch %d)", fn, c->d.arch); return -1; }
+    return 0;
+}
+
+static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out,
+                        float *dimages_out)
+{
     if (!tokens) { set_error("tokens is NULL"); return -1; }
     const Drop dr = ae_drop(dropout, true);
     int ncount = 0;
-    NVQA_TRY(ae_upload(c, c->d.B, tokens, true, &ncount));
+    NVQA_TRY(ae_upload(c, c->d.B, tokens, images, true, &ncount));
     NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
     NVQA_TRY(ae_backward(c, dr));
     c->have_grads = true;
-    if (loss_out) {
+    if (dimages_out) // layer 0's d(input) of chain step 0 (the backward pass ends with layer 0)
+        NVQA_HIP(hipMemcpyAsync(dimages_out, c->ae->dX, (size_t)c->d.B * c->d.E * 4, hipMemcpyDeviceToHost, c->s));
+    if (loss_out || dimages_out) {
         NVQA_HIP(hipStreamSynchronize(c->s));
-        *loss_out = *c->ae->h_loss;
+        if (loss_out) *loss_out = *c->ae->h_loss;
     }
     return 0;
 }
 
-extern "C" int nvqa_ae_evaluate(nvqa_ctx *c, int32_t n, const int32_t *tokens, float *loss_out, int32_t *samples_out)
+static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, float *loss_out, int32_t *samples_out)
 {
-    NVQA_TRY(ae_check(c));
     if (!tokens) { set_error("tokens is NULL"); return -1; }
     if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
     AeState &a = *c->ae;
     const Drop dr = ae_drop(nullptr, false);
     int ncount = 0;
-    NVQA_TRY(ae_upload(c, n, tokens, false, &ncount));
+    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount));
     NVQA_TRY(ae_forward(c, dr, n, ncount, false));
     if (samples_out) {
-        // sample(): the encoder state is the one just computed (slot tmax); the decoder is fed START, then its own argmax
+        // sample(): the encoder state is the one just computed (slot te); the decoder is fed START, then its own argmax
         const nvqa_dims &d = c->d;
-        const int B = d.B, L = d.L, T = a.tmax;
+        const int B = d.B, L = d.L, TE = a.te;
         for (int s = 0; s < a.D; ++s) {
-            const int q = T + s;
+            const int q = TE + s;
             NVQA_TRY(ae_embed(c, q, q + 1, s == 0 ? nullptr : a.cur, dr));
             for (int l = 0; l < L; ++l) {
                 if (l > 0) NVQA_TRY(ae_layer_input(c, l, q, q + 1, dr));
@@ -856,6 +933,35 @@ extern "C" int nvqa_ae_evaluate(nvqa_ctx *c, int32_t n, const int32_t *tokens, f
     NVQA_HIP(hipStreamSynchronize(c->s));
     if (loss_out) *loss_out = *a.h_loss;
     return 0;
+}
+
+} // namespace nvqa
+
+// AE2: images = NULL (the text script's zero image rows)
+extern "C" int nvqa_ae_step(nvqa_ctx *c, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out)
+{
+    NVQA_TRY(ae_check(c));
+    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr);
+}
+
+extern "C" int nvqa_ae_evaluate(nvqa_ctx *c, int32_t n, const int32_t *tokens, float *loss_out, int32_t *samples_out)
+{
+    NVQA_TRY(ae_check(c));
+    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out);
+}
+
+extern "C" int nvqa_ae_step_images(nvqa_ctx *c, const float *images, const int32_t *tokens, const nvqa_dropout *dropout,
+                                   float *loss_out, float *dimages_out)
+{
+    NVQA_TRY(ae_check_images(c, "nvqa_ae_step_images"));
+    return ae_step_impl(c, images, tokens, dropout, loss_out, dimages_out);
+}
+
+extern "C" int nvqa_ae_evaluate_images(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, float *loss_out,
+                                       int32_t *samples_out)
+{
+    NVQA_TRY(ae_check_images(c, "nvqa_ae_evaluate_images"));
+    return ae_evaluate_impl(c, n, images, tokens, loss_out, samples_out);
 }
 
 extern "C" int nvqa_adam_update(nvqa_ctx *c, float lr, float beta1, float beta2, float eps, float wd, float clamp,

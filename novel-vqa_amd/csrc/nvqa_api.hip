@@ -142,8 +142,8 @@ static void comm_destroy(nvqa_ctx *c); // with the RCCL loader, below
 // entry points of the VQA step refuse an auto-encoder context (its step is nvqa_ae_step, ae.hip)
 static int reject_ae(const nvqa_ctx *c, const char *fn)
 {
-    if (c && c->d.arch == NVQA_ARCH_AE1) {
-        set_error("%s: not available on an auto-encoder context (NVQA_ARCH_AE1: nvqa_ae_step / nvqa_ae_evaluate)", fn);
+    if (c && is_ae(c->d)) {
+        set_error("%s: not available on an auto-encoder context (arch %d: nvqa_ae_step / nvqa_ae_evaluate)", fn, c->d.arch);
         return -1;
     }
     return 0;
@@ -166,7 +166,7 @@ template <class T> static int dalloc(T **p, size_t n)
 static int check_dims(const nvqa_dims *d)
 {
     if (!d) { set_error("dims is NULL"); return -1; }
-    if (d->arch == NVQA_ARCH_AE1) { // text auto-encoder: B, T = seq_length, V, E, R, L; no image, fusion or answers
+    if (is_ae(*d)) { // text auto-encoders: B, T = seq_length, V, E, R, L; no image features, fusion or answers
         if (d->B < 1 || d->T < 1 || d->V < 1 || d->E < 4 || d->R < 4 || d->L < 1 || d->L > NVQA_MAX_LAYERS || d->I || d->C || d->A) {
             set_error("auto-encoder: bad dims (B=%d T=%d V=%d E=%d R=%d L=%d; I, C, A must be 0)", d->B, d->T, d->V, d->E, d->R, d->L);
             return -1;
@@ -174,7 +174,7 @@ static int check_dims(const nvqa_dims *d)
         if (d->E % 4 || d->R % 4) { set_error("auto-encoder: E, R must be multiples of 4 (got E=%d R=%d)", d->E, d->R); return -1; }
         return 0;
     }
-    if (d->arch != NVQA_ARCH1 && d->arch != NVQA_ARCH2) { set_error("arch must be 1, 2 or 3"); return -1; }
+    if (d->arch != NVQA_ARCH1 && d->arch != NVQA_ARCH2) { set_error("arch must be 1, 2, 3 or 4"); return -1; }
     if (d->B < 1 || d->T < 1 || d->V < 1 || d->L < 1 || d->L > NVQA_MAX_LAYERS) {
         set_error("bad dims (B=%d T=%d V=%d L=%d)", d->B, d->T, d->V, d->L);
         return -1;
@@ -215,7 +215,7 @@ extern "C" int nvqa_create(const nvqa_dims *dims, int device, nvqa_ctx **out)
     c->d = *dims;
     c->device = device;
     if (nvqa_layout_init(dims, &c->lo)) { delete c; set_error("layout"); return -1; }
-    const int rc = dims->arch == NVQA_ARCH_AE1 ? ae_create(c) : create_impl(c);
+    const int rc = is_ae(*dims) ? ae_create(c) : create_impl(c);
     if (rc != 0) { // a failure half-way (out of memory, ...) releases whatever was acquired; the message survives
         const std::string keep = nvqa_last_error();
         nvqa_destroy(c);
@@ -551,7 +551,7 @@ extern "C" int nvqa_sync(nvqa_ctx *c)
 extern "C" int nvqa_persistent_state(const nvqa_ctx *c, int out[2])
 {
     if (!c || !out) { set_error("NULL argument"); return -1; }
-    if (c->d.arch == NVQA_ARCH_AE1) { out[0] = out[1] = 0; return 0; }
+    if (is_ae(c->d)) { out[0] = out[1] = 0; return 0; }
     int RB = 0;
     out[0] = persist_rows(c) > 0 ? 1 : 0;
     out[1] = persist_bwd_rows(c, &RB) > 0 ? 1 : 0;
@@ -1696,7 +1696,7 @@ extern "C" int nvqa_get_loss(nvqa_ctx *c, float *loss_out)
     if (!c || !loss_out) { set_error("NULL argument"); return -1; }
     NVQA_HIP(hipSetDevice(c->device));
     NVQA_HIP(hipStreamSynchronize(c->s));
-    if (c->d.arch == NVQA_ARCH_AE1) { *loss_out = ae_last_loss(c); return 0; }
+    if (is_ae(c->d)) { *loss_out = ae_last_loss(c); return 0; }
     *loss_out = loss_mean_host(c);
     return check_persist(c);
 }
@@ -1708,14 +1708,14 @@ extern "C" int nvqa_rmsprop_update(nvqa_ctx *c, float lr, float alpha, float eps
     NVQA_HIP(hipSetDevice(c->device));
     ProfScope ps(c, PF_RMSPROP, 0, 20.0 * c->lo.total);
     const float inv_world = 1.0f / (float)c->world;
-    if (c->d.arch == NVQA_ARCH_AE1 && !(c->gscale[0] == c->gscale[1] && c->gscale[1] == c->gscale[2])) {
+    if (is_ae(c->d) && !(c->gscale[0] == c->gscale[1] && c->gscale[1] == c->gscale[2])) {
         set_error("nvqa_rmsprop_update: per-segment gradient scales are not supported on an auto-encoder context");
         return -1;
     }
     if (c->gscale[0] == c->gscale[1] && c->gscale[1] == c->gscale[2]) {
         // every VQA tensor size is a multiple of 4 (check_dims); an auto-encoder vector (b_proj has V+1 entries) is padded to
         // whole float4s with zeros (ae.hip), which the update leaves at zero
-        const size_t n4 = c->d.arch == NVQA_ARCH_AE1 ? (c->lo.total + 3) / 4 : c->lo.total / 4;
+        const size_t n4 = is_ae(c->d) ? (c->lo.total + 3) / 4 : c->lo.total / 4;
         hipLaunchKernelGGL(k_rmsprop, dim3(2048), dim3(256), 0, c->s, reinterpret_cast<float4 *>(c->P),
                            reinterpret_cast<const float4 *>(c->G), reinterpret_cast<float4 *>(c->M2), n4, lr, alpha,
                            eps, wd, clamp, inv_world * c->gscale[0], c->comm ? (const unsigned *)nullptr : c->pf_sticky,

@@ -14,7 +14,7 @@
 namespace nvqa {
 
 void set_error(const char *fmt, ...);
-int ae_create(nvqa_ctx *c);  // ae.hip: the buffers of an NVQA_ARCH_AE1 context (instead of the VQA step's)
+int ae_create(nvqa_ctx *c);  // ae.hip: the buffers of an NVQA_ARCH_AE1 / AE2 context (instead of the VQA step's)
 void ae_destroy(nvqa_ctx *c);
 float ae_last_loss(const nvqa_ctx *c); // loss of the last nvqa_ae_step / nvqa_ae_evaluate (after a synchronisation)
 
@@ -93,7 +93,7 @@ struct ProfEntry {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
-struct AeState; // ae.hip: buffers of the text auto-encoder (NVQA_ARCH_AE1)
+struct AeState; // ae.hip: buffers of the text auto-encoders (NVQA_ARCH_AE1, NVQA_ARCH_AE2)
 
 struct Dataset {
     int64_t n_q = 0, n_img = 0;
@@ -209,7 +209,7 @@ struct nvqa_ctx {
 
     nvqa::Dataset ds;
 
-    // text auto-encoder (arch NVQA_ARCH_AE1, ae.hip) and the Adam state of nvqa_adam_update (any arch, allocated on first use)
+    // text auto-encoder (arch NVQA_ARCH_AE1 / AE2, ae.hip) and the Adam state of nvqa_adam_update (any arch, allocated on first use)
     nvqa::AeState *ae = nullptr;
     float *adam_m = nullptr, *adam_v = nullptr;
     double *adam_part = nullptr; // per-workgroup {sum x^2, update count} of the log-line statistics
@@ -229,3 +229,8 @@ struct nvqa_ctx {
     nvqa::ProfEntry prof[nvqa::PF_COUNT];
     std::vector<hipEvent_t> prof_pool; // events waiting for reuse (prof.h)
 };
+
+namespace nvqa {
+// a text auto-encoder context (ae.hip runs its step; the VQA entry points refuse it)
+static inline bool is_ae(const nvqa_dims &d) { return d.arch == NVQA_ARCH_AE1 || d.arch == NVQA_ARCH_AE2; }
+} // namespace nvqa

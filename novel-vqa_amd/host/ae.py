@@ -1,6 +1,7 @@
-"""Text auto-encoder pre-training (the reference's first stage, 001_train_autoencoder/001_train_arch1_text_autoencoder.lua)
-on the library's NVQA_ARCH_AE1 context: the data loader, the training loop with its log line and learning-rate decay,
-eval_split, and the export that VQATrainer.init_from_autoencoder reads (002_convert_text_model_arch1.lua:27-39)."""
+"""Text auto-encoder pre-training (the reference's first stage, 001_train_autoencoder/001_train_arch1_text_autoencoder.lua
+and 001_train_arch2_text_autoencoder.lua) on the library's NVQA_ARCH_AE1 / NVQA_ARCH_AE2 contexts: the data loader, the
+training loop with its log line and learning-rate decay, eval_split, and the export that VQATrainer.init_from_autoencoder
+reads (002_convert_text_model_arch1.lua:27-39; arch2: the table of lua/convert_ae_arch2.lua)."""
 import json
 
 import numpy as np
@@ -74,15 +75,25 @@ def decode_sequence(ix_to_word, seq, end_token):
     return out
 
 
+# the training scripts' defaults that differ between the two auto-encoders (001_train_arch{1,2}_text_autoencoder.lua:32-50)
+ARCH_DEFAULTS = {
+    binding.ARCH_AE1: {"learning_rate": 1e-5, "max_iters": 75001, "save_model_every": 75000},
+    binding.ARCH_AE2: {"learning_rate": 5e-5, "max_iters": 40001, "save_model_every": 40000},
+}
+
+
 class AETrainer:
     """The training script's loop on the library: ae_step (lossFun), the log line, the learning-rate decay and the
-    Adam (or RMSprop) update.  dims: binding.Dims with arch = ARCH_AE1, T = seq_length, I = C = A = 0."""
+    Adam (or RMSprop) update.  dims: binding.Dims with arch = ARCH_AE1 or ARCH_AE2, T = seq_length, I = C = A = 0
+    (the arch2 script forces 1 layer, :104; the library takes any L).  learning_rate None: the script's default."""
 
-    def __init__(self, dims, device=0, learning_rate=1e-5, learning_rate_decay_start=-1, learning_rate_decay_every=50000,
+    def __init__(self, dims, device=0, learning_rate=None, learning_rate_decay_start=-1, learning_rate_decay_every=50000,
                  optim="adam", optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6, grad_clip=0.1,
                  drop_prob=0.5, seed=123):
-        if dims.arch != binding.ARCH_AE1:
-            raise ValueError("AETrainer needs dims.arch = ARCH_AE1 (3)")
+        if dims.arch not in ARCH_DEFAULTS:
+            raise ValueError("AETrainer needs dims.arch = ARCH_AE1 (3) or ARCH_AE2 (4)")
+        if learning_rate is None:
+            learning_rate = ARCH_DEFAULTS[dims.arch]["learning_rate"]
         if optim not in ("adam", "rmsprop"):
             raise ValueError("optim: adam or rmsprop (the other optimisers of misc/optim_updates.lua are not provided)")
         self.dims = dims
@@ -133,10 +144,13 @@ class AETrainer:
     def eval_split(self, loader, split="val", val_sentences_use=-1):
         """eval_split (:148-194): mean of the per-batch evaluate-mode losses, stopping when the split wraps or (when
         val_sentences_use > 0) once that many sentences were used; predictions are the greedy decodes through ix_to_word.
-        (The reference's counter `n` is never incremented there, so only the wrap ends its loop.)"""
+        (The arch1 reference's counter `n` is never incremented there, so only the wrap ends its loop.)
+        ARCH_AE2 (001_train_arch2_text_autoencoder.lua:192-195): n grows by batch_size after every batch and the loop
+        ends once n >= val_sentences_use, so a non-positive val_sentences_use evaluates one batch, as there."""
         loader.reset_iterator(split)
-        losses, preds, used = [], [], 0
+        losses, preds, used, n = [], [], 0, 0
         end = self.dims.V + 1
+        ae2 = self.dims.arch == binding.ARCH_AE2
         while True:
             batch, bounds = loader.get_batch(split, self.dims.B)
             loss, samples = self.ctx.ae_evaluate(batch, samples=True)
@@ -144,15 +158,25 @@ class AETrainer:
             for p, a in zip(decode_sequence(loader.ix_to_word, samples, end), decode_sequence(loader.ix_to_word, batch, end)):
                 used += 1
                 preds.append({"seqNo": used, "prediction": p, "actual": a})
-            if bounds["wrapped"] or (val_sentences_use > 0 and used >= val_sentences_use):
+            n += self.dims.B
+            if bounds["wrapped"]:
+                break
+            if ae2 and n >= val_sentences_use:
+                break
+            if not ae2 and val_sentences_use > 0 and used >= val_sentences_use:
                 break
         return float(np.mean(losses)), preds
 
     def export_for_vqa(self, path):
         """002_convert_text_model_arch1.lua:27-39: {lookup = W_lk^T [E x (V+1)], encoder = the encoder segment} plus
-        layout = 'nvqa' (the LSTM tensors are in include/nvqa_layout.h order), readable by init_from_autoencoder."""
+        layout = 'nvqa' (the LSTM tensors are in include/nvqa_layout.h order), readable by init_from_autoencoder.
+        ARCH_AE2: the table of lua/convert_ae_arch2.lua, {encoder, lookup_table = W_lk [(V+1) x E]}, plus the same mark;
+        an arch2 VQATrainer reads it without encoder_perm."""
         d = self.dims
         x = self.ctx.get_params()
         seg = self.ctx.segments()
         w_lk = x[seg[0] + seg[1]:].reshape(d.V + 1, d.E)
+        if d.arch == binding.ARCH_AE2:
+            t7.save(path, {"encoder": x[:seg[0]].copy(), "lookup_table": np.ascontiguousarray(w_lk), "layout": t7.LAYOUT_MARK})
+            return
         t7.save(path, {"lookup": np.ascontiguousarray(w_lk.T), "encoder": x[:seg[0]].copy(), "layout": t7.LAYOUT_MARK})

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_PKG, "libnvqa.so")
 COMM_ID_BYTES = 128
 
 
-ARCH1, ARCH2, ARCH_AE1 = 1, 2, 3
+ARCH1, ARCH2, ARCH_AE1, ARCH_AE2 = 1, 2, 3, 4
 
 
 class NvqaError(RuntimeError):
@@ -78,6 +78,8 @@ SYMBOLS = {
     "nvqa_step_images": (ctypes.c_int, [_vp, _vp, _f32p, _i32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_step": (ctypes.c_int, [_vp, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _i32p]),
+    "nvqa_ae_step_images": (ctypes.c_int, [_vp, _f32p, _i32p, ctypes.POINTER(Dropout), _f32p, _f32p]),
+    "nvqa_ae_evaluate_images": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _f32p, _i32p]),
     "nvqa_adam_update": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_profile_reset": (ctypes.c_int, [_vp]),
@@ -250,24 +252,38 @@ class Context:
     def rmsprop_update(self, lr, alpha=0.99, eps=1e-8, wd=0.0, clamp=10.0):
         self._check(self.lib.nvqa_rmsprop_update(self._h, lr, alpha, eps, wd, clamp))
 
-    # ---- text auto-encoder (arch ARCH_AE1) and Adam ---------------------------------
-    def ae_step(self, tokens, dropout=None, want_loss=True):
-        """nvqa_ae_step: tokens [B x D] left-aligned, 0 = null.  Returns the criterion's loss (or None)."""
+    # ---- text auto-encoders (arch ARCH_AE1 / ARCH_AE2) and Adam ---------------------
+    def ae_step(self, tokens, dropout=None, want_loss=True, images=None, want_dimages=False):
+        """nvqa_ae_step: tokens [B x D] left-aligned, 0 = null.  Returns the criterion's loss (or None).
+        ARCH_AE2 only: images [B x E] (None = zeros) and want_dimages go through nvqa_ae_step_images; with
+        want_dimages the return value is (loss or None, d(images) [B x E])."""
         d = self.dims
         tokens = np.ascontiguousarray(tokens, np.int32).reshape(d.B, d.T)
         loss = ctypes.c_float(0)
         dr = ctypes.byref(dropout) if dropout is not None else None
-        self._check(self.lib.nvqa_ae_step(self._h, _i32(tokens), dr, ctypes.byref(loss) if want_loss else None))
-        return float(loss.value) if want_loss else None
+        lp = ctypes.byref(loss) if want_loss else None
+        if images is None and not want_dimages:
+            self._check(self.lib.nvqa_ae_step(self._h, _i32(tokens), dr, lp))
+            return float(loss.value) if want_loss else None
+        img = None if images is None else np.ascontiguousarray(images, np.float32).reshape(d.B, d.E)
+        dimg = np.empty((d.B, d.E), np.float32) if want_dimages else None
+        self._check(self.lib.nvqa_ae_step_images(self._h, _f32(img), _i32(tokens), dr, lp, _f32(dimg)))
+        out = float(loss.value) if want_loss else None
+        return (out, dimg) if want_dimages else out
 
-    def ae_evaluate(self, tokens, samples=False):
-        """nvqa_ae_evaluate: (evaluate-mode loss, greedy samples [n x D] 1-based with V+1 = END, or None)."""
+    def ae_evaluate(self, tokens, samples=False, images=None):
+        """nvqa_ae_evaluate: (evaluate-mode loss, greedy samples [n x D] 1-based with V+1 = END, or None).
+        ARCH_AE2 only: images [n x E] (None = zeros) go through nvqa_ae_evaluate_images."""
         d = self.dims
         tokens = np.ascontiguousarray(tokens, np.int32).reshape(-1, d.T)
         n = tokens.shape[0]
         out = np.empty((n, d.T), np.int32) if samples else None
         loss = ctypes.c_float(0)
-        self._check(self.lib.nvqa_ae_evaluate(self._h, n, _i32(tokens), ctypes.byref(loss), _i32(out)))
+        if images is None:
+            self._check(self.lib.nvqa_ae_evaluate(self._h, n, _i32(tokens), ctypes.byref(loss), _i32(out)))
+        else:
+            img = np.ascontiguousarray(images, np.float32).reshape(n, d.E)
+            self._check(self.lib.nvqa_ae_evaluate_images(self._h, n, _f32(img), _i32(tokens), ctypes.byref(loss), _i32(out)))
         return float(loss.value), out
 
     def adam_update(self, lr, beta1=0.8, beta2=0.999, eps=1e-8, wd=0.0, clamp=0.0, stats=False):

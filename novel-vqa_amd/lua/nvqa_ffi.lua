@@ -58,6 +58,10 @@ int nvqa_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const float *images, const in
                      const int32_t *lengths, const int32_t *labels, const nvqa_dropout *dropout, float *loss_out);
 int nvqa_ae_step(nvqa_ctx *ctx, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out);
 int nvqa_ae_evaluate(nvqa_ctx *ctx, int32_t n, const int32_t *tokens, float *loss_out, int32_t *samples_out);
+int nvqa_ae_step_images(nvqa_ctx *ctx, const float *images, const int32_t *tokens, const nvqa_dropout *dropout,
+                        float *loss_out, float *dimages_out);
+int nvqa_ae_evaluate_images(nvqa_ctx *ctx, int32_t n, const float *images, const int32_t *tokens, float *loss_out,
+                            int32_t *samples_out);
 int nvqa_adam_update(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                      float stats_out[2]);
 int nvqa_profile_enable(nvqa_ctx *ctx, int enable);

@@ -1,0 +1,149 @@
+--[[
+train_ae_arch2.lua -- 001_train_autoencoder/001_train_arch2_text_autoencoder.lua with the hot path on libnvqa.
+
+Same command-line options (:22-58, minus -backend / -language_eval), same HDF5/JSON inputs (misc/DataLoader.lua, whose
+image rows are zeros, :84), same log line (:271-273), learning-rate decay (:342-348), update (-optim adam | rmsprop) and
+stopping rules (:367-375); num_layers is 1 as in the script (:104).  eval_split counts the sentences it used and stops at
+-val_sentences_use (:192-195).  What changed: the AutoEncoder / LanguageModelCriterion modules, their clones, lossFun and
+the optimiser are one library context of arch NVQA_ARCH_AE2 (include/nvqa.h), where nvqa_ae_step feeds the zero image
+rows.  Instead of the thin nn checkpoints (best validation loss every -save_checkpoint_every, every -save_model_every) it
+writes the table that convert_ae_arch2.lua makes ({encoder, lookup_table}) plus layout = 'nvqa', which train_arch2_ae.lua
+and VQATrainer.init_from_autoencoder read without -encoder_perm.  Needs LuaJIT + torch + hdf5 + cjson; NOT executable in
+the build image, where novel-vqa_amd/host/ae.py (AETrainer) is the executed twin.
+]]--
+require 'torch'
+require 'hdf5'
+local cjson = require 'cjson'
+local ffi = require 'ffi'
+local nvqa = require 'nvqa_ffi'
+
+cmd = torch.CmdLine()
+cmd:option('-input_h5','data/data.h5','path to the h5file containing the preprocessed dataset')
+cmd:option('-input_json','data/data.json','path to the json file containing additional info and vocab')
+cmd:option('-rnn_size',512,'size of the rnn in number of hidden nodes in each layer')
+cmd:option('-input_encoding_size',512,'the encoding size of each token in the vocabulary, and the image.')
+cmd:option('-max_iters', 40001, 'max number of iterations to run for (-1 = run forever)')
+cmd:option('-batch_size',1000,'what is the batch size in number of sentences per batch?')
+cmd:option('-grad_clip',0.1,'clip gradients at this value')
+cmd:option('-drop_prob_ae', 0.5, 'strength of dropout in the AutoEncoder RNN')
+cmd:option('-optim','adam','what update to use? adam|rmsprop')
+cmd:option('-learning_rate',5e-5,'learning rate')
+cmd:option('-learning_rate_decay_start', -1, 'at what iteration to start decaying learning rate? (-1 = dont)')
+cmd:option('-learning_rate_decay_every', 50000, 'every how many iterations thereafter to drop LR by half?')
+cmd:option('-optim_alpha',0.8,'alpha for rmsprop/adam')
+cmd:option('-optim_beta',0.999,'beta used for adam')
+cmd:option('-optim_epsilon',1e-8,'epsilon that goes into denominator for smoothing')
+cmd:option('-weight_decay', 1e-6, 'L2 regularization parameter')
+cmd:option('-val_sentences_use', 30000, 'how many sentences to use when periodically evaluating the validation loss?')
+cmd:option('-save_checkpoint_every', 2500, 'how often to evaluate and save the best export table?')
+cmd:option('-save_model_every', 40000, 'how often to save an export table regardless of the validation loss?')
+cmd:option('-checkpoint_path', '', 'folder to save checkpoints into (empty = this folder)')
+cmd:option('-id', '', 'an id identifying this run/job')
+cmd:option('-seed', 123, 'random number generator seed to use')
+cmd:option('-gpuid', 0, 'which MI355X to use')
+opt = cmd:parse(arg)
+torch.manualSeed(opt.seed)
+
+-- data (misc/DataLoader.lua:6-31) ------------------------------------------------------------------------------------
+local f = io.open(opt.input_json, 'r'); local info = cjson.decode(f:read('*a')); f:close()
+local vocab_size = 0
+for _ in pairs(info.ix_to_word) do vocab_size = vocab_size + 1 end
+local h5 = hdf5.open(opt.input_h5, 'r')
+local labels = {train = h5:read('/labels/train'):all():int(), val = h5:read('/labels/val'):all():int()}
+h5:close()
+local seq_length = labels.train:size(2)
+local iterators = {train = 1, val = 1}
+
+local function getBatch(split, batch_size)          -- DataLoader:getBatch (:58-89), wrap-around included
+  local data, max_index, it = labels[split], labels[split]:size(1), iterators[split]
+  local batch = torch.IntTensor(batch_size, seq_length)
+  local wrapped = false
+  if it + batch_size - 1 > max_index then
+    wrapped = true
+    if it < max_index then
+      local num_left = max_index - it + 1
+      batch[{{1, num_left}, {}}] = data[{{it, max_index}, {}}]
+      batch[{{num_left + 1, batch_size}, {}}] = data[{{1, batch_size - num_left}, {}}]
+    else
+      batch:copy(data[{{1, batch_size}, {}}])
+    end
+    iterators[split] = 1
+  else
+    batch:copy(data[{{it, it + batch_size - 1}, {}}])
+    iterators[split] = it + batch_size
+  end
+  return batch:contiguous(), wrapped
+end
+
+-- the context: [encoder | decoder | lookup], *_w:uniform(-0.08, 0.08); one LSTM layer (:104) ----------------------------
+opt.num_layers = 1
+opt.nhimage, opt.common_embedding_size, opt.num_output = 0, 0, 0
+local ctx = nvqa.create(4, opt, vocab_size, seq_length, opt.gpuid)
+nvqa.check(nvqa.lib.nvqa_init_params(ctx, opt.seed, -0.08, 0.08))
+local n_params = tonumber(nvqa.lib.nvqa_param_count(ctx))
+
+local function eval_split(split)                    -- eval_split (:148-204): mean of the per-batch losses
+  iterators[split] = 1
+  local loss_sum, evals, n = 0, 0, 0
+  local loss = ffi.new('float[1]')
+  while true do
+    local batch, wrapped = getBatch(split, opt.batch_size)
+    nvqa.check(nvqa.lib.nvqa_ae_evaluate(ctx, opt.batch_size, nvqa.iptr(batch), loss, nil))
+    loss_sum = loss_sum + loss[0]; evals = evals + 1
+    n = n + opt.batch_size
+    if wrapped then break end
+    if n >= opt.val_sentences_use then break end
+  end
+  return loss_sum / evals
+end
+
+local function export(path)                          -- convert_ae_arch2.lua's table + layout = 'nvqa'
+  local x = torch.FloatTensor(n_params)
+  nvqa.check(nvqa.lib.nvqa_get_params(ctx, nvqa.fptr(x)))
+  local seg = ffi.new('size_t[3]'); nvqa.check(nvqa.lib.nvqa_segments(ctx, seg))
+  local s0, s1 = tonumber(seg[0]), tonumber(seg[1])
+  local lookup = x:narrow(1, s0 + s1 + 1, tonumber(seg[2])):view(vocab_size + 1, opt.input_encoding_size)
+  torch.save(path, {encoder = x:narrow(1, 1, s0):clone(), lookup_table = lookup:clone(), layout = 'nvqa'})
+end
+
+-- main loop (:265-376) ------------------------------------------------------------------------------------------------
+local iter, loss0, best_score = 1, nil, nil
+local loss, stats = ffi.new('float[1]'), ffi.new('float[2]')
+local checkpoint_path = paths.concat(opt.checkpoint_path, 'model_id' .. opt.id)
+while true do
+  local batch = getBatch('train', opt.batch_size)
+  nvqa.check(nvqa.lib.nvqa_ae_step(ctx, nvqa.iptr(batch), nvqa.dropout(1, opt.drop_prob_ae, opt.seed, iter), loss))
+  local learning_rate = opt.learning_rate
+  if iter > opt.learning_rate_decay_start and opt.learning_rate_decay_start >= 0 then
+    local frac = (iter - opt.learning_rate_decay_start) / opt.learning_rate_decay_every
+    learning_rate = learning_rate * math.pow(0.5, frac)
+  end
+  if opt.optim == 'adam' then
+    nvqa.check(nvqa.lib.nvqa_adam_update(ctx, learning_rate, opt.optim_alpha, opt.optim_beta, opt.optim_epsilon,
+                                         opt.weight_decay, opt.grad_clip, stats))
+    print(string.format('iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f', iter, loss[0], stats[1], stats[0]))
+  elseif opt.optim == 'rmsprop' then
+    print(string.format('iter %d: loss: %.3f', iter, loss[0]))
+    nvqa.check(nvqa.lib.nvqa_rmsprop_update(ctx, learning_rate, opt.optim_alpha, opt.optim_epsilon, opt.weight_decay,
+                                            opt.grad_clip))
+  else
+    error('bad option opt.optim (adam | rmsprop)')
+  end
+  if iter % opt.save_checkpoint_every == 0 or iter == opt.max_iters then
+    local val_loss = eval_split('val')
+    print('validation loss: ', val_loss)
+    if best_score == nil or -val_loss > best_score then  -- the negative validation loss decides (:300-322)
+      best_score = -val_loss
+      export(checkpoint_path .. '_vqa.t7')
+      print('wrote BEST export table to ' .. checkpoint_path .. '_vqa.t7')
+    end
+  end
+  if iter % opt.save_model_every == 0 then
+    export(checkpoint_path .. iter .. '_vqa.t7')
+    print('wrote export table to ' .. checkpoint_path .. iter .. '_vqa.t7')
+  end
+  iter = iter + 1
+  if loss0 == nil then loss0 = loss[0] end
+  if loss[0] > loss0 * 20 then print('loss seems to be exploding, quitting.'); break end
+  if opt.max_iters > 0 and iter >= opt.max_iters then break end
+end

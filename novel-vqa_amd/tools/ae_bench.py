@@ -4,8 +4,10 @@ shape (001_train_arch1_text_autoencoder.lua: B = 1000, seq_length D = 16, E = R 
 the VQA vocabulary (V = 14773), on random sentences of lengths U{3..16}.  Prints ONE JSON line: ms per step and
 sentences/s (median over timed blocks after warm-up), the per-group profile of a separate profiled pass, and the
 step's fraction of the f32 MFMA roofline (FLOPs computed from the shape, 3 x forward).
+--arch 2: the image-first-token auto-encoder (001_train_arch2_text_autoencoder.lua, NVQA_ARCH_AE2) at the same shape,
+with the text script's zero image rows (nvqa_ae_step on an AE2 context) and its learning rate 5e-5.
 
-    python novel-vqa_amd/tools/ae_bench.py [--blocks 5 --steps 10 --warmup 5] [--out FILE]
+    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2] [--blocks 5 --steps 10 --warmup 5] [--out FILE]
 """
 import argparse
 import json
@@ -23,15 +25,16 @@ import __graft_entry__ as ge  # noqa: E402
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md "Peak FP32 (matrix)"
 
 
-def step_flops(B, T, V, E, R, L):
-    """3 x forward of a batch whose tmax is T: T encoder + T+1 decoder LSTM steps, T+1 projections"""
+def step_flops(B, T, V, E, R, L, arch=1):
+    """3 x forward of a batch whose tmax is T: T (arch 2: T + 2) encoder + T+1 decoder LSTM steps, T+1 projections"""
     lstm = sum(2 * B * 4 * R * ((E if l == 0 else R) + R) for l in range(L))
-    fwd = (2 * T + 1) * lstm + (T + 1) * 2.0 * B * R * (V + 1)
+    fwd = (2 * T + 1 + (2 if arch == 2 else 0)) * lstm + (T + 1) * 2.0 * B * R * (V + 1)
     return 3 * fwd
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arch", type=int, default=1, choices=(1, 2))
     ap.add_argument("--B", type=int, default=1000)
     ap.add_argument("--D", type=int, default=16)
     ap.add_argument("--V", type=int, default=14773)
@@ -45,7 +48,8 @@ def main():
     a = ap.parse_args()
     pkg = ge.load_package()
     b = pkg.binding
-    dims = b.Dims(b.ARCH_AE1, a.B, a.D, a.V, a.E, a.R, a.L, 0, 0, 0)
+    dims = b.Dims(b.ARCH_AE1 if a.arch == 1 else b.ARCH_AE2, a.B, a.D, a.V, a.E, a.R, a.L, 0, 0, 0)
+    lr = 1e-5 if a.arch == 1 else 5e-5
     ctx = b.Context(dims, 0)
     ctx.init_params(123, -0.08, 0.08)
     rng = np.random.default_rng(0)
@@ -61,7 +65,7 @@ def main():
     def one_step():
         it[0] += 1
         ctx.ae_step(batches[it[0] % len(batches)], b.Dropout(1, 0.5, 123, it[0]), want_loss=False)
-        ctx.adam_update(1e-5, 0.8, 0.999, 1e-8, 1e-6, 0.1)
+        ctx.adam_update(lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
 
     for _ in range(a.warmup):
         one_step()
@@ -92,8 +96,8 @@ def main():
     ctx.profile_enable(False)
     ctx.close()
     tmaxes = [int(np.nonzero(t.any(0))[0][-1]) + 1 for t in batches]
-    fl = float(np.mean([step_flops(a.B, T, a.V, a.E, a.R, a.L) for T in tmaxes]))
-    line = {"workload": "ae_arch1_text", "B": a.B, "D": a.D, "V": a.V, "E": a.E, "R": a.R, "L": a.L,
+    fl = float(np.mean([step_flops(a.B, T, a.V, a.E, a.R, a.L, a.arch) for T in tmaxes]))
+    line = {"workload": "ae_arch%d_text" % a.arch, "B": a.B, "D": a.D, "V": a.V, "E": a.E, "R": a.R, "L": a.L,
             "ms_per_step": round(ms, 4), "block_ms": [round(x, 4) for x in block_ms],
             "sentences_per_s": round(a.B / (ms * 1e-3), 1), "loss": loss,
             "tflop_per_step": round(fl / 1e12, 4), "achieved_tflops": round(fl / (ms * 1e-3) / 1e12, 2),
