@@ -46,10 +46,13 @@ extern "C" {
                          * (misc/AutoEncoder_text_nostart.lua); dims T = seq_length D, I = C = A = 0 */
 #define NVQA_ARCH_AE2 4 /* 001_train_autoencoder/001_train_arch2_text_autoencoder.lua: image-first-token LSTM auto-encoder
                          * (misc/AutoEncoder.lua); dims as NVQA_ARCH_AE1, the image row is E wide */
+#define NVQA_ARCH_AE2_WP 5 /* 001_train_autoencoder/004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua: the AE2 model fed
+                            * L2Normalize(features) W_p^T + b_p as its image row, with a frozen lookup table
+                            * (misc/AutoEncoderNull.lua); dims B, T = seq_length, V, E, R, L, I = feature width; C = A = 0 */
 
 /* Model dimensions (SURVEY.md symbol table). */
 typedef struct nvqa_dims {
-    int32_t arch; /* NVQA_ARCH1 | NVQA_ARCH2 | NVQA_ARCH_AE1 | NVQA_ARCH_AE2 */
+    int32_t arch; /* NVQA_ARCH1 | NVQA_ARCH2 | NVQA_ARCH_AE1 | NVQA_ARCH_AE2 | NVQA_ARCH_AE2_WP */
     int32_t B;    /* minibatch (QA pairs) per device             -batch_size          */
     int32_t T;    /* question buffer length (columns of ques_*)  buffer_size_q        */
     int32_t V;    /* question vocabulary size                    vocabulary_size_q    */
@@ -93,7 +96,8 @@ int nvqa_sync(nvqa_ctx *ctx); /* wait for all enqueued work (loss_out becomes va
  *  ae1 encoder     : LSTM layers as above (AutoEncoder_text_nostart.lua:89-110 parameters() order)
  *  ae1 decoder     : LSTM layers as above, then W_proj[(V+1) x R], b_proj[V+1]
  *  ae1 lookup      : W_lk[(V+1) x E] (row V+1 = the START / END token)
- *  ae2             : as ae1 (AutoEncoder.lua:86-107 parameters() order)                          */
+ *  ae2             : as ae1 (AutoEncoder.lua:86-107 parameters() order)
+ *  ae2_wp          : as ae2; the image projection W_p [E x I], b_p [E] lives outside the vector (nvqa_ae_wp_*)  */
 size_t nvqa_param_count(const nvqa_ctx *ctx);
 int nvqa_segments(const nvqa_ctx *ctx, size_t sizes_out[3]);
 int nvqa_init_params(nvqa_ctx *ctx, uint64_t seed, float lo, float hi);
@@ -255,6 +259,35 @@ int nvqa_ae_step_images(nvqa_ctx *ctx, const float *images, const int32_t *token
                         float *loss_out, float *dimages_out);
 int nvqa_ae_evaluate_images(nvqa_ctx *ctx, int32_t n, const float *images, const int32_t *tokens, float *loss_out,
                             int32_t *samples_out);
+/* ---- weak-paired auto-encoder (NVQA_ARCH_AE2_WP contexts) ---- */
+/* 004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua with misc/AutoEncoderNull.lua.  The CNN body is frozen and runs
+ * outside: feats [B x I] are its output (vgg: post-ReLU fc7 as nvqa_vgg16_fc7 returns it, I = 4096; inc: I = 2048).  The
+ * library L2-normalises them (in place on its copy, the caller's rows only) and forms the encoder's step-0 input
+ * x0 = f^ W_p^T + b_p.  The encoder then runs START and enc_tokens (0 -> 1) for 2 + tmax(enc_tokens) steps; enc_tokens =
+ * NULL is the null sentence (2 steps).  The decoder and the criterion read tokens, for tmax(tokens) + 1 steps.  The lookup
+ * table is frozen: its slice of nvqa_get_grads is zero, and nvqa_adam_update clamps, decays, updates and takes its
+ * statistics over [encoder | decoder] only.  nvqa_ae_step*, nvqa_ae_evaluate* and nvqa_rmsprop_update return an error on
+ * such a context; the calls below return an error on every other context.
+ * nvqa_ae_wp_step: one training forward + criterion + backward; the projection's gradient is kept for
+ * nvqa_ae_wp_get_projection_grads / nvqa_ae_wp_projection_adam. */
+int nvqa_ae_wp_step(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                    const nvqa_dropout *dropout, float *loss_out);
+/* Evaluate-mode loss and (samples_out not NULL) greedy decoding of n <= B rows; feats [n x I], enc_tokens [n x D] or NULL,
+ * tokens [n x D].  eval_split feeds enc_tokens = tokens (forward{feats, labels, labels}). */
+int nvqa_ae_wp_evaluate(nvqa_ctx *ctx, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                        float *loss_out, int32_t *samples_out);
+/* The projection Linear(I, E) (build_cnn's last module): w [E x I] (Torch layout), b [E].  nvqa_init_params sets
+ * w = uniform(lo, hi) from its seed and b = 0, as build_cnn does, and resets the projection's Adam state. */
+int nvqa_ae_wp_set_projection(nvqa_ctx *ctx, const float *w, const float *b);
+int nvqa_ae_wp_get_projection(nvqa_ctx *ctx, float *w_out, float *b_out);
+/* dW_p = dx0^T f^ and db_p = colsum(dx0) of the last step, dx0 = d(loss)/d(x0) */
+int nvqa_ae_wp_get_projection_grads(nvqa_ctx *ctx, float *w_out, float *b_out);
+/* The projection's own update (the cnn branch of the script, :318-325, :456-467): g += wd * x (wd != 0), then
+ * g = clamp(g, -clamp, clamp) (clamp > 0) -- the reverse of nvqa_adam_update's order -- then adam() with a step counter of
+ * its own.  stats_out (may be NULL; synchronises) = {||W_p||_2 (weight only), count(|lr g| >= 0.01 |x|) over W_p and b_p}
+ * of x before the update. */
+int nvqa_ae_wp_projection_adam(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
+                               float stats_out[2]);
 /* Valid on every context.  One pass over the flat vector: g = clamp(g, -clamp, clamp) (clamp > 0), g += wd * x, then
  * adam() of misc/optim_updates.lua:78-111 (step counter held by the context, reset by nvqa_init_params).
  * stats_out (may be NULL; synchronises) = {||x||_2, count(|lr g| >= 0.01 |x|)} of x before the update, g after clamp + wd

@@ -29,7 +29,7 @@ typedef struct nvqa_layout {
     size_t w_q, b_q, w_v, b_v, w_o, b_o; /* multimodal */
     /* arch2 */
     size_t w_p, b_p; /* cnn projection W_p [E x I], b_p [E] */
-    size_t w_lk;     /* lookup table [(V+1) x E] (arch2, ae1, ae2) */
+    size_t w_lk;     /* lookup table [(V+1) x E] (arch2, ae1, ae2, ae2_wp) */
     /* ae1 / ae2 (text auto-encoders): the encoder uses w_i2h.. above, the decoder these */
     size_t d_w_i2h[NVQA_MAX_LAYERS], d_b_i2h[NVQA_MAX_LAYERS];
     size_t d_w_h2h[NVQA_MAX_LAYERS], d_b_h2h[NVQA_MAX_LAYERS];
@@ -89,8 +89,9 @@ static inline int nvqa_layout_init_fusion(const nvqa_dims *d, int fusion, nvqa_l
         lo->b_o = off; off += A;
         lo->seg[2] = off - lo->seg[0] - lo->seg[1];
         lo->w_e = lo->b_e = lo->w_q = lo->b_q = lo->w_v = lo->b_v = 0;
-    } else if (d->arch == NVQA_ARCH_AE1 || d->arch == NVQA_ARCH_AE2) {
-        /* [encoder | decoder | lookup]: AutoEncoder_text_nostart.lua:89-110, AutoEncoder.lua:86-107 */
+    } else if (d->arch == NVQA_ARCH_AE1 || d->arch == NVQA_ARCH_AE2 || d->arch == NVQA_ARCH_AE2_WP) {
+        /* [encoder | decoder | lookup]: AutoEncoder_text_nostart.lua:89-110, AutoEncoder.lua:86-107 (AE2_WP: the same vector,
+         * AutoEncoderNull.lua leaves the lookup out of parameters(); its projection lives outside) */
         for (size_t l = 0; l < L; ++l) {
             const size_t in = l == 0 ? E : R;
             lo->in_dim[l] = (int32_t)in;

@@ -25,6 +25,7 @@
  * step stride is D+2; the lookup is a plain LookupTable and draws no mask (no ENC_LK / DEC_LK):
  *   NVQA_SITE_AE_TOP      decoder top h         idx = (b*(D+2) + s)*R + j
  *   NVQA_SITE_AE_LSTM     input of layer l >= 1 idx = (((k*L + l)*B + b)*(D+2) + t)*R + j   (encoder t = 0..D+1)
+ * The weak-paired auto-encoder (NVQA_ARCH_AE2_WP) draws the NVQA_ARCH_AE2 masks with the same indices.
  */
 #ifndef NVQA_RNG_H
 #define NVQA_RNG_H

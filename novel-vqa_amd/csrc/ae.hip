@@ -1,5 +1,6 @@
 // ae.hip -- the text auto-encoder of the reference's first stage (NVQA_ARCH_AE1): training forward, LanguageModelCriterion,
-// backward, evaluate-mode loss and greedy decoding, and the fused clamp / weight-decay / Adam update (any context).
+// backward, evaluate-mode loss and greedy decoding, and the fused clamp / weight-decay / Adam update (any context); the
+// arch2 text and weak-paired auto-encoders (NVQA_ARCH_AE2, NVQA_ARCH_AE2_WP) run the same code, below.
 //
 // Reference: 001_train_autoencoder/001_train_arch1_text_autoencoder.lua (lossFun :212-245, update :349-362, log line
 // :266-268, eval_split :148-194) with misc/AutoEncoder_text_nostart.lua (model :26-31, forward :215-343, backward :348-393,
@@ -17,6 +18,11 @@
 //   chain step q in [2, te)  : encoder step q: lookup of tok[:, q-2], 0 -> 1
 //   chain step q = te + s    : decoder step s, as above
 // with a plain LookupTable (no Dropout, no Tanh), and d(images) = layer 0's d(input) rows of chain step 0.
+// The weak-paired auto-encoder (NVQA_ARCH_AE2_WP, misc/AutoEncoderNull.lua with 004_train_arch2_weakpaired_autoencoder_*.lua)
+// is AE2's chain with two token streams: the encoder reads enc_tokens (te = 2 + tmax(enc_tokens), 2 for the null sentence),
+// the decoder and the criterion read tokens (tmax(tokens) + 1 steps).  Chain step 0 is x0 = L2Normalize(feats) W_p^T + b_p,
+// written by the projection GEMM; the lookup table is frozen (no lookup gradient), so layer 0's d(input) is needed for chain
+// step 0 only, where it is dx0, the projection's output gradient.
 // Per layer, one array of states over the whole chain (slot 0 = the zero initial state, slot q+1 = after chain step q):
 // the decoder's initial state IS the encoder's final slot, and in the backward pass the decoder's state gradient at its
 // step 0 flows into the encoder's last step through the ordinary recurrent product, with the encoder's W_h2h replaced by
@@ -39,7 +45,8 @@ using namespace nvqa;
 namespace nvqa {
 
 struct AeState {
-    bool ae2 = false;    // NVQA_ARCH_AE2: image row and START in front of the encoder's tokens
+    bool ae2 = false;    // NVQA_ARCH_AE2 (and AE2_WP): image row and START in front of the encoder's tokens
+    bool wp = false;     // NVQA_ARCH_AE2_WP: projected features as the image row, encoder tokens of their own, frozen lookup
     int D = 0, QM = 0;   // seq_length; chain steps the buffers hold (AE1 2 D + 1, AE2 2 D + 3)
     int ldl = 0;         // leading dimension of the logits (V + 1 rounded up to 4 floats; the padding columns stay zero)
     int tmax = 0;        // last step's tmax
@@ -70,6 +77,15 @@ struct AeState {
     float *rowloss = nullptr;   // [(D + 1) B]
     float *loss = nullptr;      // device scalar
     float *h_loss = nullptr;    // pinned
+    int32_t *etok = nullptr;    // AE2_WP: [B x D] encoder tokens of the current batch (device; 0 rows = the null sentence)
+    int32_t *h_etok = nullptr;  // AE2_WP: pinned staging
+    float *feat = nullptr;      // AE2_WP: [B x I] features, L2-normalised in place (f^, kept for dW_p)
+    float *h_feat = nullptr;    // AE2_WP: pinned staging
+    float *wp_x = nullptr, *wp_g = nullptr, *wp_m = nullptr, *wp_v = nullptr; // AE2_WP: [W_p (E x I) | b_p (E)], its gradient, Adam
+    double *wp_part = nullptr;  // AE2_WP: per-workgroup statistics of nvqa_ae_wp_projection_adam
+    int64_t wp_t = 0;           // AE2_WP: the projection's Adam step counter
+    hipEvent_t staged = nullptr; // AE2_WP: the last batch's host-to-device copies are done (the staging buffers are free)
+    bool staged_rec = false;
     float *slabs = nullptr;     // split-K partials of the weight gradients
     size_t slab_floats = 0;
     float *colpart = nullptr;   // column-sum partials
@@ -471,6 +487,38 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a)
     if (threadIdx.x == 0) { a.part[2 * blockIdx.x] = sh[0][0]; a.part[2 * blockIdx.x + 1] = sh[1][0]; }
 }
 
+// the weak-paired AE's projection update (the cnn branch of 004_train_arch2_weakpaired_autoencoder_vgg.lua: g += wd x, then
+// clamp (:318-322), then adam of misc/optim_updates.lua:78-111 with lrs = 1, cnnFinalLearningScales of the final Linear), over
+// x = [W_p | b_p], n values; part[2 blk] = sum x^2 of the weight (i < nw: cnn:get(40).weight), part[2 blk + 1] =
+// count(|lr g| >= 0.01 |x|) over all n (:302-305), both of x before the update
+__global__ __launch_bounds__(256) void k_ae_wp_adam(float *x, float *m, float *v, const float *g, size_t n, size_t nw, float lr,
+                                                    float b1, float b2, float eps, float wd, float clamp, float step, double *part)
+{
+    __shared__ double sh[2][256];
+    double sq = 0, cnt = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float xi = x[i];
+        float gi = g[i];
+        if (wd != 0.f) gi += wd * xi;
+        if (clamp > 0.f) gi = fminf(fmaxf(gi, -clamp), clamp);
+        if (i < nw) sq += (double)xi * (double)xi;
+        cnt += fabsf(gi * lr) >= fabsf(xi) * 0.01f ? 1.0 : 0.0;
+        const float mi = b1 * m[i] + (1.f - b1) * gi, vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        x[i] = xi - step * (mi / (sqrtf(vi) + eps));
+    }
+    if (!part) return;
+    sh[0][threadIdx.x] = sq;
+    sh[1][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = sh[0][0]; part[2 * blockIdx.x + 1] = sh[1][0]; }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // GEMM configurations (gemm_f32.h).  Projection and time-batched products: 128 x 128 tiles (16x16x4 MFMA, 8 waves) for
 // the short-K forms, the 4-wave 32x32x2 form for the long-K weight gradients (the choice nvqa_api.hip measured for the same
@@ -529,7 +577,8 @@ int ae_create(nvqa_ctx *c)
     c->ae = new AeState();
     AeState &a = *c->ae;
     const size_t B = d.B, D = d.T, E = d.E, R = d.R, L = d.L, V = d.V;
-    a.ae2 = d.arch == NVQA_ARCH_AE2;
+    a.ae2 = d.arch == NVQA_ARCH_AE2 || d.arch == NVQA_ARCH_AE2_WP;
+    a.wp = d.arch == NVQA_ARCH_AE2_WP;
     a.D = (int)D;
     a.QM = (int)(2 * D + (a.ae2 ? 3 : 1));
     a.dstr = (int)D + (a.ae2 ? 1 : 0);
@@ -546,17 +595,32 @@ int ae_create(nvqa_ctx *c)
     }
     AE_ALLOC(a.cur, B);
     AE_ALLOC(a.samples, B * D);
-    AE_ALLOC(a.lk_tok, QM * B);
-    AE_ALLOC(a.lk_tc, QM * B + 1);
-    AE_ALLOC(a.lk_start, QM * B + 1);
-    AE_ALLOC(a.lk_pos, QM * B);
-    AE_ALLOC(a.lk_part, QM * B * E);
-    NVQA_HIP(hipHostMalloc((void **)&a.h_lk, (4 * QM * B + 4) * 4, hipHostMallocDefault));
+    if (!a.wp) { // the frozen lookup of AE2_WP takes no gradient
+        AE_ALLOC(a.lk_tok, QM * B);
+        AE_ALLOC(a.lk_tc, QM * B + 1);
+        AE_ALLOC(a.lk_start, QM * B + 1);
+        AE_ALLOC(a.lk_pos, QM * B);
+        AE_ALLOC(a.lk_part, QM * B * E);
+        NVQA_HIP(hipHostMalloc((void **)&a.h_lk, (4 * QM * B + 4) * 4, hipHostMallocDefault));
+    }
     NVQA_HIP(hipHostMalloc((void **)&a.h_tok, B * D * 4, hipHostMallocDefault));
     NVQA_HIP(hipHostMalloc((void **)&a.h_loss, 16, hipHostMallocDefault));
-    if (a.ae2) {
+    if (a.ae2 && !a.wp) {
         AE_ALLOC(a.img, B * E);
         NVQA_HIP(hipHostMalloc((void **)&a.h_img, B * E * 4, hipHostMallocDefault));
+    }
+    if (a.wp) {
+        const size_t I = d.I, NP = E * I + E;
+        AE_ALLOC(a.etok, B * D);
+        NVQA_HIP(hipHostMalloc((void **)&a.h_etok, B * D * 4, hipHostMallocDefault));
+        AE_ALLOC(a.feat, B * I);
+        NVQA_HIP(hipHostMalloc((void **)&a.h_feat, B * I * 4, hipHostMallocDefault));
+        AE_ALLOC(a.wp_x, NP);
+        AE_ALLOC(a.wp_g, NP);
+        AE_ALLOC(a.wp_m, NP);
+        AE_ALLOC(a.wp_v, NP);
+        AE_ALLOC(a.wp_part, 2 * 1024);
+        NVQA_HIP(hipEventCreateWithFlags(&a.staged, hipEventDisableTiming));
     }
     AE_ALLOC(a.X0, QM * B * E);
     for (size_t l = 0; l < L; ++l) {
@@ -584,13 +648,15 @@ void ae_destroy(nvqa_ctx *c)
     if (!c->ae) return;
     AeState &a = *c->ae;
     void *ptrs[] = {a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
-                    a.logits, a.rowloss, a.loss, a.slabs, a.colpart, a.img};
+                    a.logits, a.rowloss, a.loss, a.slabs, a.colpart, a.img, a.etok, a.feat, a.wp_x, a.wp_g, a.wp_m, a.wp_v,
+                    a.wp_part};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    if (a.staged) (void)hipEventDestroy(a.staged);
     for (int l = 0; l < NVQA_MAX_LAYERS; ++l)
         for (void *p : {(void *)a.Gt[l], (void *)a.Hs[l], (void *)a.Cs[l], (void *)a.U[l]})
             if (p) (void)hipFree(p);
-    for (void *p : {(void *)a.h_lk, (void *)a.h_tok, (void *)a.h_loss, (void *)a.h_img})
+    for (void *p : {(void *)a.h_lk, (void *)a.h_tok, (void *)a.h_loss, (void *)a.h_img, (void *)a.h_etok, (void *)a.h_feat})
         if (p) (void)hipHostFree(p);
     delete c->ae;
     c->ae = nullptr;
@@ -679,7 +745,16 @@ static int ae_embed(nvqa_ctx *c, int q0, int q1, const int32_t *direct, const Dr
     const nvqa_dims &d = c->d;
     if (q1 <= q0) return 0;
     ProfScope ps(c, PF_AE_EMB, 0, (double)(q1 - q0) * d.B * d.E * 8);
-    if (a.ae2)
+    if (a.wp) { // AE2's assembly per token stream: encoder rows [1, te) from etok, decoder rows from tok; row 0 is ae_wp_project's
+        const int e0 = std::max(q0, 1), e1 = std::min(q1, a.te), d0 = std::max(q0, a.te);
+        const dim3 nt(std::min(256, (d.E + 63) / 64 * 64));
+        if (e1 > e0)
+            hipLaunchKernelGGL(k_ae2_assemble, dim3((unsigned)((e1 - e0) * d.B)), nt, 0, c->s, a.etok, (const int32_t *)nullptr,
+                               (const float *)nullptr, d.B, a.D, d.V, d.E, a.te, e0, c->P + c->lo.w_lk, a.X0);
+        if (q1 > d0)
+            hipLaunchKernelGGL(k_ae2_assemble, dim3((unsigned)((q1 - d0) * d.B)), nt, 0, c->s, a.tok, direct, (const float *)nullptr,
+                               d.B, a.D, d.V, d.E, a.te, d0, c->P + c->lo.w_lk, a.X0);
+    } else if (a.ae2)
         hipLaunchKernelGGL(k_ae2_assemble, dim3((unsigned)((q1 - q0) * d.B)), dim3(std::min(256, (d.E + 63) / 64 * 64)), 0, c->s,
                            a.tok, direct, a.img_live ? a.img : nullptr, d.B, a.D, d.V, d.E, a.te, q0, c->P + c->lo.w_lk, a.X0);
     else
@@ -689,12 +764,25 @@ static int ae_embed(nvqa_ctx *c, int q0, int q1, const int32_t *direct, const Dr
     return 0;
 }
 
+// AE2_WP: chain step 0 of X0 = f^ W_p^T + b_p (build_cnn's final Linear, misc/net_utils.lua:37-41), one GEMM M = B, N = E, K = I
+static int ae_wp_project(nvqa_ctx *c)
+{
+    AeState &a = *c->ae;
+    const int B = c->d.B, E = c->d.E, I = c->d.I;
+    ProfScope ps(c, PF_AE_WP_PROJ_FWD, 2.0 * B * E * (double)I);
+    GemmArgs g = ae_args(a.feat, I, a.wp_x, I, B, E, I);
+    const EpiAeBias e{a.X0, E, a.wp_x + (size_t)E * I};
+    AE_LAUNCH(AeCfgWide, A_KC, B_KC, false, EpiAeBias, 0, g, e);
+    return 0;
+}
+
 // teacher-forced forward of the whole chain (training and evaluate mode) + the criterion; grad: d(logits) in place
 static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool grad)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
     const int B = d.B, L = d.L, Q = a.te + a.tmax + 1, Vp1 = d.V + 1;
+    if (a.wp) NVQA_TRY(ae_wp_project(c));
     NVQA_TRY(ae_embed(c, 0, Q, nullptr, dr));
     for (int l = 0; l < L; ++l) {
         if (l > 0) NVQA_TRY(ae_layer_input(c, l, 0, Q, dr));
@@ -750,10 +838,11 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
                                  B, R, last ? 0 : 4 * R);
             AE_LAUNCH(AeCfgStepBwd, A_KC, B_NC, false, EpiLstmBwd, 0, g, e);
         }
-        {   // d(input) of both phases
-            ProfScope ps(c, PF_AE_DGRAD, 2.0 * Q * B * 4.0 * R * in);
+        {   // d(input) of both phases (AE2_WP, layer 0: chain step 0 only, dx0 -- the frozen lookup takes no gradient)
+            const bool cut = a.wp && l == 0;
+            ProfScope ps(c, PF_AE_DGRAD, 2.0 * (cut ? 1 : Q) * B * 4.0 * R * in);
             for (int ph = 0; ph < 2; ++ph) {
-                const int q0 = ph ? TE : 0, q1 = ph ? Q : TE;
+                const int q0 = ph ? TE : 0, q1 = cut ? (ph ? q0 : 1) : (ph ? Q : TE);
                 if (q1 <= q0) continue;
                 GemmArgs g = ae_args(a.Gt[l] + (size_t)q0 * B * 4 * R, 4 * R, c->P + w_i2h_of(c, l, ph == 1), in, (q1 - q0) * B, in, 4 * R);
                 const EpiStore e{a.dX + (size_t)q0 * B * in, in, 0};
@@ -779,6 +868,13 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
             NVQA_HIP(hipGetLastError());
         }
     }
+    if (a.wp) { // the projection: dW_p = dx0^T f^ (K = B), db_p = colsum(dx0); dx0 = layer 0's d(input) rows of chain step 0
+        const int I = d.I;
+        ProfScope ps(c, PF_AE_WP_PROJ_BWD, 2.0 * B * E * (double)I);
+        NVQA_TRY(wgrad(c, a.dX, E, a.feat, I, E, I, B, a.wp_g));
+        NVQA_TRY(colsum(c, a.dX, B, E, E, a.wp_g + (size_t)E * I, nullptr));
+        return 0;
+    }
     {   // lookup table: both token streams into one gradient (AE2: every chain row but the image's)
         ProfScope ps(c, PF_AE_EMB_BWD, 0, (double)Q * B * E * (a.ae2 ? 4 : 12));
         NVQA_HIP(hipMemsetAsync(c->G + c->lo.w_lk, 0, (size_t)Vp1 * E * 4, c->s));
@@ -795,12 +891,18 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
 
 // host side of a batch: tokens -> device, tmax, the criterion's n, and (training) the token -> rows index of the lookup
 // gradient (a counting sort: deterministic row order per token).  AE2: images [n x E] (NULL: zeros) -> the device rows.
-static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *images, bool index, int *ncount)
+// AE2_WP: enc_tokens [n x D] (NULL: the null sentence) -> etok and te = 2 + their tmax; feats [n x I] -> feat, L2-normalised
+// over the n rows (the padding rows stay zero).
+static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *images, bool index, int *ncount,
+                     const float *feats = nullptr, const int32_t *enc_tokens = nullptr)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
     const int B = d.B, D = a.D, V = d.V;
-    NVQA_HIP(hipStreamSynchronize(c->s)); // the staging buffers may still feed the previous step's copies
+    // the staging buffers may still feed the previous step's copies.  AE2_WP waits for those copies only, so that staging its
+    // B x I features overlaps the previous step's kernels
+    if (a.wp && a.staged_rec) NVQA_HIP(hipEventSynchronize(a.staged));
+    else NVQA_HIP(hipStreamSynchronize(c->s));
     int tmax = 0, cnt = 0;
     for (int b = 0; b < B; ++b)
         for (int t = 0; t < D; ++t) {
@@ -818,10 +920,31 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *ima
             else if (first) { ++cnt; first = false; }
         }
     }
+    int tmax_e = 0;
+    if (a.wp) {
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < D; ++t) {
+                const int v = b < n && enc_tokens ? enc_tokens[(size_t)b * D + t] : 0;
+                if (v < 0 || v > V) { set_error("ae: enc_tokens %d at (%d, %d) outside 0..%d", v, b, t, V); return -1; }
+                a.h_etok[(size_t)b * D + t] = v;
+                if (v) tmax_e = std::max(tmax_e, t + 1);
+            }
+    }
     a.tmax = tmax;
-    a.te = a.ae2 ? tmax + 2 : tmax;
+    a.te = a.wp ? tmax_e + 2 : (a.ae2 ? tmax + 2 : tmax);
     *ncount = cnt;
     NVQA_HIP(hipMemcpyAsync(a.tok, a.h_tok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
+    if (a.wp) {
+        const size_t I = d.I;
+        NVQA_HIP(hipMemcpyAsync(a.etok, a.h_etok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
+        memcpy(a.h_feat, feats, (size_t)n * I * 4);
+        if (n < B) memset(a.h_feat + (size_t)n * I, 0, (size_t)(B - n) * I * 4);
+        NVQA_HIP(hipMemcpyAsync(a.feat, a.h_feat, (size_t)B * I * 4, hipMemcpyHostToDevice, c->s));
+        NVQA_HIP(hipEventRecord(a.staged, c->s));
+        a.staged_rec = true;
+        ProfScope ps(c, PF_AE_WP_PROJ_FWD, 0, (double)n * I * 12);
+        NVQA_TRY(l2norm_rows_launch(c->s, a.feat, n, (int)I));
+    }
     a.img_live = a.ae2 && images;
     if (a.img_live) {
         const size_t E = d.E;
@@ -868,10 +991,32 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *ima
 
 float ae_last_loss(const nvqa_ctx *c) { return c->ae ? *c->ae->h_loss : 0.f; }
 
+// AE2_WP part of nvqa_init_params: W_p = uniform(lo, hi) from the seed, b_p = 0 (build_cnn, misc/net_utils.lua:38-40), and a
+// fresh start of the projection's Adam
+int ae_wp_init(nvqa_ctx *c, uint64_t seed, float lo, float hi)
+{
+    AeState &a = *c->ae;
+    const size_t nw = (size_t)c->d.E * c->d.I, np = nw + c->d.E;
+    std::vector<float> w(np, 0.f);
+    for (size_t i = 0; i < nw; ++i) { // site 98: the flat vector's draw uses 99
+        const float u = (float)(nvqa_hash32(seed, 0, 98u, i) >> 8) * (1.0f / 16777216.0f);
+        w[i] = lo + (hi - lo) * u;
+    }
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    NVQA_HIP(hipMemcpy(a.wp_x, w.data(), np * 4, hipMemcpyHostToDevice));
+    NVQA_HIP(hipMemset(a.wp_m, 0, np * 4));
+    NVQA_HIP(hipMemset(a.wp_v, 0, np * 4));
+    a.wp_t = 0;
+    return 0;
+}
+
 static int ae_check(nvqa_ctx *c)
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
-    if (!is_ae(c->d) || !c->ae) { set_error("not an auto-encoder context (arch %d; NVQA_ARCH_AE1 = 3, NVQA_ARCH_AE2 = 4)", c->d.arch); return -1; }
+    if (!is_ae(c->d) || !c->ae) {
+        set_error("not an auto-encoder context (arch %d; NVQA_ARCH_AE1 = 3, NVQA_ARCH_AE2 = 4, NVQA_ARCH_AE2_WP = 5)", c->d.arch);
+        return -1;
+    }
     NVQA_HIP(hipSetDevice(c->device));
     return 0;
 }
@@ -883,13 +1028,31 @@ static int ae_check_images(nvqa_ctx *c, const char *fn)
     return 0;
 }
 
+// AE2_WP: the step carries features; the text calls have none
+static int ae_check_not_wp(nvqa_ctx *c, const char *fn)
+{
+    NVQA_TRY(ae_check(c));
+    if (c->d.arch == NVQA_ARCH_AE2_WP) {
+        set_error("%s: not available on a weak-paired auto-encoder context (NVQA_ARCH_AE2_WP: nvqa_ae_wp_step / nvqa_ae_wp_evaluate)", fn);
+        return -1;
+    }
+    return 0;
+}
+
+static int ae_check_wp(nvqa_ctx *c, const char *fn)
+{
+    NVQA_TRY(ae_check(c));
+    if (c->d.arch != NVQA_ARCH_AE2_WP) { set_error("%s: an NVQA_ARCH_AE2_WP context expected (arch %d)", fn, c->d.arch); return -1; }
+    return 0;
+}
+
 static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out,
-                        float *dimages_out)
+                        float *dimages_out, const float *feats = nullptr, const int32_t *enc_tokens = nullptr)
 {
     if (!tokens) { set_error("tokens is NULL"); return -1; }
     const Drop dr = ae_drop(dropout, true);
     int ncount = 0;
-    NVQA_TRY(ae_upload(c, c->d.B, tokens, images, true, &ncount));
+    NVQA_TRY(ae_upload(c, c->d.B, tokens, images, !c->ae->wp, &ncount, feats, enc_tokens));
     NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
     NVQA_TRY(ae_backward(c, dr));
     c->have_grads = true;
@@ -902,14 +1065,15 @@ static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens,
     return 0;
 }
 
-static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, float *loss_out, int32_t *samples_out)
+static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, float *loss_out, int32_t *samples_out,
+                            const float *feats = nullptr, const int32_t *enc_tokens = nullptr)
 {
     if (!tokens) { set_error("tokens is NULL"); return -1; }
     if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
     AeState &a = *c->ae;
     const Drop dr = ae_drop(nullptr, false);
     int ncount = 0;
-    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount));
+    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount, feats, enc_tokens));
     NVQA_TRY(ae_forward(c, dr, n, ncount, false));
     if (samples_out) {
         // sample(): the encoder state is the one just computed (slot te); the decoder is fed START, then its own argmax
@@ -940,13 +1104,13 @@ static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const i
 // AE2: images = NULL (the text script's zero image rows)
 extern "C" int nvqa_ae_step(nvqa_ctx *c, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out)
 {
-    NVQA_TRY(ae_check(c));
+    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_step"));
     return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr);
 }
 
 extern "C" int nvqa_ae_evaluate(nvqa_ctx *c, int32_t n, const int32_t *tokens, float *loss_out, int32_t *samples_out)
 {
-    NVQA_TRY(ae_check(c));
+    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_evaluate"));
     return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out);
 }
 
@@ -964,6 +1128,85 @@ extern "C" int nvqa_ae_evaluate_images(nvqa_ctx *c, int32_t n, const float *imag
     return ae_evaluate_impl(c, n, images, tokens, loss_out, samples_out);
 }
 
+extern "C" int nvqa_ae_wp_step(nvqa_ctx *c, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                               const nvqa_dropout *dropout, float *loss_out)
+{
+    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_step"));
+    if (!feats) { set_error("nvqa_ae_wp_step: feats is NULL"); return -1; }
+    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr, feats, enc_tokens);
+}
+
+extern "C" int nvqa_ae_wp_evaluate(nvqa_ctx *c, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                                   float *loss_out, int32_t *samples_out)
+{
+    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_evaluate"));
+    if (!feats) { set_error("nvqa_ae_wp_evaluate: feats is NULL"); return -1; }
+    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, feats, enc_tokens);
+}
+
+extern "C" int nvqa_ae_wp_set_projection(nvqa_ctx *c, const float *w, const float *b)
+{
+    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_set_projection"));
+    if (!w || !b) { set_error("NULL argument"); return -1; }
+    AeState &a = *c->ae;
+    const size_t nw = (size_t)c->d.E * c->d.I;
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    NVQA_HIP(hipMemcpy(a.wp_x, w, nw * 4, hipMemcpyHostToDevice));
+    NVQA_HIP(hipMemcpy(a.wp_x + nw, b, (size_t)c->d.E * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+static int ae_wp_copy_out(nvqa_ctx *c, const float *src, float *w_out, float *b_out)
+{
+    if (!w_out || !b_out) { set_error("NULL argument"); return -1; }
+    const size_t nw = (size_t)c->d.E * c->d.I;
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    NVQA_HIP(hipMemcpy(w_out, src, nw * 4, hipMemcpyDeviceToHost));
+    NVQA_HIP(hipMemcpy(b_out, src + nw, (size_t)c->d.E * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nvqa_ae_wp_get_projection(nvqa_ctx *c, float *w_out, float *b_out)
+{
+    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_get_projection"));
+    return ae_wp_copy_out(c, c->ae->wp_x, w_out, b_out);
+}
+
+extern "C" int nvqa_ae_wp_get_projection_grads(nvqa_ctx *c, float *w_out, float *b_out)
+{
+    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_get_projection_grads"));
+    if (!c->have_grads) { set_error("nvqa_ae_wp_get_projection_grads before any nvqa_ae_wp_step"); return -1; }
+    return ae_wp_copy_out(c, c->ae->wp_g, w_out, b_out);
+}
+
+extern "C" int nvqa_ae_wp_projection_adam(nvqa_ctx *c, float lr, float beta1, float beta2, float eps, float wd, float clamp,
+                                          float stats_out[2])
+{
+    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_projection_adam"));
+    if (!c->have_grads) { set_error("nvqa_ae_wp_projection_adam before any nvqa_ae_wp_step"); return -1; }
+    AeState &a = *c->ae;
+    const size_t nw = (size_t)c->d.E * c->d.I, n = nw + c->d.E;
+    const int NB = 1024;
+    a.wp_t += 1;
+    const double t = (double)a.wp_t;
+    const float step = (float)(lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
+    ProfScope ps(c, PF_ADAM, 0, 28.0 * n);
+    hipLaunchKernelGGL(k_ae_wp_adam, dim3(NB), dim3(256), 0, c->s, a.wp_x, a.wp_m, a.wp_v, (const float *)a.wp_g, n, nw, lr, beta1,
+                       beta2, eps, wd, clamp, step, stats_out ? a.wp_part : (double *)nullptr);
+    NVQA_HIP(hipGetLastError());
+    if (stats_out) {
+        std::vector<double> h(2 * NB);
+        NVQA_HIP(hipMemcpyAsync(h.data(), a.wp_part, 2 * NB * sizeof(double), hipMemcpyDeviceToHost, c->s));
+        NVQA_HIP(hipStreamSynchronize(c->s));
+        double sq = 0, cnt = 0;
+        for (int b = 0; b < NB; ++b) { sq += h[2 * b]; cnt += h[2 * b + 1]; }
+        stats_out[0] = (float)sqrt(sq);
+        stats_out[1] = (float)cnt;
+    }
+    return 0;
+}
+
+// AE2_WP: [encoder | decoder] only (the reference's params; the frozen lookup is left out of parameters())
 extern "C" int nvqa_adam_update(nvqa_ctx *c, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                                 float stats_out[2])
 {
@@ -981,9 +1224,10 @@ extern "C" int nvqa_adam_update(nvqa_ctx *c, float lr, float beta1, float beta2,
         c->adam_t = 0;
     }
     c->adam_t += 1;
-    ProfScope ps(c, PF_ADAM, 0, 28.0 * n);
+    ProfScope ps(c, PF_ADAM, 0, 28.0 * (c->d.arch == NVQA_ARCH_AE2_WP ? c->lo.seg[0] + c->lo.seg[1] : n));
     AdamArgs a = {};
-    a.x = c->P; a.m = c->adam_m; a.v = c->adam_v; a.g = c->G; a.n = n;
+    a.x = c->P; a.m = c->adam_m; a.v = c->adam_v; a.g = c->G;
+    a.n = c->d.arch == NVQA_ARCH_AE2_WP ? c->lo.seg[0] + c->lo.seg[1] : n;
     a.seg0 = c->lo.seg[0]; a.seg1 = c->lo.seg[0] + c->lo.seg[1];
     const float inv_world = 1.0f / (float)c->world;
     for (int i = 0; i < 3; ++i) a.gs[i] = c->gscale[i] * inv_world;

@@ -48,7 +48,8 @@ static const char *kProfNames[PF_COUNT] = {
     "colsum",        "emb_bwd",       "rmsprop",       "allreduce",    "gather_batch", "lstm_bwd_finish",
     "ride_gemm",
     "ae_emb_fwd",    "ae_gemm_i2h",   "ae_lstm_step_fwd", "ae_gemm_proj_fwd", "ae_softmax_ce", "ae_gemm_proj_bwd",
-    "ae_lstm_step_bwd", "ae_gemm_dgrad", "ae_gemm_wgrad", "ae_emb_bwd",      "adam"};
+    "ae_lstm_step_bwd", "ae_gemm_dgrad", "ae_gemm_wgrad", "ae_emb_bwd",      "adam",
+    "ae_wp_proj_fwd", "ae_wp_proj_bwd"};
 
 
 static void prof_collect(nvqa_ctx *c)
@@ -166,15 +167,20 @@ template <class T> static int dalloc(T **p, size_t n)
 static int check_dims(const nvqa_dims *d)
 {
     if (!d) { set_error("dims is NULL"); return -1; }
-    if (is_ae(*d)) { // text auto-encoders: B, T = seq_length, V, E, R, L; no image features, fusion or answers
-        if (d->B < 1 || d->T < 1 || d->V < 1 || d->E < 4 || d->R < 4 || d->L < 1 || d->L > NVQA_MAX_LAYERS || d->I || d->C || d->A) {
-            set_error("auto-encoder: bad dims (B=%d T=%d V=%d E=%d R=%d L=%d; I, C, A must be 0)", d->B, d->T, d->V, d->E, d->R, d->L);
+    if (d->arch == NVQA_ARCH_AE2_WP && (d->I < 4 || d->I % 4)) { // the weak-paired AE's features: whole float4 rows
+        set_error("weak-paired auto-encoder: I must be a positive multiple of 4 (got I=%d)", d->I);
+        return -1;
+    }
+    if (is_ae(*d)) { // text auto-encoders: B, T = seq_length, V, E, R, L; no image features (AE2_WP: I), fusion or answers
+        if (d->B < 1 || d->T < 1 || d->V < 1 || d->E < 4 || d->R < 4 || d->L < 1 || d->L > NVQA_MAX_LAYERS ||
+            (d->I && d->arch != NVQA_ARCH_AE2_WP) || d->C || d->A) {
+            set_error("auto-encoder: bad dims (B=%d T=%d V=%d E=%d R=%d L=%d; C, A (and I but on arch 5) must be 0)", d->B, d->T, d->V, d->E, d->R, d->L);
             return -1;
         }
         if (d->E % 4 || d->R % 4) { set_error("auto-encoder: E, R must be multiples of 4 (got E=%d R=%d)", d->E, d->R); return -1; }
         return 0;
     }
-    if (d->arch != NVQA_ARCH1 && d->arch != NVQA_ARCH2) { set_error("arch must be 1, 2, 3 or 4"); return -1; }
+    if (d->arch != NVQA_ARCH1 && d->arch != NVQA_ARCH2) { set_error("arch must be 1, 2, 3, 4 or 5"); return -1; }
     if (d->B < 1 || d->T < 1 || d->V < 1 || d->L < 1 || d->L > NVQA_MAX_LAYERS) {
         set_error("bad dims (B=%d T=%d V=%d L=%d)", d->B, d->T, d->V, d->L);
         return -1;
@@ -655,6 +661,7 @@ extern "C" int nvqa_init_params(nvqa_ctx *c, uint64_t seed, float lo, float hi)
         p[i] = lo + (hi - lo) * u;
     }
     NVQA_TRY(nvqa_set_params(c, p.data()));
+    if (c->d.arch == NVQA_ARCH_AE2_WP) NVQA_TRY(ae_wp_init(c, seed, lo, hi));
     NVQA_HIP(hipMemset(c->M2, 0, c->lo.total * 4));
     if (c->adam_m) { // a fresh start of nvqa_adam_update too
         NVQA_HIP(hipMemset(c->adam_m, 0, c->lo.total * 4));
@@ -688,6 +695,13 @@ extern "C" int nvqa_get_grads(nvqa_ctx *c, float *out, float clamp)
     if (clamp > 0.f)
         for (float &v : in) v = std::min(std::max(v, -clamp), clamp);
     to_abi(c, in, out);
+    return 0;
+}
+
+int nvqa::l2norm_rows_launch(hipStream_t s, float *F, int n, int I)
+{
+    hipLaunchKernelGGL(k_l2norm_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, F, (int64_t)n, I, 0, I);
+    NVQA_HIP(hipGetLastError());
     return 0;
 }
 
@@ -1705,6 +1719,10 @@ extern "C" int nvqa_rmsprop_update(nvqa_ctx *c, float lr, float alpha, float eps
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
     if (!c->have_grads) { set_error("nvqa_rmsprop_update before any nvqa_step"); return -1; }
+    if (c->d.arch == NVQA_ARCH_AE2_WP) { // it would decay the frozen lookup table
+        set_error("nvqa_rmsprop_update: not available on a weak-paired auto-encoder context (frozen lookup; nvqa_adam_update)");
+        return -1;
+    }
     NVQA_HIP(hipSetDevice(c->device));
     ProfScope ps(c, PF_RMSPROP, 0, 20.0 * c->lo.total);
     const float inv_world = 1.0f / (float)c->world;

@@ -14,9 +14,12 @@
 namespace nvqa {
 
 void set_error(const char *fmt, ...);
-int ae_create(nvqa_ctx *c);  // ae.hip: the buffers of an NVQA_ARCH_AE1 / AE2 context (instead of the VQA step's)
+int ae_create(nvqa_ctx *c);  // ae.hip: the buffers of an NVQA_ARCH_AE1 / AE2 / AE2_WP context (instead of the VQA step's)
 void ae_destroy(nvqa_ctx *c);
 float ae_last_loss(const nvqa_ctx *c); // loss of the last nvqa_ae_step / nvqa_ae_evaluate (after a synchronisation)
+int ae_wp_init(nvqa_ctx *c, uint64_t seed, float lo, float hi); // NVQA_ARCH_AE2_WP: the projection's part of nvqa_init_params
+// nvqa_api.hip: k_l2norm_rows (kernels.h) over rows [0, n) of F [n x I] in place (the weak-paired auto-encoder's features)
+int l2norm_rows_launch(hipStream_t s, float *F, int n, int I);
 
 #define NVQA_HIP(expr)                                                                           \
     do {                                                                                         \
@@ -70,6 +73,8 @@ enum ProfId {
     PF_AE_WGRAD,     // time-batched weight gradients + bias sums
     PF_AE_EMB_BWD,   // lookup-table gradient
     PF_ADAM,         // nvqa_adam_update
+    PF_AE_WP_PROJ_FWD, // weak-paired AE: feature L2 norm + x0 = f^ W_p^T + b_p
+    PF_AE_WP_PROJ_BWD, // weak-paired AE: dW_p, db_p
     PF_COUNT
 };
 
@@ -93,7 +98,7 @@ struct ProfEntry {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
-struct AeState; // ae.hip: buffers of the text auto-encoders (NVQA_ARCH_AE1, NVQA_ARCH_AE2)
+struct AeState; // ae.hip: buffers of the text auto-encoders (NVQA_ARCH_AE1, NVQA_ARCH_AE2, NVQA_ARCH_AE2_WP)
 
 struct Dataset {
     int64_t n_q = 0, n_img = 0;
@@ -232,5 +237,5 @@ struct nvqa_ctx {
 
 namespace nvqa {
 // a text auto-encoder context (ae.hip runs its step; the VQA entry points refuse it)
-static inline bool is_ae(const nvqa_dims &d) { return d.arch == NVQA_ARCH_AE1 || d.arch == NVQA_ARCH_AE2; }
+static inline bool is_ae(const nvqa_dims &d) { return d.arch == NVQA_ARCH_AE1 || d.arch == NVQA_ARCH_AE2 || d.arch == NVQA_ARCH_AE2_WP; }
 } // namespace nvqa

@@ -1,7 +1,9 @@
 """Text auto-encoder pre-training (the reference's first stage, 001_train_autoencoder/001_train_arch1_text_autoencoder.lua
 and 001_train_arch2_text_autoencoder.lua) on the library's NVQA_ARCH_AE1 / NVQA_ARCH_AE2 contexts: the data loader, the
 training loop with its log line and learning-rate decay, eval_split, and the export that VQATrainer.init_from_autoencoder
-reads (002_convert_text_model_arch1.lua:27-39; arch2: the table of lua/convert_ae_arch2.lua)."""
+reads (002_convert_text_model_arch1.lua:27-39; arch2: the table of lua/convert_ae_arch2.lua).
+The weak-paired auto-encoder of the second stage (004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua) runs on an
+NVQA_ARCH_AE2_WP context: WeakPairedDataLoader and WeakPairedAETrainer."""
 import json
 
 import numpy as np
@@ -180,3 +182,170 @@ class AETrainer:
             t7.save(path, {"encoder": x[:seg[0]].copy(), "lookup_table": np.ascontiguousarray(w_lk), "layout": t7.LAYOUT_MARK})
             return
         t7.save(path, {"lookup": np.ascontiguousarray(w_lk.T), "encoder": x[:seg[0]].copy(), "layout": t7.LAYOUT_MARK})
+
+    def export_params(self, path):
+        """The whole flat vector [encoder | decoder | lookup] (include/nvqa_layout.h order) as {params, layout = 'nvqa'}: what
+        the weak-paired script's -start_from_text takes from a text checkpoint (protos.ae), read by
+        WeakPairedAETrainer.init_from_text."""
+        t7.save(path, {"params": self.ctx.get_params(), "layout": t7.LAYOUT_MARK})
+
+
+class WeakPairedDataLoader(DataLoader):
+    """misc/DataLoaderWeakPaired.lua: captions `labels/<split>` and their images walked in lockstep with DataLoader's wrap rule.
+    The CNN body is frozen and runs outside the library, so the images come as its output: feats {split: [N x I]} (vgg:
+    post-ReLU fc7, e.g. from nvqa_vgg16_fc7; inc: the pooled 2048-wide features), row i belonging to caption i."""
+
+    def __init__(self, labels, feats, ix_to_word=None, json_file=None):
+        super().__init__(labels=labels, ix_to_word=ix_to_word, json_file=json_file)
+        self.feats = {k: np.asarray(v, np.float32) for k, v in feats.items()}
+        for k, v in self.labels.items():
+            if k in self.feats and self.feats[k].shape[0] != v.shape[0]:
+                raise ValueError(f"split {k}: {v.shape[0]} captions but {self.feats[k].shape[0]} feature rows")
+
+    def get_batch(self, split, batch_size):
+        """getBatch (:58-103): (labels [batch_size x D], feats [batch_size x I], bounds), the rows of DataLoader.get_batch"""
+        it, max_index = self.iterators[split], self.labels[split].shape[0]
+        labels, bounds = super().get_batch(split, batch_size)
+        if it + batch_size - 1 > max_index and it < max_index:
+            num_left = max_index - it + 1
+            rows = np.concatenate([np.arange(it - 1, max_index), np.arange(batch_size - num_left)])
+        elif it + batch_size - 1 > max_index:
+            rows = np.arange(batch_size)
+        else:
+            rows = np.arange(it - 1, it - 1 + batch_size)
+        return labels, self.feats[split][rows], bounds
+
+
+# 004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua: the AE learning rate and the CNN feature width differ (:36-48, :62)
+WEAKPAIRED_DEFAULTS = {"vgg": {"learning_rate": 1e-5, "I": 4096}, "inc": {"learning_rate": 3e-5, "I": 2048}}
+
+
+class WeakPairedAETrainer:
+    """The weak-paired script's loop on an NVQA_ARCH_AE2_WP context: the null-sentence draw, ae_wp_step (lossFun), the log line
+    with both update counts, the learning-rate decay, Adam on [encoder | decoder] (the lookup table is frozen) and, once
+    fine-tuning has started (finetune_cnn_after >= 0 and iter >= it), Adam on the projection with its own state.
+    dims: binding.Dims with arch = ARCH_AE2_WP, T = seq_length, I = the CNN feature width, C = A = 0.
+    variant: 'vgg' or 'inc' (the default learning rate); learning_rate None: the variant's.
+
+    The null-sentence draw replaces Lua's `math.random() <= rand_val` (:289-295), whose stream cannot be reproduced: a
+    numpy generator seeded by (seed, iter), so the draw of an iteration does not depend on anything before it."""
+
+    def __init__(self, dims, device=0, variant="vgg", learning_rate=None, learning_rate_decay_start=-1,
+                 learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
+                 grad_clip=0.1, drop_prob=0.5, rand_val=0.5, finetune_cnn_after=-1, cnn_optim_alpha=0.8, cnn_optim_beta=0.999,
+                 cnn_learning_rate=1e-5, cnn_weight_decay=0.0, seed=123):
+        if dims.arch != binding.ARCH_AE2_WP:
+            raise ValueError("WeakPairedAETrainer needs dims.arch = ARCH_AE2_WP (5)")
+        if variant not in WEAKPAIRED_DEFAULTS:
+            raise ValueError("variant: 'vgg' or 'inc'")
+        self.dims = dims
+        self.ctx = binding.Context(dims, device)
+        self.learning_rate = WEAKPAIRED_DEFAULTS[variant]["learning_rate"] if learning_rate is None else learning_rate
+        self.decay_start, self.decay_every = learning_rate_decay_start, learning_rate_decay_every
+        self.alpha, self.beta, self.eps = optim_alpha, optim_beta, optim_epsilon
+        self.weight_decay, self.grad_clip = weight_decay, grad_clip
+        self.drop_prob, self.rand_val, self.seed = drop_prob, rand_val, seed
+        self.finetune_cnn_after = finetune_cnn_after
+        self.cnn_alpha, self.cnn_beta = cnn_optim_alpha, cnn_optim_beta
+        self.cnn_learning_rate, self.cnn_weight_decay = cnn_learning_rate, cnn_weight_decay
+        self.iter = 1
+        self._frozen_cnn_stats = None
+        self.ctx.init_params(seed, -0.08, 0.08)  # W_p uniform(-0.08, 0.08), b_p = 0 (build_cnn)
+
+    def init_from_text(self, path):
+        """-start_from_text: the text auto-encoder's [encoder | decoder | lookup], an AETrainer(ARCH_AE2).export_params table
+        of the same dims (the flat vector is AE2's byte for byte)."""
+        t = t7.load(path)
+        if t.get("layout") != t7.LAYOUT_MARK:
+            raise ValueError("text model table has no layout = 'nvqa' marker (AETrainer.export_params writes one)")
+        self.set_params(t["params"])
+
+    def set_params(self, x):
+        x = np.asarray(x, np.float32).ravel()
+        if x.size != self.ctx.param_count:
+            raise ValueError(f"params has {x.size} values, the model wants {self.ctx.param_count}")
+        self.ctx.set_params(x)
+
+    def null_sentence(self, it=None):
+        """True when iteration `it` feeds the null sentence to the encoder (probability rand_val)"""
+        it = self.iter if it is None else it
+        return bool(np.random.default_rng([self.seed, it]).random() <= self.rand_val)
+
+    def current_lr(self):
+        """(AE rate, cnn rate) after the decay (:443-451)"""
+        f = 1.0
+        if self.decay_start >= 0 and self.iter > self.decay_start:
+            f = 0.5 ** ((self.iter - self.decay_start) / self.decay_every)
+        return self.learning_rate * f, self.cnn_learning_rate * f
+
+    def finetuning(self):
+        return self.finetune_cnn_after >= 0 and self.iter >= self.finetune_cnn_after
+
+    def _cnn_stats_frozen(self):
+        """the log line's cnn figures while the projection is frozen: its gradient stays zero, so the count is that of the
+        entries with |x| = 0 (computed once; the projection does not change)"""
+        if self._frozen_cnn_stats is None:
+            w, b = self.ctx.ae_wp_get_projection()
+            self._frozen_cnn_stats = (float(np.sqrt((w.astype(np.float64) ** 2).sum())),
+                                      int((w == 0).sum() + (b == 0).sum()))
+        return self._frozen_cnn_stats
+
+    def train_step(self, tokens, feats):
+        """lossFun + log line + updates of one iteration; returns (loss, # updates, paramsNorm, # cnn updates, cnnParamsNorm,
+        the log line)."""
+        null = self.null_sentence()
+        dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.seed, self.iter)
+        loss = self.ctx.ae_wp_step(feats, tokens, enc_tokens=None if null else tokens, dropout=dr)
+        lr, cnn_lr = self.current_lr()
+        norm, count = self.ctx.adam_update(lr, self.alpha, self.beta, self.eps, self.weight_decay, self.grad_clip, stats=True)
+        if self.finetuning():
+            # wd then clamp, and only when cnn_weight_decay > 0, as the script's lossFun does (:318-322)
+            clamp = self.grad_clip if self.cnn_weight_decay > 0 else 0.0
+            cnn_norm, cnn_count = self.ctx.ae_wp_projection_adam(cnn_lr, self.cnn_alpha, self.cnn_beta, self.eps,
+                                                                 self.cnn_weight_decay, clamp, stats=True)
+            self._frozen_cnn_stats = None
+        else:
+            cnn_norm, cnn_count = self._cnn_stats_frozen()
+        line = "iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f | # cnn updates: %4d | cnnParamsNorm: %.4f" % (
+            self.iter, loss, count, norm, cnn_count, cnn_norm)
+        self.iter += 1
+        return loss, count, norm, cnn_count, cnn_norm, line
+
+    def train(self, loader, iters, log=print):
+        losses = []
+        for _ in range(iters):
+            labels, feats, _ = loader.get_batch("train", self.dims.B)
+            out = self.train_step(labels, feats)
+            losses.append(out[0])
+            if log:
+                log(out[-1])
+        return losses
+
+    def eval_split(self, loader, split="val", val_sentences_use=-1):
+        """eval_split (:199-260): AE2's stopping rule (n grows by batch_size; the loop ends on a wrap or once
+        n >= val_sentences_use).  The loss and the greedy decodes take enc_tokens = tokens (forward{feats, labels, labels})."""
+        loader.reset_iterator(split)
+        losses, preds, used, n = [], [], 0, 0
+        end = self.dims.V + 1
+        while True:
+            labels, feats, bounds = loader.get_batch(split, self.dims.B)
+            loss, samples = self.ctx.ae_wp_evaluate(feats, labels, enc_tokens=labels, samples=True)
+            losses.append(loss)
+            for p, a in zip(decode_sequence(loader.ix_to_word, samples, end), decode_sequence(loader.ix_to_word, labels, end)):
+                used += 1
+                preds.append({"seqNo": used, "prediction": p, "actual": a})
+            n += self.dims.B
+            if bounds["wrapped"] or n >= val_sentences_use:
+                break
+        return float(np.mean(losses)), preds
+
+    def export_for_vqa(self, path):
+        """What 003_train_vqa_arch2/003_train_ae_based_wp_{vgg,inc}.lua take from the checkpoint (:76-77, 150-154, 174, 193):
+        {encoder, lookup_table = W_lk [(V+1) x E], cnn_w = [W_p (E x I, row-major) | b_p], layout = 'nvqa'}; cnn_w is
+        arch2's cnn segment as it stands, read by VQATrainer.init_from_autoencoder(..., with_cnn=True)."""
+        d = self.dims
+        x = self.ctx.get_params()
+        seg = self.ctx.segments()
+        w, b = self.ctx.ae_wp_get_projection()
+        t7.save(path, {"encoder": x[:seg[0]].copy(), "lookup_table": np.ascontiguousarray(x[seg[0] + seg[1]:].reshape(d.V + 1, d.E)),
+                       "cnn_w": np.concatenate([w.ravel(), b]), "layout": t7.LAYOUT_MARK})

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_PKG, "libnvqa.so")
 COMM_ID_BYTES = 128
 
 
-ARCH1, ARCH2, ARCH_AE1, ARCH_AE2 = 1, 2, 3, 4
+ARCH1, ARCH2, ARCH_AE1, ARCH_AE2, ARCH_AE2_WP = 1, 2, 3, 4, 5
 
 
 class NvqaError(RuntimeError):
@@ -81,6 +81,12 @@ SYMBOLS = {
     "nvqa_ae_step_images": (ctypes.c_int, [_vp, _f32p, _i32p, ctypes.POINTER(Dropout), _f32p, _f32p]),
     "nvqa_ae_evaluate_images": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _f32p, _i32p]),
     "nvqa_adam_update": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
+    "nvqa_ae_wp_step": (ctypes.c_int, [_vp, _f32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
+    "nvqa_ae_wp_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _i32p, _f32p, _i32p]),
+    "nvqa_ae_wp_set_projection": (ctypes.c_int, [_vp, _f32p, _f32p]),
+    "nvqa_ae_wp_get_projection": (ctypes.c_int, [_vp, _f32p, _f32p]),
+    "nvqa_ae_wp_get_projection_grads": (ctypes.c_int, [_vp, _f32p, _f32p]),
+    "nvqa_ae_wp_projection_adam": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_profile_reset": (ctypes.c_int, [_vp]),
     "nvqa_profile_count": (ctypes.c_int, [_vp]),
@@ -290,6 +296,57 @@ class Context:
         """clamp -> + wd x -> adam in one pass; stats=True returns (paramsNorm, # updates) of the log line."""
         out = np.zeros(2, np.float32) if stats else None
         self._check(self.lib.nvqa_adam_update(self._h, lr, beta1, beta2, eps, wd, clamp, _f32(out)))
+        return (float(out[0]), int(out[1])) if stats else None
+
+    # ---- weak-paired auto-encoder (arch ARCH_AE2_WP) --------------------------------
+    def ae_wp_step(self, feats, tokens, enc_tokens=None, dropout=None, want_loss=True):
+        """nvqa_ae_wp_step: feats [B x I] (the frozen CNN body's output; the library L2-normalises its copy), tokens [B x D]
+        for the decoder and criterion, enc_tokens [B x D] for the encoder (None = the null sentence)."""
+        d = self.dims
+        f = np.ascontiguousarray(feats, np.float32).reshape(d.B, d.I)
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(d.B, d.T)
+        et = None if enc_tokens is None else np.ascontiguousarray(enc_tokens, np.int32).reshape(d.B, d.T)
+        loss = ctypes.c_float(0)
+        dr = ctypes.byref(dropout) if dropout is not None else None
+        self._check(self.lib.nvqa_ae_wp_step(self._h, _f32(f), _i32(et), _i32(tok), dr, ctypes.byref(loss) if want_loss else None))
+        return float(loss.value) if want_loss else None
+
+    def ae_wp_evaluate(self, feats, tokens, enc_tokens=None, samples=False):
+        """nvqa_ae_wp_evaluate of n = len(tokens) rows: (evaluate-mode loss, greedy samples [n x D] or None)."""
+        d = self.dims
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(-1, d.T)
+        n = tok.shape[0]
+        f = np.ascontiguousarray(feats, np.float32).reshape(n, d.I)
+        et = None if enc_tokens is None else np.ascontiguousarray(enc_tokens, np.int32).reshape(n, d.T)
+        out = np.empty((n, d.T), np.int32) if samples else None
+        loss = ctypes.c_float(0)
+        self._check(self.lib.nvqa_ae_wp_evaluate(self._h, n, _f32(f), _i32(et), _i32(tok), ctypes.byref(loss), _i32(out)))
+        return float(loss.value), out
+
+    def ae_wp_set_projection(self, w, b):
+        d = self.dims
+        w = np.ascontiguousarray(w, np.float32).reshape(d.E, d.I)
+        b = np.ascontiguousarray(b, np.float32).reshape(d.E)
+        self._check(self.lib.nvqa_ae_wp_set_projection(self._h, _f32(w), _f32(b)))
+
+    def ae_wp_get_projection(self):
+        """(W_p [E x I], b_p [E])"""
+        d = self.dims
+        w, b = np.empty((d.E, d.I), np.float32), np.empty(d.E, np.float32)
+        self._check(self.lib.nvqa_ae_wp_get_projection(self._h, _f32(w), _f32(b)))
+        return w, b
+
+    def ae_wp_get_projection_grads(self):
+        """(dW_p [E x I], db_p [E]) of the last step"""
+        d = self.dims
+        w, b = np.empty((d.E, d.I), np.float32), np.empty(d.E, np.float32)
+        self._check(self.lib.nvqa_ae_wp_get_projection_grads(self._h, _f32(w), _f32(b)))
+        return w, b
+
+    def ae_wp_projection_adam(self, lr, beta1=0.8, beta2=0.999, eps=1e-8, wd=0.0, clamp=0.0, stats=False):
+        """+ wd x -> clamp -> adam on [W_p | b_p]; stats=True returns (||W_p||, # cnn updates) of the log line."""
+        out = np.zeros(2, np.float32) if stats else None
+        self._check(self.lib.nvqa_ae_wp_projection_adam(self._h, lr, beta1, beta2, eps, wd, clamp, _f32(out)))
         return (float(out[0]), int(out[1])) if stats else None
 
     def set_fusion(self, mode):

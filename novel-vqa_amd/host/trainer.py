@@ -156,7 +156,7 @@ class VQATrainer:
         self.set_params(t7.load_checkpoint(path, self.dims.arch, self.ctx.segments(), encoder_perm=encoder_perm))
 
     # -- initialisation from an auto-encoder checkpoint (the *_ae_based* scripts) -------------------------------------------
-    def init_from_autoencoder(self, path, encoder_perm=None, with_multimodal=False):
+    def init_from_autoencoder(self, path, encoder_perm=None, with_multimodal=False, with_cnn=False):
         """What the AE-based trainers do in place of `*_w:uniform(-0.08, 0.08)`.
 
         arch1 (002_train_vqa_arch1/003_train_ae_based.lua:65,175-186; _inc / _ef alike): `path` is the table written by
@@ -170,12 +170,17 @@ class VQATrainer:
         modelT.ae.lookup_table out of the AE checkpoint's nn modules; this reader takes tensors only (nothing in a file
         is executed), so `path` is the table lua/convert_ae_arch2.lua writes from that checkpoint: encoder = the LSTM's
         flat parameters, lookup_table = [(V+1) x E].  cnn_w and multimodal_w <- uniform(-0.08, 0.08) (:189,194).
+        with_cnn (003_train_ae_based_wp_{vgg,inc}.lua:76-77,150-154,174,193, arch2 only): cnn_w is copied from the table's
+        'cnn_w' as well -- the weak-paired auto-encoder's projection [W_p (E x I) | b_p (E)], which
+        WeakPairedAETrainer.export_for_vqa writes and which is arch2's cnn segment as it stands.
 
         The uniform segments come from the library's counter-based stream (nvqa_init_params with this trainer's seed), so
         every rank of a data-parallel job builds the same vector.  As with load_checkpoint, the order of the LSTM tensors
         inside `encoder` is nngraph's: a table without layout = 'nvqa' needs encoder_perm (t7.encoder_permutation).
         PARITY UNPINNED: the reference ships no AE checkpoint."""
         d = self.dims
+        if with_cnn and d.arch != 2:
+            raise ValueError("with_cnn=True is the arch2 weak-paired path (003_train_ae_based_wp_*.lua)")
         t = t7.load(path)
         if t.get("layout") != t7.LAYOUT_MARK and encoder_perm is None:
             raise ValueError("auto-encoder table has no layout = 'nvqa' marker: the order of the LSTM tensors inside 'encoder' is "
@@ -216,6 +221,14 @@ class VQATrainer:
                 raise ValueError(f"encoder has {enc.size} values, the model's LSTM wants {n_lstm}")
             x[seg[0]:seg[0] + n_lstm] = enc
             x[seg[0] + n_lstm:seg[0] + seg[1]] = lk.ravel()
+            if with_cnn:
+                if "cnn_w" not in t:
+                    raise ValueError("with_cnn=True: the table has no cnn_w (a weak-paired auto-encoder export carries one)")
+                cw = np.asarray(t["cnn_w"], np.float32).ravel()
+                if cw.size != seg[0]:
+                    raise ValueError(f"cnn_w has {cw.size} values, the model's W_p [E x I] + b_p [E] want {seg[0]} "
+                                     f"(E = {d.E}, I = {d.I})")
+                x[:seg[0]] = cw
         self.ctx.set_params(x)
 
     def close(self):

@@ -64,6 +64,15 @@ int nvqa_ae_evaluate_images(nvqa_ctx *ctx, int32_t n, const float *images, const
                             int32_t *samples_out);
 int nvqa_adam_update(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                      float stats_out[2]);
+int nvqa_ae_wp_step(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                    const nvqa_dropout *dropout, float *loss_out);
+int nvqa_ae_wp_evaluate(nvqa_ctx *ctx, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                        float *loss_out, int32_t *samples_out);
+int nvqa_ae_wp_set_projection(nvqa_ctx *ctx, const float *w, const float *b);
+int nvqa_ae_wp_get_projection(nvqa_ctx *ctx, float *w_out, float *b_out);
+int nvqa_ae_wp_get_projection_grads(nvqa_ctx *ctx, float *w_out, float *b_out);
+int nvqa_ae_wp_projection_adam(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
+                               float stats_out[2]);
 int nvqa_profile_enable(nvqa_ctx *ctx, int enable);
 int nvqa_profile_reset(nvqa_ctx *ctx);
 int nvqa_profile_count(const nvqa_ctx *ctx);

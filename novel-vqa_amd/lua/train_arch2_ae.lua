@@ -1,8 +1,9 @@
 --[[
-train_arch2_ae.lua -- 003_train_vqa_arch2/003_train_ae_based.lua (and its _ef / _wp_vgg / _wp_inc siblings, which differ in
--nhimage and the input files) with the hot path on libnvqa.  Everything is train_arch2.lua except the initialisation
-(:74-75,150-152,186-194): the encoder LSTM and the lookup table come from the auto-encoder, cnn_w and multimodal_w are
-uniform(-0.08, 0.08).  -input_ae_model is the tensor table convert_ae_arch2.lua writes from the AE checkpoint (the reference
+train_arch2_ae.lua -- 003_train_vqa_arch2/003_train_ae_based.lua (and its _ef sibling, which differs in -nhimage and the
+input files) with the hot path on libnvqa.  Everything is train_arch2.lua except the initialisation (:74-75,150-152,186-194):
+the encoder LSTM and the lookup table come from the auto-encoder, cnn_w and multimodal_w are uniform(-0.08, 0.08).  The
+_wp_vgg / _wp_inc siblings also take cnn_w from the weak-paired auto-encoder (the CNN's final Linear, modelT.cnn:get(40) /
+:get(32), :76-77,150-154,174,193): -ae_cnn 1, with the table train_arch2_wp_ae.lua writes.  -input_ae_model is the tensor table convert_ae_arch2.lua writes from the AE checkpoint (the reference
 clones the nn modules directly; see that file).  VQATrainer.init_from_autoencoder is the executed twin.  Not executable in
 the build image (no LuaJIT).
 ]]--
@@ -17,6 +18,7 @@ cmd:option('-input_img_h5','data_img.h5','path to the h5file containing the imag
 cmd:option('-input_ques_h5','data_prepro.h5','path to the h5file containing the preprocessed dataset')
 cmd:option('-input_json','data_prepro.json','path to the json file containing additional info and vocab')
 cmd:option('-input_ae_model', '', 'tensor table of the auto-encoder (convert_ae_arch2.lua)')
+cmd:option('-ae_cnn', 0, '1 = cnn_w from the table\'s cnn_w too (the weak-paired auto-encoder, 003_train_ae_based_wp_*.lua)')
 cmd:option('-encoder_perm', '', 'torch file with the LongTensor that maps the AE encoder\'s tensor order onto libnvqa\'s (optional)')
 cmd:option('-drop_prob_ae', 0.5, 'dropout value')
 cmd:option('-learning_rate',1e-4,'learning rate for rmsprop')
@@ -80,6 +82,11 @@ do                                                                              
   if opt.encoder_perm ~= '' then enc = enc:index(1, torch.load(opt.encoder_perm):long()) end
   x[{{a + 1, a + n_lstm}}]:copy(enc)                                               -- encoder segment: LSTM parameters, then the lookup table
   x[{{a + n_lstm + 1, a + b}}]:copy(lk:contiguous():view(-1))
+  if opt.ae_cnn == 1 then                                                           -- modelT.cnn's final Linear (_wp_*.lua:150-154)
+    assert(ae.cnn_w ~= nil, '-ae_cnn 1: the table has no cnn_w (train_arch2_wp_ae.lua writes one)')
+    assert(ae.cnn_w:nElement() == a, 'cnn_w does not match -nhimage / -input_encoding_size ([W_p (E x I) | b_p (E)])')
+    x[{{1, a}}]:copy(ae.cnn_w:float():contiguous():view(-1))
+  end
   nvqa.check(nvqa.lib.nvqa_set_params(ctx, nvqa.fptr(x)))
 end
 nvqa.check(nvqa.lib.nvqa_set_precision(ctx, opt.bf16))

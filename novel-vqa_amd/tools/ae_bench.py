@@ -6,8 +6,13 @@ sentences/s (median over timed blocks after warm-up), the per-group profile of a
 step's fraction of the f32 MFMA roofline (FLOPs computed from the shape, 3 x forward).
 --arch 2: the image-first-token auto-encoder (001_train_arch2_text_autoencoder.lua, NVQA_ARCH_AE2) at the same shape,
 with the text script's zero image rows (nvqa_ae_step on an AE2 context) and its learning rate 5e-5.
+--arch 5: the weak-paired auto-encoder (004_train_arch2_weakpaired_autoencoder_vgg.lua, NVQA_ARCH_AE2_WP): nvqa_ae_wp_step on
+random post-ReLU-like features [B x I] (--I, default 4096), the encoder fed the null sentence in a share --null-share of the
+steps (a fixed draw per step) and the captions otherwise, then nvqa_adam_update on [encoder | decoder] (the script's default
+-finetune_cnn_after -1 never updates the projection).  The reference shape is --B 20 --null-share 0.5.
 
-    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2] [--blocks 5 --steps 10 --warmup 5] [--out FILE]
+    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5] [--I 4096 --null-share 0.5] [--blocks 5 --steps 10 --warmup 5]
+                                           [--out FILE]
 """
 import argparse
 import json
@@ -25,22 +30,28 @@ import __graft_entry__ as ge  # noqa: E402
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md "Peak FP32 (matrix)"
 
 
-def step_flops(B, T, V, E, R, L, arch=1):
-    """3 x forward of a batch whose tmax is T: T (arch 2: T + 2) encoder + T+1 decoder LSTM steps, T+1 projections"""
+def step_flops(B, T, V, E, R, L, arch=1, te=None, I=0):
+    """3 x forward of a batch whose tmax is T: T (arch 2: T + 2) encoder + T+1 decoder LSTM steps, T+1 projections.
+    arch 5: te encoder steps (2 + the encoder tokens' tmax), T+1 decoder steps, and the feature projection (forward and
+    dW_p: 2 x 2 B E I; no d(features))"""
     lstm = sum(2 * B * 4 * R * ((E if l == 0 else R) + R) for l in range(L))
+    if arch == 5:
+        return 3 * ((te + T + 1) * lstm + (T + 1) * 2.0 * B * R * (V + 1)) + 4.0 * B * E * I
     fwd = (2 * T + 1 + (2 if arch == 2 else 0)) * lstm + (T + 1) * 2.0 * B * R * (V + 1)
     return 3 * fwd
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--arch", type=int, default=1, choices=(1, 2, 5))
     ap.add_argument("--B", type=int, default=1000)
     ap.add_argument("--D", type=int, default=16)
     ap.add_argument("--V", type=int, default=14773)
     ap.add_argument("--E", type=int, default=512)
     ap.add_argument("--R", type=int, default=512)
     ap.add_argument("--L", type=int, default=1)
+    ap.add_argument("--I", type=int, default=4096)
+    ap.add_argument("--null-share", type=float, default=0.5)
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
@@ -48,8 +59,10 @@ def main():
     a = ap.parse_args()
     pkg = ge.load_package()
     b = pkg.binding
-    dims = b.Dims(b.ARCH_AE1 if a.arch == 1 else b.ARCH_AE2, a.B, a.D, a.V, a.E, a.R, a.L, 0, 0, 0)
-    lr = 1e-5 if a.arch == 1 else 5e-5
+    arch = {1: b.ARCH_AE1, 2: b.ARCH_AE2, 5: b.ARCH_AE2_WP}[a.arch]
+    I = a.I if a.arch == 5 else 0
+    dims = b.Dims(arch, a.B, a.D, a.V, a.E, a.R, a.L, I, 0, 0)
+    lr = {1: 1e-5, 2: 5e-5, 5: 1e-5}[a.arch]
     ctx = b.Context(dims, 0)
     ctx.init_params(123, -0.08, 0.08)
     rng = np.random.default_rng(0)
@@ -60,11 +73,25 @@ def main():
         for i, n in enumerate(lens):
             tok[i, :n] = rng.integers(1, a.V + 1, n)
         batches.append(tok)
+    feats = []
+    if a.arch == 5:
+        for _ in batches:
+            f = rng.uniform(0, 1, (a.B, I)).astype(np.float32)
+            f[rng.uniform(0, 1, (a.B, I)) < 0.5] = 0.0
+            feats.append(f)
+    # the null-sentence draw of step k (a fixed sequence, so that every run times the same mix)
+    null = np.random.default_rng(1).random(4096) < a.null_share
     it = [0]
 
     def one_step():
         it[0] += 1
-        ctx.ae_step(batches[it[0] % len(batches)], b.Dropout(1, 0.5, 123, it[0]), want_loss=False)
+        k = it[0] % len(batches)
+        dr = b.Dropout(1, 0.5, 123, it[0])
+        if a.arch == 5:
+            ctx.ae_wp_step(feats[k], batches[k], enc_tokens=None if null[it[0] % null.size] else batches[k], dropout=dr,
+                           want_loss=False)
+        else:
+            ctx.ae_step(batches[k], dr, want_loss=False)
         ctx.adam_update(lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
 
     for _ in range(a.warmup):
@@ -78,7 +105,11 @@ def main():
         ctx.sync()
         block_ms.append((time.perf_counter() - t0) * 1e3 / a.steps)
     ms = float(np.median(block_ms))
-    loss = ctx.ae_step(batches[0], b.Dropout(1, 0.5, 123, 0))
+    timed = range(a.warmup + 1, a.warmup + a.blocks * a.steps + 1)  # the iteration numbers of the timed steps
+    if a.arch == 5:
+        loss = ctx.ae_wp_step(feats[0], batches[0], enc_tokens=batches[0], dropout=b.Dropout(1, 0.5, 123, 0))
+    else:
+        loss = ctx.ae_step(batches[0], b.Dropout(1, 0.5, 123, 0))
     # profiled pass (events around every launch group: slower, reported per group only)
     ctx.profile_enable(True)
     for _ in range(3):
@@ -96,13 +127,20 @@ def main():
     ctx.profile_enable(False)
     ctx.close()
     tmaxes = [int(np.nonzero(t.any(0))[0][-1]) + 1 for t in batches]
-    fl = float(np.mean([step_flops(a.B, T, a.V, a.E, a.R, a.L, a.arch) for T in tmaxes]))
-    line = {"workload": "ae_arch%d_text" % a.arch, "B": a.B, "D": a.D, "V": a.V, "E": a.E, "R": a.R, "L": a.L,
-            "ms_per_step": round(ms, 4), "block_ms": [round(x, 4) for x in block_ms],
+    if a.arch == 5:  # the timed steps' own batches and encoder lengths
+        fl = float(np.mean([step_flops(a.B, tmaxes[i % len(batches)], a.V, a.E, a.R, a.L, 5,
+                                       te=2 if null[i % null.size] else tmaxes[i % len(batches)] + 2, I=I) for i in timed]))
+    else:
+        fl = float(np.mean([step_flops(a.B, T, a.V, a.E, a.R, a.L, a.arch) for T in tmaxes]))
+    line = {"workload": "ae_arch%d_%s" % (a.arch, "weakpaired" if a.arch == 5 else "text"), "B": a.B, "D": a.D, "V": a.V,
+            "E": a.E, "R": a.R, "L": a.L, "ms_per_step": round(ms, 4), "block_ms": [round(x, 4) for x in block_ms],
+            "block_spread_pct": round(100.0 * (max(block_ms) - min(block_ms)) / ms, 2),
             "sentences_per_s": round(a.B / (ms * 1e-3), 1), "loss": loss,
             "tflop_per_step": round(fl / 1e12, 4), "achieved_tflops": round(fl / (ms * 1e-3) / 1e12, 2),
             "fraction_of_f32_mfma_peak": round(fl / (ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
             "profile": prof}
+    if a.arch == 5:
+        line.update(I=I, null_share=a.null_share, null_steps_timed=int(sum(null[i % null.size] for i in timed)))
     s = json.dumps(line)
     print(s)
     if a.out:
