@@ -19,6 +19,7 @@
 #include "gemm_f32.h"
 #include "kernels.h"
 #include "wgrad_bf16.h"
+#include "wgrad_split.h"
 #include "nvqa_ctx.h"
 #include "persist_host.h"
 
@@ -320,6 +321,7 @@ static int create_impl(nvqa_ctx *c)
     c->slab_floats = 8 * 4 * R * std::max<size_t>(std::max(R, E), 128);
     NVQA_TRY(dalloc(&c->slabs, c->slab_floats));
     NVQA_TRY(dalloc(&c->chain_slabs, (size_t)L * 2 * NVQA_BWD_ZMAX * ((B + 63) / 64 * 64) * ((R + 63) / 64 * 64)));
+    c->wgrad_split_on = env_on("NVQA_WGRAD_SPLIT"); // 0: the f32 weight gradients as the exact f32 MFMA chain (wgrad_split.h)
     c->fold_i2h = env_on("NVQA_FOLD_I2H"); // 0: layer 0's input projection as a separate time-batched GEMM (A/B runs of the per-level path)
     {   // persistent forward LSTM (lstm_persist.h) where the shape is eligible; NVQA_PERSIST=0: one launch per wavefront level
         c->persist_on = env_on("NVQA_PERSIST");
@@ -759,12 +761,46 @@ static int wgrad_bf16(nvqa_ctx *c, const float *A, const unsigned short *A16, in
     return 0;
 }
 
+// f32 mode: each f32 product as six bf16 MFMA terms (wgrad_split.h); the K stages that hold active rows are dealt
+// round-robin to the ks slices inside the kernel, so ks is all the host chooses
+static int wgrad_split(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb, int M, int N, int K,
+                       float *dW, float *slabs, hipStream_t st)
+{
+    const int tiles = ((M + NVQA_WS_BM - 1) / NVQA_WS_BM) * ((N + NVQA_WS_BN - 1) / NVQA_WS_BN);
+    int ks = 1;
+    while (ks < 16 && tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2; // 2048 x 512: 8 slices, 2048 x 200: 16
+    if ((size_t)ks * M * N > c->slab_floats) ks = std::max<int>(1, (int)(c->slab_floats / ((size_t)M * N)));
+    {
+        // bytes: the compulsory traffic -- each operand row once (the filled share of the K rows where the kernel can skip
+        // padding stages, seg_rows % 32 == 0; all K rows otherwise) and the slabs -- not the re-reads of a dG row tile per
+        // column tile and of a column tile per row tile, which L2 serves in part (profiles/wgrad_split_ab.json: 249 MB fetched)
+        const double kfrac = c->d.B % NVQA_WS_BK == 0 ? c->batch_len_frac : 1.0;
+        ProfScope ps(c, PF_GEMM_WGRAD, 2.0 * M * N * K, ((double)K * (M + N) * kfrac + (double)ks * M * N) * 4, st);
+        WgradSplitArgs g{A, Bm, ks == 1 ? dW : slabs, ks == 1 ? 0 : (size_t)M * N, c->nrows, c->d.B, lda, ldb, N, M, N, K};
+        const dim3 grid((M + NVQA_WS_BM - 1) / NVQA_WS_BM, (N + NVQA_WS_BN - 1) / NVQA_WS_BN, ks);
+        static bool attr = false;
+        if (!attr) {
+            NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_split, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS_LDS_BYTES));
+            attr = true;
+        }
+        hipLaunchKernelGGL(k_wgrad_split, grid, dim3(256), NVQA_WS_LDS_BYTES, st, g);
+        NVQA_HIP(hipGetLastError());
+    }
+    if (ks == 1) return 0;
+    ProfScope ps(c, PF_REDUCE, 0, (double)(ks + 1) * M * N * 4, st);
+    const size_t n4 = (size_t)M * N / 4;
+    hipLaunchKernelGGL(k_reduce_slabs, dim3((n4 + 255) / 256), dim3(256), 0, st, slabs, ks, n4, reinterpret_cast<float4 *>(dW));
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
+
 // dW[M x N] = A^T B with A stored [K][M], B stored [K][N]; K = TS*B is long, the output
 // small: split K over blockIdx.z into slabs, then sum the slabs in order (deterministic).
 static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb, int M, int N, int K,
                  float *dW, float *slabs, hipStream_t st, const unsigned short *A16 = nullptr, const unsigned short *B16 = nullptr)
 {
     if (c->bf16 && M % 4 == 0 && N % 4 == 0) return wgrad_bf16(c, A, A16, lda, Bm, B16, ldb, M, N, K, dW, slabs, st);
+    if (!c->bf16 && c->wgrad_split_on && wgrad_split_takes(M, N, K, lda, ldb, c->d.B)) return wgrad_split(c, A, lda, Bm, ldb, M, N, K, dW, slabs, st);
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
     int ks = 1;
     while (ks < 16 && tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2; // tools/kbench11: 2048 x 200 x 13312: 16 slices 115 us, 8 slices 129 us

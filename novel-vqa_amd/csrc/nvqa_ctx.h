@@ -177,6 +177,7 @@ struct nvqa_ctx {
     float *colpart = nullptr, *slabs = nullptr;
     float *chain_slabs = nullptr; // [L][2][NVQA_BWD_Z][B][R] split-K partials of the BPTT level products
     bool bf16 = false;            // nvqa_set_precision: GEMM operands rounded to bf16, bf16 MFMA, f32 accumulate
+    bool wgrad_split_on = true;   // f32 mode: weight gradients as six bf16 MFMA terms per product (wgrad_split.h); NVQA_WGRAD_SPLIT=0: the f32 MFMA chain
     bool fold_i2h = true;         // layer-0 input projection as a first K segment of the level kernel; NVQA_FOLD_I2H=0: separate time-batched GEMM
     bool batch_uniform = false;   // current batch: all lengths equal (known on the host)
     float batch_len_frac = 1.f;   // current batch: filled share of its B x T (row, step) slots (host batches: exact; dataset route: the dataset's mean)
