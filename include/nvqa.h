@@ -49,10 +49,14 @@ extern "C" {
 #define NVQA_ARCH_AE2_WP 5 /* 001_train_autoencoder/004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua: the AE2 model fed
                             * L2Normalize(features) W_p^T + b_p as its image row, with a frozen lookup table
                             * (misc/AutoEncoderNull.lua); dims B, T = seq_length, V, E, R, L, I = feature width; C = A = 0 */
+#define NVQA_ARCH_AE1_WP 6 /* 001_train_autoencoder/004_train_arch1_weakpaired_autoencoder_{vgg,inc}.lua: the AE1 model whose
+                            * decoder starts from the encoder's final state plus a multimodal correction of that state and the
+                            * image (misc/AutoEncoder_vqa_arch.lua); dims B, T = seq_length, V, E, R, L = 1, I = feature width,
+                            * C = 2R, A = 0 */
 
 /* Model dimensions (SURVEY.md symbol table). */
 typedef struct nvqa_dims {
-    int32_t arch; /* NVQA_ARCH1 | NVQA_ARCH2 | NVQA_ARCH_AE1 | NVQA_ARCH_AE2 | NVQA_ARCH_AE2_WP */
+    int32_t arch; /* NVQA_ARCH1 | NVQA_ARCH2 | NVQA_ARCH_AE1 | NVQA_ARCH_AE2 | NVQA_ARCH_AE2_WP | NVQA_ARCH_AE1_WP */
     int32_t B;    /* minibatch (QA pairs) per device             -batch_size          */
     int32_t T;    /* question buffer length (columns of ques_*)  buffer_size_q        */
     int32_t V;    /* question vocabulary size                    vocabulary_size_q    */
@@ -288,6 +292,31 @@ int nvqa_ae_wp_get_projection_grads(nvqa_ctx *ctx, float *w_out, float *b_out);
  * of x before the update. */
 int nvqa_ae_wp_projection_adam(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                                float stats_out[2]);
+/* ---- arch1 weak-paired auto-encoder (NVQA_ARCH_AE1_WP contexts) ---- */
+/* 004_train_arch1_weakpaired_autoencoder_{vgg,inc}.lua with misc/AutoEncoder_vqa_arch.lua.  The flat vector is
+ * [encoder | decoder | multimodal] with multimodal = W_q [2R x 2R], b_q [2R], W_v [2R x I], b_v [2R] (netdef.AxB(2R, I, 2R));
+ * the lookup table LookupTable -> Tanh is frozen, evaluates without its Dropout even in training, and lives outside the vector
+ * (the two calls at the end).  feats [B x I] are the frozen CNN body's output; the library L2-normalises its copy (the
+ * caller's rows only) into f^.  With j = [c_T | h_T] the encoder's final state (enc_tokens, 0 -> 1, tmax(enc_tokens) steps) or
+ * the caller's enc_state [B x 2R] (encoder_skip_flag = 1: the encoder does not run and its gradient segment is zero):
+ *   m = D_Z (tanh(W_q (D_Q j) + b_q) * tanh(W_v (D_V f^) + b_v)),  decoder state (c, h) = (c_T + m[:, :R], h_T + m[:, R:]),
+ * then AE1's decoder, projection and criterion over tokens.  Every other step / evaluate entry point, nvqa_comm_init,
+ * nvqa_set_precision(ctx, 1) and nvqa_rmsprop_update return an error on such a context; the calls below return an error on
+ * every other context.  nvqa_adam_update runs over the whole vector.
+ * nvqa_ae1_wp_step: exactly one of enc_tokens [B x D] and enc_state [B x 2R] is non-NULL; dfeats_out [B x I] (may be NULL) =
+ * d(loss)/d(f^), the module's gradInput for the features. */
+int nvqa_ae1_wp_step(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const float *enc_state,
+                     const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out);
+/* Evaluate-mode loss and (samples_out [n x D] not NULL) greedy decoding of n <= B rows, the encoder run on enc_tokens [n x D]
+ * (eval_split feeds enc_tokens = tokens with the flag at 0); feats [n x I], tokens [n x D]. */
+int nvqa_ae1_wp_evaluate(nvqa_ctx *ctx, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                         float *loss_out, int32_t *samples_out);
+/* Evaluate-mode encoder only: state_out [n x 2R] = [c_T | h_T] of n <= B rows (the sentence vectors whose corpus mean the skip
+ * mode is fed). */
+int nvqa_ae1_wp_encode(nvqa_ctx *ctx, int32_t n, const int32_t *enc_tokens, float *state_out);
+/* The frozen lookup table W_lk [(V+1) x E] (row V = START); no update ever touches it. */
+int nvqa_ae1_wp_set_lookup(nvqa_ctx *ctx, const float *w);
+int nvqa_ae1_wp_get_lookup(nvqa_ctx *ctx, float *w_out);
 /* Valid on every context.  One pass over the flat vector: g = clamp(g, -clamp, clamp) (clamp > 0), g += wd * x, then
  * adam() of misc/optim_updates.lua:78-111 (step counter held by the context, reset by nvqa_init_params).
  * stats_out (may be NULL; synchronises) = {||x||_2, count(|lr g| >= 0.01 |x|)} of x before the update, g after clamp + wd

@@ -29,7 +29,7 @@ typedef struct nvqa_layout {
     size_t w_q, b_q, w_v, b_v, w_o, b_o; /* multimodal */
     /* arch2 */
     size_t w_p, b_p; /* cnn projection W_p [E x I], b_p [E] */
-    size_t w_lk;     /* lookup table [(V+1) x E] (arch2, ae1, ae2, ae2_wp) */
+    size_t w_lk;     /* lookup table [(V+1) x E] (arch2, ae1, ae2, ae2_wp; ae1_wp: outside the vector, 0 here) */
     /* ae1 / ae2 (text auto-encoders): the encoder uses w_i2h.. above, the decoder these */
     size_t d_w_i2h[NVQA_MAX_LAYERS], d_b_i2h[NVQA_MAX_LAYERS];
     size_t d_w_h2h[NVQA_MAX_LAYERS], d_b_h2h[NVQA_MAX_LAYERS];
@@ -114,6 +114,30 @@ static inline int nvqa_layout_init_fusion(const nvqa_dims *d, int fusion, nvqa_l
         lo->w_lk = off; off += (V + 1) * E;
         lo->seg[2] = off - lo->seg[0] - lo->seg[1];
         lo->w_e = lo->b_e = lo->w_q = lo->b_q = lo->w_v = lo->b_v = lo->w_o = lo->b_o = lo->w_p = lo->b_p = 0;
+    } else if (d->arch == NVQA_ARCH_AE1_WP) {
+        /* [encoder | decoder | multimodal]: AutoEncoder_vqa_arch.lua:103-127 (one layer; the frozen lookup table is left out of
+         * parameters() and lives outside the vector); multimodal = netdef.AxB(2R, I, 2R): W_q [2R x 2R], b_q, W_v [2R x I], b_v */
+        const size_t C2 = 2 * R;
+        if (d->L != 1) return -1;
+        lo->in_dim[0] = (int32_t)E;
+        lo->w_i2h[0] = off; off += 4 * R * E;
+        lo->b_i2h[0] = off; off += 4 * R;
+        lo->w_h2h[0] = off; off += 4 * R * R;
+        lo->b_h2h[0] = off; off += 4 * R;
+        lo->seg[0] = off;
+        lo->d_w_i2h[0] = off; off += 4 * R * E;
+        lo->d_b_i2h[0] = off; off += 4 * R;
+        lo->d_w_h2h[0] = off; off += 4 * R * R;
+        lo->d_b_h2h[0] = off; off += 4 * R;
+        lo->w_proj = off; off += (V + 1) * R;
+        lo->b_proj = off; off += V + 1;
+        lo->seg[1] = off - lo->seg[0];
+        lo->w_q = off; off += C2 * C2;
+        lo->b_q = off; off += C2;
+        lo->w_v = off; off += C2 * I;
+        lo->b_v = off; off += C2;
+        lo->seg[2] = off - lo->seg[0] - lo->seg[1];
+        lo->w_e = lo->b_e = lo->w_o = lo->b_o = lo->w_p = lo->b_p = lo->w_lk = 0;
     } else {
         return -1;
     }

@@ -28,6 +28,12 @@
 // step 0 flows into the encoder's last step through the ordinary recurrent product, with the encoder's W_h2h replaced by
 // the decoder's at the boundary.  Each layer runs its whole chain before the layer above it starts (the decoder of layer l
 // needs the encoder of layer l only); the backward pass runs the layers top-down.
+// The arch1 weak-paired auto-encoder (NVQA_ARCH_AE1_WP, misc/AutoEncoder_vqa_arch.lua with
+// 004_train_arch1_weakpaired_autoencoder_*.lua; one layer) is AE1's chain with two token streams, a frozen lookup that runs
+// without its Dropout, and the bridge of ae_bridge.h between the two LSTMs: the state arrays hold one slot more, decoder step s
+// reads slot te + 1 + s and writes te + 2 + s, slot te + 1 = the bridge's output.  The backward pass stops the recurrent
+// product behind decoder step 0, runs the bridge's backward there, and starts the encoder's last step from its dc_T / dh_T.
+// With the encoder skipped (encoder_skip_flag = 1) te = 0, j is the caller's and the encoder's gradient segment is zeroed.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,6 +42,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "ae_bridge.h"
 #include "gemm_f32.h"
 #include "nvqa_ctx.h"
 #include "prof.h"
@@ -86,6 +93,15 @@ struct AeState {
     int64_t wp_t = 0;           // AE2_WP: the projection's Adam step counter
     hipEvent_t staged = nullptr; // AE2_WP: the last batch's host-to-device copies are done (the staging buffers are free)
     bool staged_rec = false;
+    // NVQA_ARCH_AE1_WP
+    bool bridge = false;        // the bridge of ae_bridge.h sits between the LSTMs; decoder state slots are shifted by one
+    bool feats = false;         // wp || bridge: features, encoder tokens of their own, frozen lookup
+    bool skip = false;          // the current step got enc_state instead of enc_tokens (te = 0)
+    BridgePlan plan;
+    float *jbuf = nullptr, *h_j = nullptr; // [B x 2R] j = [c_T | h_T] (device) and the pinned staging of enc_state
+    float *qd = nullptr, *vd = nullptr, *qc = nullptr, *ic = nullptr; // [B x 2R], [B x I], [B x 2R] x 2
+    float *dqp = nullptr, *dvp = nullptr, *dh0 = nullptr, *dfeat = nullptr; // [B x 2R] x 2, [B x R], [B x I]
+    float *br_slabs = nullptr;  // [zq + zv][B][2R] split-K partials of the bridge's projections
     float *slabs = nullptr;     // split-K partials of the weight gradients
     size_t slab_floats = 0;
     float *colpart = nullptr;   // column-sum partials
@@ -579,12 +595,22 @@ int ae_create(nvqa_ctx *c)
     const size_t B = d.B, D = d.T, E = d.E, R = d.R, L = d.L, V = d.V;
     a.ae2 = d.arch == NVQA_ARCH_AE2 || d.arch == NVQA_ARCH_AE2_WP;
     a.wp = d.arch == NVQA_ARCH_AE2_WP;
+    a.bridge = d.arch == NVQA_ARCH_AE1_WP;
+    a.feats = a.wp || a.bridge;
     a.D = (int)D;
     a.QM = (int)(2 * D + (a.ae2 ? 3 : 1));
     a.dstr = (int)D + (a.ae2 ? 1 : 0);
     a.ldl = (int)((V + 1 + 3) / 4 * 4);
     const size_t QM = a.QM, total4 = (c->lo.total + 3) / 4 * 4; // (padding: nvqa_rmsprop_update runs over whole float4s)
-    AE_ALLOC(c->P, total4);
+    if (a.bridge) {
+        // device order [encoder | decoder but b_proj | multimodal | b_proj]: b_proj has V + 1 entries, and the products read W_q and
+        // W_v in 16-byte pieces (nvqa_api.hip converts at the ABI); the frozen lookup table sits behind the (padded) vector
+        const size_t nb = V + 1;
+        c->lo.w_q -= nb; c->lo.b_q -= nb; c->lo.w_v -= nb; c->lo.b_v -= nb;
+        c->lo.b_proj = c->lo.total - nb;
+        c->lo.w_lk = total4;
+    }
+    AE_ALLOC(c->P, total4 + (a.bridge ? (V + 1) * E : 0));
     AE_ALLOC(c->G, total4);
     AE_ALLOC(c->M2, total4);
     AE_ALLOC(a.tok, B * D);
@@ -595,7 +621,7 @@ int ae_create(nvqa_ctx *c)
     }
     AE_ALLOC(a.cur, B);
     AE_ALLOC(a.samples, B * D);
-    if (!a.wp) { // the frozen lookup of AE2_WP takes no gradient
+    if (!a.feats) { // the frozen lookup of the weak-paired archs takes no gradient
         AE_ALLOC(a.lk_tok, QM * B);
         AE_ALLOC(a.lk_tc, QM * B + 1);
         AE_ALLOC(a.lk_start, QM * B + 1);
@@ -609,24 +635,44 @@ int ae_create(nvqa_ctx *c)
         AE_ALLOC(a.img, B * E);
         NVQA_HIP(hipHostMalloc((void **)&a.h_img, B * E * 4, hipHostMallocDefault));
     }
-    if (a.wp) {
-        const size_t I = d.I, NP = E * I + E;
+    if (a.feats) {
+        const size_t I = d.I;
         AE_ALLOC(a.etok, B * D);
         NVQA_HIP(hipHostMalloc((void **)&a.h_etok, B * D * 4, hipHostMallocDefault));
         AE_ALLOC(a.feat, B * I);
         NVQA_HIP(hipHostMalloc((void **)&a.h_feat, B * I * 4, hipHostMallocDefault));
+        NVQA_HIP(hipEventCreateWithFlags(&a.staged, hipEventDisableTiming));
+    }
+    if (a.bridge) {
+        const size_t I = d.I, N = 2 * R;
+        int cus = 0;
+        NVQA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        a.plan = ae1wp_bridge_plan((int)B, (int)N, (int)N, (int)I, cus > 0 ? cus : 256);
+        AE_ALLOC(a.jbuf, B * N);
+        NVQA_HIP(hipHostMalloc((void **)&a.h_j, B * N * 4, hipHostMallocDefault));
+        AE_ALLOC(a.qd, B * N);
+        AE_ALLOC(a.vd, B * I);
+        AE_ALLOC(a.qc, B * N);
+        AE_ALLOC(a.ic, B * N);
+        AE_ALLOC(a.dqp, B * N);
+        AE_ALLOC(a.dvp, B * N);
+        AE_ALLOC(a.dh0, B * R);
+        AE_ALLOC(a.dfeat, B * I);
+        AE_ALLOC(a.br_slabs, (size_t)(a.plan.zq + a.plan.zv) * B * N);
+    }
+    if (a.wp) {
+        const size_t I = d.I, NP = E * I + E;
         AE_ALLOC(a.wp_x, NP);
         AE_ALLOC(a.wp_g, NP);
         AE_ALLOC(a.wp_m, NP);
         AE_ALLOC(a.wp_v, NP);
         AE_ALLOC(a.wp_part, 2 * 1024);
-        NVQA_HIP(hipEventCreateWithFlags(&a.staged, hipEventDisableTiming));
     }
     AE_ALLOC(a.X0, QM * B * E);
     for (size_t l = 0; l < L; ++l) {
         AE_ALLOC(a.Gt[l], QM * B * 4 * R);
-        AE_ALLOC(a.Hs[l], (QM + 1) * B * R);
-        AE_ALLOC(a.Cs[l], (QM + 1) * B * R);
+        AE_ALLOC(a.Hs[l], (QM + 1 + (a.bridge ? 1 : 0)) * B * R);
+        AE_ALLOC(a.Cs[l], (QM + 1 + (a.bridge ? 1 : 0)) * B * R);
         if (l > 0) AE_ALLOC(a.U[l], QM * B * R);
     }
     AE_ALLOC(a.dX, QM * B * std::max(E, R));
@@ -637,6 +683,7 @@ int ae_create(nvqa_ctx *c)
     AE_ALLOC(a.rowloss, (D + 1) * B);
     AE_ALLOC(a.loss, 4);
     a.slab_floats = (size_t)8 * 4 * R * std::max(E, R);
+    if (a.bridge) a.slab_floats = std::max(a.slab_floats, (size_t)2 * R * std::max<size_t>(2 * R, d.I)); // dW_q, dW_v: at least one slab
     AE_ALLOC(a.slabs, a.slab_floats);
     a.colpart_floats = (size_t)64 * std::max<size_t>(4 * R, V + 1);
     AE_ALLOC(a.colpart, a.colpart_floats);
@@ -649,14 +696,14 @@ void ae_destroy(nvqa_ctx *c)
     AeState &a = *c->ae;
     void *ptrs[] = {a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
                     a.logits, a.rowloss, a.loss, a.slabs, a.colpart, a.img, a.etok, a.feat, a.wp_x, a.wp_g, a.wp_m, a.wp_v,
-                    a.wp_part};
+                    a.wp_part, a.jbuf, a.qd, a.vd, a.qc, a.ic, a.dqp, a.dvp, a.dh0, a.dfeat, a.br_slabs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (a.staged) (void)hipEventDestroy(a.staged);
     for (int l = 0; l < NVQA_MAX_LAYERS; ++l)
         for (void *p : {(void *)a.Gt[l], (void *)a.Hs[l], (void *)a.Cs[l], (void *)a.U[l]})
             if (p) (void)hipFree(p);
-    for (void *p : {(void *)a.h_lk, (void *)a.h_tok, (void *)a.h_loss, (void *)a.h_img, (void *)a.h_etok, (void *)a.h_feat})
+    for (void *p : {(void *)a.h_lk, (void *)a.h_tok, (void *)a.h_loss, (void *)a.h_img, (void *)a.h_etok, (void *)a.h_feat, (void *)a.h_j})
         if (p) (void)hipHostFree(p);
     delete c->ae;
     c->ae = nullptr;
@@ -691,19 +738,21 @@ static int ae_fwd_step(nvqa_ctx *c, int l, int q, const Drop &dr)
     AeState &a = *c->ae;
     const int B = c->d.B, R = c->d.R;
     const bool dec = q >= a.te;
-    ProfScope ps(c, PF_AE_LSTM_FWD, q > 0 ? 2.0 * B * 4 * R * R : 0.0);
+    const int sl = q + (a.bridge && dec ? 1 : 0); // state slot step q reads
+    const bool h_in = q > 0 || (a.bridge && dec); // h_{-1} = 0 but for a decoder that starts from the bridge
+    ProfScope ps(c, PF_AE_LSTM_FWD, h_in ? 2.0 * B * 4 * R * R : 0.0);
     EpiLstmFwd e = {};
     e.gx = a.Gt[l] + (size_t)q * B * 4 * R;
-    e.c_prev = a.Cs[l] + (size_t)q * B * R;
-    e.c = a.Cs[l] + (size_t)(q + 1) * B * R;
-    e.h = a.Hs[l] + (size_t)(q + 1) * B * R;
+    e.c_prev = a.Cs[l] + (size_t)sl * B * R;
+    e.c = a.Cs[l] + (size_t)(sl + 1) * B * R;
+    e.h = a.Hs[l] + (size_t)(sl + 1) * B * R;
     e.nrows = a.nrows;
     e.R = R; e.B = B; e.T = a.QM; e.t = q; e.lnext_m1 = l;
     e.dr = dr;
-    const float *hprev = a.Hs[l] + (size_t)q * B * R;
+    const float *hprev = a.Hs[l] + (size_t)sl * B * R;
     GemmArgs g = ae_args(hprev, R, c->P + w_h2h_of(c, l, dec), R, B, R, 0);
     g.R = R;
-    g.A2 = hprev; g.lda2 = R; g.B2 = c->P + w_h2h_of(c, l, dec); g.ldb2 = R; g.K2 = q > 0 ? R : 0; // h_{-1} = 0
+    g.A2 = hprev; g.lda2 = R; g.B2 = c->P + w_h2h_of(c, l, dec); g.ldb2 = R; g.K2 = h_in ? R : 0;
     AE_LAUNCH(AeCfgGates, A_KC, B_KC, true, EpiLstmFwd, 1, g, e);
     return 0;
 }
@@ -728,7 +777,7 @@ static int ae_project(nvqa_ctx *c, int s0, int s1, const Drop &dr)
     const int B = c->d.B, R = c->d.R, L = c->d.L, Vp1 = c->d.V + 1;
     const size_t n = (size_t)(s1 - s0) * B * R;
     hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s,
-                       a.Hs[L - 1] + (size_t)(a.te + 1 + s0) * B * R, a.Htd + (size_t)s0 * B * R, n, R, B, a.dstr, L, 0, 0,
+                       a.Hs[L - 1] + (size_t)(a.te + 1 + (a.bridge ? 1 : 0) + s0) * B * R, a.Htd + (size_t)s0 * B * R, n, R, B, a.dstr, L, 0, 0,
                        s0 * B, 1, dr);
     NVQA_HIP(hipGetLastError());
     const int M = (s1 - s0) * B;
@@ -745,7 +794,17 @@ static int ae_embed(nvqa_ctx *c, int q0, int q1, const int32_t *direct, const Dr
     const nvqa_dims &d = c->d;
     if (q1 <= q0) return 0;
     ProfScope ps(c, PF_AE_EMB, 0, (double)(q1 - q0) * d.B * d.E * 8);
-    if (a.wp) { // AE2's assembly per token stream: encoder rows [1, te) from etok, decoder rows from tok; row 0 is ae_wp_project's
+    if (a.bridge) { // AE1's lookup per token stream, evaluate()d (no mask: AutoEncoder_vqa_arch.lua:133-134), from the table behind the vector
+        const int e1 = std::min(q1, a.te), d0 = std::max(q0, a.te);
+        const dim3 nt(std::min(256, (d.E + 63) / 64 * 64));
+        const Drop none = ae_drop(nullptr, false);
+        if (e1 > q0)
+            hipLaunchKernelGGL(k_ae_embed, dim3((unsigned)((e1 - q0) * d.B)), nt, 0, c->s, a.etok, (const int32_t *)nullptr, d.B, a.D,
+                               d.V, d.E, a.te, q0, c->P + c->lo.w_lk, none, a.X0);
+        if (q1 > d0)
+            hipLaunchKernelGGL(k_ae_embed, dim3((unsigned)((q1 - d0) * d.B)), nt, 0, c->s, a.tok, direct, d.B, a.D, d.V, d.E, a.te,
+                               d0, c->P + c->lo.w_lk, none, a.X0);
+    } else if (a.wp) { // AE2's assembly per token stream: encoder rows [1, te) from etok, decoder rows from tok; row 0 is ae_wp_project's
         const int e0 = std::max(q0, 1), e1 = std::min(q1, a.te), d0 = std::max(q0, a.te);
         const dim3 nt(std::min(256, (d.E + 63) / 64 * 64));
         if (e1 > e0)
@@ -776,6 +835,72 @@ static int ae_wp_project(nvqa_ctx *c)
     return 0;
 }
 
+// AE1_WP: the bridge (ae_bridge.h) from the encoder's final slot te (or the caller's j: skip) into the decoder's slot te + 1
+static int ae_bridge_forward(nvqa_ctx *c, const Drop &dr)
+{
+    AeState &a = *c->ae;
+    const int B = c->d.B, R = c->d.R, I = c->d.I, N = 2 * R;
+    const BridgePlan &pl = a.plan;
+    ProfScope ps(c, PF_AE1WP_BRIDGE_FWD, 2.0 * B * N * (double)(N + I), 4.0 * N * (double)(N + I));
+    const size_t sl = (size_t)a.te * B * R;
+    hipLaunchKernelGGL(k_ae1wp_bridge_prep, dim3((unsigned)std::min<size_t>(((size_t)B * (N + I) + 255) / 256, 2048)), dim3(256), 0, c->s,
+                       a.skip ? (const float *)nullptr : a.Cs[0] + sl, a.skip ? (const float *)nullptr : a.Hs[0] + sl, a.jbuf,
+                       (const float *)a.feat, B, R, I, dr, a.qd, a.vd);
+    NVQA_HIP(hipGetLastError());
+    float *sq = a.br_slabs, *sv = a.br_slabs + (size_t)pl.zq * B * N;
+    const float *Wq = c->P + c->lo.w_q, *Wv = c->P + c->lo.w_v;
+    if (pl.skinny) {
+        BridgeGemvArgs g = {};
+        g.x[0] = a.qd; g.x[1] = a.vd; g.w[0] = Wq; g.w[1] = Wv; g.slab[0] = sq; g.slab[1] = sv;
+        g.K[0] = N; g.K[1] = I; g.Z[0] = pl.zq; g.Z[1] = pl.zv; g.B = B; g.N = N; g.ks = pl.ks;
+        hipLaunchKernelGGL(k_ae1wp_bridge_gemv, dim3((unsigned)pl.workgroups), dim3(256), 0, c->s, g);
+        NVQA_HIP(hipGetLastError());
+    } else {
+        GemmArgs gq = ae_args(a.qd, N, Wq, N, B, N, N, pl.ks), gv = ae_args(a.vd, I, Wv, I, B, N, I, pl.ks);
+        const EpiStore eq{sq, N, (size_t)B * N}, ev{sv, N, (size_t)B * N};
+        AE_LAUNCH(AeCfgWide, A_KC, B_KC, false, EpiStore, 0, gq, eq);
+        AE_LAUNCH(AeCfgWide, A_KC, B_KC, false, EpiStore, 0, gv, ev);
+    }
+    hipLaunchKernelGGL(k_ae1wp_bridge_fwd, dim3((unsigned)(((size_t)B * N + 255) / 256)), dim3(256), 0, c->s, (const float *)sq, pl.zq,
+                       (const float *)sv, pl.zv, B, R, c->P + c->lo.b_q, c->P + c->lo.b_v, (const float *)a.jbuf, dr, a.qc, a.ic,
+                       a.Cs[0] + sl + (size_t)B * R, a.Hs[0] + sl + (size_t)B * R);
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
+
+// AE1_WP, behind the backward of decoder step 0 (chain step te): a.dc = dc0, Gt[te] = that step's dG.  dh0 = dG W_h2h (the
+// decoder's), the bridge's backward, its weight gradients, and -- if the encoder ran -- dc_T into a.dc and dh_T into the
+// encoder's last row block of dHx.  want_df: df^ into a.dfeat.
+static int ae_bridge_backward(nvqa_ctx *c, const Drop &dr, bool want_df)
+{
+    AeState &a = *c->ae;
+    const int B = c->d.B, R = c->d.R, I = c->d.I, N = 2 * R, TE = a.te;
+    ProfScope ps(c, PF_AE1WP_BRIDGE_BWD, 2.0 * B * 4 * R * R + 2.0 * B * N * (double)(N + I) * (want_df ? 2 : 1) + (a.skip ? 0.0 : 2.0 * B * N * N));
+    {
+        GemmArgs g = ae_args(a.Gt[0] + (size_t)TE * B * 4 * R, 4 * R, c->P + c->lo.d_w_h2h[0], R, B, R, 4 * R);
+        const EpiStore e{a.dh0, R, 0};
+        AE_LAUNCH(AeCfgStepBwd, A_KC, B_NC, false, EpiStore, 0, g, e);
+    }
+    hipLaunchKernelGGL(k_ae1wp_bridge_bwd, dim3((unsigned)(((size_t)B * N + 255) / 256)), dim3(256), 0, c->s, (const float *)a.dc,
+                       (const float *)a.dh0, (const float *)a.qc, (const float *)a.ic, B, R, dr, a.dqp, a.dvp);
+    NVQA_HIP(hipGetLastError());
+    NVQA_TRY(wgrad(c, a.dqp, N, a.qd, N, N, N, B, c->G + c->lo.w_q));
+    NVQA_TRY(colsum(c, a.dqp, B, N, N, c->G + c->lo.b_q, nullptr));
+    NVQA_TRY(wgrad(c, a.dvp, N, a.vd, I, N, I, B, c->G + c->lo.w_v));
+    NVQA_TRY(colsum(c, a.dvp, B, N, N, c->G + c->lo.b_v, nullptr));
+    if (!a.skip) {
+        GemmArgs g = ae_args(a.dqp, N, c->P + c->lo.w_q, N, B, N, N);
+        const EpiAe1wpDj e{a.dc, a.dHx + (size_t)(TE - 1) * B * R, a.dh0, R, dr};
+        AE_LAUNCH(AeCfgStepBwd, A_KC, B_NC, false, EpiAe1wpDj, 0, g, e);
+    }
+    if (want_df) {
+        GemmArgs g = ae_args(a.dvp, N, c->P + c->lo.w_v, I, B, I, N);
+        const EpiAe1wpDf e{a.dfeat, I, dr};
+        AE_LAUNCH(AeCfgWide, A_KC, B_NC, false, EpiAe1wpDf, 0, g, e);
+    }
+    return 0;
+}
+
 // teacher-forced forward of the whole chain (training and evaluate mode) + the criterion; grad: d(logits) in place
 static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool grad)
 {
@@ -788,7 +913,10 @@ static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool 
         if (l > 0) NVQA_TRY(ae_layer_input(c, l, 0, Q, dr));
         NVQA_TRY(ae_i2h(c, l, 0, a.te, false));
         NVQA_TRY(ae_i2h(c, l, a.te, Q, true));
-        for (int q = 0; q < Q; ++q) NVQA_TRY(ae_fwd_step(c, l, q, dr));
+        for (int q = 0; q < Q; ++q) {
+            if (a.bridge && q == a.te) NVQA_TRY(ae_bridge_forward(c, dr));
+            NVQA_TRY(ae_fwd_step(c, l, q, dr));
+        }
     }
     NVQA_TRY(ae_project(c, 0, a.tmax + 1, dr));
     const int rows = (a.tmax + 1) * B;
@@ -803,14 +931,14 @@ static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool 
     return 0;
 }
 
-static int ae_backward(nvqa_ctx *c, const Drop &dr)
+static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
     const int B = d.B, R = d.R, E = d.E, L = d.L, Vp1 = d.V + 1, T = a.tmax, TE = a.te, Q = TE + T + 1;
     const int rows = (T + 1) * B;
     // projection: dH_top (through drop_final) into the decoder rows of dHx, dW_proj, db_proj
-    NVQA_HIP(hipMemsetAsync(a.dHx, 0, (size_t)TE * B * R * 4, c->s)); // the encoder's rows: no loss reaches them directly
+    if (TE > 0) NVQA_HIP(hipMemsetAsync(a.dHx, 0, (size_t)TE * B * R * 4, c->s)); // the encoder's rows: no loss reaches them directly
     {
         ProfScope ps(c, PF_AE_PROJ_BWD, 4.0 * rows * (double)Vp1 * R);
         GemmArgs g = ae_args(a.logits, a.ldl, c->P + c->lo.w_proj, R, rows, R, Vp1);
@@ -824,12 +952,15 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
         NVQA_HIP(hipMemsetAsync(a.dc, 0, (size_t)B * R * 4, c->s));
         for (int q = Q - 1; q >= 0; --q) {
             // dh_q = dG_{q+1} W_h2h (of the phase of step q+1) + dHx_q; cell backward (epilogues.h EpiLstmBwd)
-            const bool last = q == Q - 1, dec_next = q + 1 >= TE;
+            // (AE1_WP: the encoder's last step gets its dh_T from the bridge through dHx, not from a recurrent product)
+            const bool last = q == Q - 1 || (a.bridge && q == TE - 1), dec_next = q + 1 >= TE;
+            const int sl = q + (a.bridge && q >= TE ? 1 : 0);
+            {
             ProfScope ps(c, PF_AE_LSTM_BWD, last ? 0.0 : 2.0 * B * 4 * R * R);
             EpiLstmBwd e = {};
             e.gates = a.Gt[l] + (size_t)q * B * 4 * R;
-            e.c_prev = a.Cs[l] + (size_t)q * B * R;
-            e.c = a.Cs[l] + (size_t)(q + 1) * B * R;
+            e.c_prev = a.Cs[l] + (size_t)sl * B * R;
+            e.c = a.Cs[l] + (size_t)(sl + 1) * B * R;
             e.dc = a.dc;
             e.dh_ext = a.dHx + (size_t)q * B * R;
             e.nrows = a.nrows;
@@ -837,8 +968,11 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
             GemmArgs g = ae_args(last ? a.Gt[l] : a.Gt[l] + (size_t)(q + 1) * B * 4 * R, 4 * R, c->P + w_h2h_of(c, l, dec_next), R,
                                  B, R, last ? 0 : 4 * R);
             AE_LAUNCH(AeCfgStepBwd, A_KC, B_NC, false, EpiLstmBwd, 0, g, e);
+            }
+            if (a.bridge && q == TE) NVQA_TRY(ae_bridge_backward(c, dr, want_df));
         }
-        {   // d(input) of both phases (AE2_WP, layer 0: chain step 0 only, dx0 -- the frozen lookup takes no gradient)
+        if (!a.bridge) { // d(input) of both phases (AE2_WP, layer 0: chain step 0 only, dx0 -- the frozen lookup takes no gradient;
+                         // AE1_WP: frozen lookup and no image row, so nobody reads it)
             const bool cut = a.wp && l == 0;
             ProfScope ps(c, PF_AE_DGRAD, 2.0 * (cut ? 1 : Q) * B * 4.0 * R * in);
             for (int ph = 0; ph < 2; ++ph) {
@@ -853,10 +987,14 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
             ProfScope ps(c, PF_AE_WGRAD, 4.0 * Q * B * 4.0 * R * (in + R));
             for (int ph = 0; ph < 2; ++ph) {
                 const int q0 = ph ? TE : 0, q1 = ph ? Q : TE, K = (q1 - q0) * B;
+                if (a.bridge && K == 0) { // the encoder was skipped: its gradient segment is exactly zero
+                    NVQA_HIP(hipMemsetAsync(c->G, 0, c->lo.seg[0] * 4, c->s));
+                    continue;
+                }
                 const float *dG = a.Gt[l] + (size_t)q0 * B * 4 * R;
                 const float *X = (l == 0 ? a.X0 : a.U[l]) + (size_t)q0 * B * in;
                 NVQA_TRY(wgrad(c, dG, 4 * R, X, in, 4 * R, in, K, c->G + w_i2h_of(c, l, ph == 1)));
-                NVQA_TRY(wgrad(c, dG, 4 * R, a.Hs[l] + (size_t)q0 * B * R, R, 4 * R, R, K, c->G + w_h2h_of(c, l, ph == 1)));
+                NVQA_TRY(wgrad(c, dG, 4 * R, a.Hs[l] + (size_t)(q0 + (a.bridge && ph ? 1 : 0)) * B * R, R, 4 * R, R, K, c->G + w_h2h_of(c, l, ph == 1)));
                 NVQA_TRY(colsum(c, dG, K, 4 * R, 4 * R, c->G + (ph ? c->lo.d_b_i2h[l] : c->lo.b_i2h[l]),
                                 c->G + (ph ? c->lo.d_b_h2h[l] : c->lo.b_h2h[l])));
             }
@@ -875,6 +1013,7 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
         NVQA_TRY(colsum(c, a.dX, B, E, E, a.wp_g + (size_t)E * I, nullptr));
         return 0;
     }
+    if (a.bridge) return 0; // the frozen table has no gradient
     {   // lookup table: both token streams into one gradient (AE2: every chain row but the image's)
         ProfScope ps(c, PF_AE_EMB_BWD, 0, (double)Q * B * E * (a.ae2 ? 4 : 12));
         NVQA_HIP(hipMemsetAsync(c->G + c->lo.w_lk, 0, (size_t)Vp1 * E * 4, c->s));
@@ -894,14 +1033,14 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr)
 // AE2_WP: enc_tokens [n x D] (NULL: the null sentence) -> etok and te = 2 + their tmax; feats [n x I] -> feat, L2-normalised
 // over the n rows (the padding rows stay zero).
 static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *images, bool index, int *ncount,
-                     const float *feats = nullptr, const int32_t *enc_tokens = nullptr)
+                     const float *feats = nullptr, const int32_t *enc_tokens = nullptr, const float *enc_state = nullptr)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
     const int B = d.B, D = a.D, V = d.V;
     // the staging buffers may still feed the previous step's copies.  AE2_WP waits for those copies only, so that staging its
     // B x I features overlaps the previous step's kernels
-    if (a.wp && a.staged_rec) NVQA_HIP(hipEventSynchronize(a.staged));
+    if (a.feats && a.staged_rec) NVQA_HIP(hipEventSynchronize(a.staged));
     else NVQA_HIP(hipStreamSynchronize(c->s));
     int tmax = 0, cnt = 0;
     for (int b = 0; b < B; ++b)
@@ -921,7 +1060,7 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *ima
         }
     }
     int tmax_e = 0;
-    if (a.wp) {
+    if (a.feats) {
         for (int b = 0; b < B; ++b)
             for (int t = 0; t < D; ++t) {
                 const int v = b < n && enc_tokens ? enc_tokens[(size_t)b * D + t] : 0;
@@ -931,18 +1070,26 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *ima
             }
     }
     a.tmax = tmax;
-    a.te = a.wp ? tmax_e + 2 : (a.ae2 ? tmax + 2 : tmax);
+    a.te = a.wp ? tmax_e + 2 : (a.ae2 ? tmax + 2 : (a.bridge ? tmax_e : tmax));
+    a.skip = a.bridge && enc_state;
+    if (a.bridge && !a.skip && tmax_e == 0) { set_error("ae: enc_tokens holds no token (every row is null)"); return -1; }
     *ncount = cnt;
     NVQA_HIP(hipMemcpyAsync(a.tok, a.h_tok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
-    if (a.wp) {
+    if (a.feats) {
         const size_t I = d.I;
+        if (a.skip) {
+            const size_t N = 2 * (size_t)d.R;
+            memcpy(a.h_j, enc_state, (size_t)n * N * 4);
+            if (n < B) memset(a.h_j + (size_t)n * N, 0, (size_t)(B - n) * N * 4);
+            NVQA_HIP(hipMemcpyAsync(a.jbuf, a.h_j, (size_t)B * N * 4, hipMemcpyHostToDevice, c->s));
+        }
         NVQA_HIP(hipMemcpyAsync(a.etok, a.h_etok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
         memcpy(a.h_feat, feats, (size_t)n * I * 4);
         if (n < B) memset(a.h_feat + (size_t)n * I, 0, (size_t)(B - n) * I * 4);
         NVQA_HIP(hipMemcpyAsync(a.feat, a.h_feat, (size_t)B * I * 4, hipMemcpyHostToDevice, c->s));
         NVQA_HIP(hipEventRecord(a.staged, c->s));
         a.staged_rec = true;
-        ProfScope ps(c, PF_AE_WP_PROJ_FWD, 0, (double)n * I * 12);
+        ProfScope ps(c, a.bridge ? PF_AE1WP_BRIDGE_FWD : PF_AE_WP_PROJ_FWD, 0, (double)n * I * 12);
         NVQA_TRY(l2norm_rows_launch(c->s, a.feat, n, (int)I));
     }
     a.img_live = a.ae2 && images;
@@ -1014,7 +1161,7 @@ static int ae_check(nvqa_ctx *c)
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
     if (!is_ae(c->d) || !c->ae) {
-        set_error("not an auto-encoder context (arch %d; NVQA_ARCH_AE1 = 3, NVQA_ARCH_AE2 = 4, NVQA_ARCH_AE2_WP = 5)", c->d.arch);
+        set_error("not an auto-encoder context (arch %d; NVQA_ARCH_AE1 = 3, NVQA_ARCH_AE2 = 4, NVQA_ARCH_AE2_WP = 5, NVQA_ARCH_AE1_WP = 6)", c->d.arch);
         return -1;
     }
     NVQA_HIP(hipSetDevice(c->device));
@@ -1036,6 +1183,17 @@ static int ae_check_not_wp(nvqa_ctx *c, const char *fn)
         set_error("%s: not available on a weak-paired auto-encoder context (NVQA_ARCH_AE2_WP: nvqa_ae_wp_step / nvqa_ae_wp_evaluate)", fn);
         return -1;
     }
+    if (c->d.arch == NVQA_ARCH_AE1_WP) {
+        set_error("%s: not available on an arch1 weak-paired auto-encoder context (NVQA_ARCH_AE1_WP: nvqa_ae1_wp_step / nvqa_ae1_wp_evaluate)", fn);
+        return -1;
+    }
+    return 0;
+}
+
+static int ae_check_bridge(nvqa_ctx *c, const char *fn)
+{
+    NVQA_TRY(ae_check(c));
+    if (c->d.arch != NVQA_ARCH_AE1_WP) { set_error("%s: an NVQA_ARCH_AE1_WP context expected (arch %d)", fn, c->d.arch); return -1; }
     return 0;
 }
 
@@ -1047,15 +1205,20 @@ static int ae_check_wp(nvqa_ctx *c, const char *fn)
 }
 
 static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out,
-                        float *dimages_out, const float *feats = nullptr, const int32_t *enc_tokens = nullptr)
+                        float *dimages_out, const float *feats = nullptr, const int32_t *enc_tokens = nullptr,
+                        const float *enc_state = nullptr, float *dfeats_out = nullptr)
 {
     if (!tokens) { set_error("tokens is NULL"); return -1; }
     const Drop dr = ae_drop(dropout, true);
     int ncount = 0;
-    NVQA_TRY(ae_upload(c, c->d.B, tokens, images, !c->ae->wp, &ncount, feats, enc_tokens));
+    NVQA_TRY(ae_upload(c, c->d.B, tokens, images, !c->ae->feats, &ncount, feats, enc_tokens, enc_state));
     NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
-    NVQA_TRY(ae_backward(c, dr));
+    NVQA_TRY(ae_backward(c, dr, dfeats_out != nullptr));
     c->have_grads = true;
+    if (dfeats_out) {
+        NVQA_HIP(hipMemcpyAsync(dfeats_out, c->ae->dfeat, (size_t)c->d.B * c->d.I * 4, hipMemcpyDeviceToHost, c->s));
+        NVQA_HIP(hipStreamSynchronize(c->s));
+    }
     if (dimages_out) // layer 0's d(input) of chain step 0 (the backward pass ends with layer 0)
         NVQA_HIP(hipMemcpyAsync(dimages_out, c->ae->dX, (size_t)c->d.B * c->d.E * 4, hipMemcpyDeviceToHost, c->s));
     if (loss_out || dimages_out) {
@@ -1142,6 +1305,79 @@ extern "C" int nvqa_ae_wp_evaluate(nvqa_ctx *c, int32_t n, const float *feats, c
     NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_evaluate"));
     if (!feats) { set_error("nvqa_ae_wp_evaluate: feats is NULL"); return -1; }
     return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, feats, enc_tokens);
+}
+
+extern "C" int nvqa_ae1_wp_step(nvqa_ctx *c, const float *feats, const int32_t *enc_tokens, const float *enc_state,
+                                const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out)
+{
+    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_step"));
+    if (!feats) { set_error("nvqa_ae1_wp_step: feats is NULL"); return -1; }
+    if ((enc_tokens != nullptr) == (enc_state != nullptr)) {
+        set_error("nvqa_ae1_wp_step: exactly one of enc_tokens and enc_state must be given");
+        return -1;
+    }
+    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr, feats, enc_tokens, enc_state, dfeats_out);
+}
+
+extern "C" int nvqa_ae1_wp_evaluate(nvqa_ctx *c, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                                    float *loss_out, int32_t *samples_out)
+{
+    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_evaluate"));
+    if (!feats || !enc_tokens) { set_error("nvqa_ae1_wp_evaluate: feats or enc_tokens is NULL"); return -1; }
+    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, feats, enc_tokens);
+}
+
+// the evaluate-mode encoder alone: [c_T | h_T] of the state slot te, joined by the bridge's prep kernel
+extern "C" int nvqa_ae1_wp_encode(nvqa_ctx *c, int32_t n, const int32_t *enc_tokens, float *state_out)
+{
+    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_encode"));
+    if (!enc_tokens || !state_out) { set_error("nvqa_ae1_wp_encode: NULL argument"); return -1; }
+    if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
+    AeState &a = *c->ae;
+    const int B = c->d.B, D = a.D, V = c->d.V, R = c->d.R, I = c->d.I;
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    int te = 0;
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < D; ++t) {
+            const int v = b < n ? enc_tokens[(size_t)b * D + t] : 0;
+            if (v < 0 || v > V) { set_error("ae: enc_tokens %d at (%d, %d) outside 0..%d", v, b, t, V); return -1; }
+            a.h_etok[(size_t)b * D + t] = v;
+            if (v) te = std::max(te, t + 1);
+        }
+    if (te == 0) { set_error("ae: enc_tokens holds no token (every row is null)"); return -1; }
+    a.te = te;
+    a.skip = false;
+    NVQA_HIP(hipMemcpyAsync(a.etok, a.h_etok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
+    const Drop dr = ae_drop(nullptr, false);
+    NVQA_TRY(ae_embed(c, 0, te, nullptr, dr));
+    NVQA_TRY(ae_i2h(c, 0, 0, te, false));
+    for (int q = 0; q < te; ++q) NVQA_TRY(ae_fwd_step(c, 0, q, dr));
+    const size_t sl = (size_t)te * B * R;
+    hipLaunchKernelGGL(k_ae1wp_bridge_prep, dim3((unsigned)std::min<size_t>(((size_t)B * (2 * R + I) + 255) / 256, 2048)), dim3(256), 0,
+                       c->s, (const float *)(a.Cs[0] + sl), (const float *)(a.Hs[0] + sl), a.jbuf, (const float *)a.feat, B, R, I, dr,
+                       a.qd, a.vd);
+    NVQA_HIP(hipGetLastError());
+    NVQA_HIP(hipMemcpyAsync(state_out, a.jbuf, (size_t)n * 2 * R * 4, hipMemcpyDeviceToHost, c->s));
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    return 0;
+}
+
+extern "C" int nvqa_ae1_wp_set_lookup(nvqa_ctx *c, const float *w)
+{
+    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_set_lookup"));
+    if (!w) { set_error("NULL argument"); return -1; }
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    NVQA_HIP(hipMemcpy(c->P + c->lo.w_lk, w, ((size_t)c->d.V + 1) * c->d.E * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int nvqa_ae1_wp_get_lookup(nvqa_ctx *c, float *w_out)
+{
+    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_get_lookup"));
+    if (!w_out) { set_error("NULL argument"); return -1; }
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    NVQA_HIP(hipMemcpy(w_out, c->P + c->lo.w_lk, ((size_t)c->d.V + 1) * c->d.E * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int nvqa_ae_wp_set_projection(nvqa_ctx *c, const float *w, const float *b)

@@ -50,7 +50,8 @@ static const char *kProfNames[PF_COUNT] = {
     "ride_gemm",
     "ae_emb_fwd",    "ae_gemm_i2h",   "ae_lstm_step_fwd", "ae_gemm_proj_fwd", "ae_softmax_ce", "ae_gemm_proj_bwd",
     "ae_lstm_step_bwd", "ae_gemm_dgrad", "ae_gemm_wgrad", "ae_emb_bwd",      "adam",
-    "ae_wp_proj_fwd", "ae_wp_proj_bwd"};
+    "ae_wp_proj_fwd", "ae_wp_proj_bwd",
+    "ae1wp_bridge_fwd", "ae1wp_bridge_bwd"};
 
 
 static void prof_collect(nvqa_ctx *c)
@@ -168,20 +169,24 @@ template <class T> static int dalloc(T **p, size_t n)
 static int check_dims(const nvqa_dims *d)
 {
     if (!d) { set_error("dims is NULL"); return -1; }
-    if (d->arch == NVQA_ARCH_AE2_WP && (d->I < 4 || d->I % 4)) { // the weak-paired AE's features: whole float4 rows
+    if ((d->arch == NVQA_ARCH_AE2_WP || d->arch == NVQA_ARCH_AE1_WP) && (d->I < 4 || d->I % 4)) { // the weak-paired AEs' features: whole float4 rows
         set_error("weak-paired auto-encoder: I must be a positive multiple of 4 (got I=%d)", d->I);
         return -1;
     }
+    if (d->arch == NVQA_ARCH_AE1_WP) { // AutoEncoder_vqa_arch.lua:24,33: one layer, the bridge's output is the (c, h) pair
+        if (d->L != 1) { set_error("arch1 weak-paired auto-encoder: L must be 1 (got L=%d): the skip connection assumes one layer", d->L); return -1; }
+        if (d->C != 2 * d->R) { set_error("arch1 weak-paired auto-encoder: C must be 2R (got C=%d, R=%d)", d->C, d->R); return -1; }
+    }
     if (is_ae(*d)) { // text auto-encoders: B, T = seq_length, V, E, R, L; no image features (AE2_WP: I), fusion or answers
         if (d->B < 1 || d->T < 1 || d->V < 1 || d->E < 4 || d->R < 4 || d->L < 1 || d->L > NVQA_MAX_LAYERS ||
-            (d->I && d->arch != NVQA_ARCH_AE2_WP) || d->C || d->A) {
-            set_error("auto-encoder: bad dims (B=%d T=%d V=%d E=%d R=%d L=%d; C, A (and I but on arch 5) must be 0)", d->B, d->T, d->V, d->E, d->R, d->L);
+            (d->I && d->arch != NVQA_ARCH_AE2_WP && d->arch != NVQA_ARCH_AE1_WP) || (d->C && d->arch != NVQA_ARCH_AE1_WP) || d->A) {
+            set_error("auto-encoder: bad dims (B=%d T=%d V=%d E=%d R=%d L=%d; A (and I, C but on the weak-paired archs) must be 0)", d->B, d->T, d->V, d->E, d->R, d->L);
             return -1;
         }
         if (d->E % 4 || d->R % 4) { set_error("auto-encoder: E, R must be multiples of 4 (got E=%d R=%d)", d->E, d->R); return -1; }
         return 0;
     }
-    if (d->arch != NVQA_ARCH1 && d->arch != NVQA_ARCH2) { set_error("arch must be 1, 2, 3, 4 or 5"); return -1; }
+    if (d->arch != NVQA_ARCH1 && d->arch != NVQA_ARCH2) { set_error("arch must be 1, 2, 3, 4, 5 or 6"); return -1; }
     if (d->B < 1 || d->T < 1 || d->V < 1 || d->L < 1 || d->L > NVQA_MAX_LAYERS) {
         set_error("bad dims (B=%d T=%d V=%d L=%d)", d->B, d->T, d->V, d->L);
         return -1;
@@ -582,6 +587,7 @@ extern "C" int nvqa_segments(const nvqa_ctx *c, size_t out[3])
 // (Torch nn.Linear [E][V] at the ABI, gather-friendly [V][E] on the device).
 static void to_internal(const nvqa_ctx *c, const float *abi, std::vector<float> &in)
 {
+    const float *abi_ = abi;
     in.assign(abi, abi + c->lo.total);
     if (c->d.arch == NVQA_ARCH1) {
         const size_t E = c->d.E, V = c->d.V;
@@ -589,6 +595,13 @@ static void to_internal(const nvqa_ctx *c, const float *abi, std::vector<float> 
         float *dst = in.data() + c->lo.w_e;
         for (size_t e = 0; e < E; ++e)
             for (size_t v = 0; v < V; ++v) dst[v * E + e] = src[e * V + v];
+    }
+    if (c->d.arch == NVQA_ARCH_AE1_WP) { // the device keeps b_proj (V+1 floats) behind the multimodal tensors: 16-byte rows for the products
+        nvqa_layout abi;
+        (void)nvqa_layout_init(&c->d, &abi);
+        const size_t nb = (size_t)c->d.V + 1, mm = abi.seg[2];
+        memcpy(in.data() + abi.b_proj, abi_ + abi.w_q, mm * sizeof(float));
+        memcpy(in.data() + abi.b_proj + mm, abi_ + abi.b_proj, nb * sizeof(float));
     }
 }
 static void to_abi(const nvqa_ctx *c, const std::vector<float> &in, float *abi)
@@ -601,6 +614,13 @@ static void to_abi(const nvqa_ctx *c, const std::vector<float> &in, float *abi)
         for (size_t v = 0; v < V; ++v)
             for (size_t e = 0; e < E; ++e) dst[e * V + v] = src[v * E + e];
     }
+    if (c->d.arch == NVQA_ARCH_AE1_WP) {
+        nvqa_layout l6;
+        (void)nvqa_layout_init(&c->d, &l6);
+        const size_t nb = (size_t)c->d.V + 1, mm = l6.seg[2];
+        memcpy(abi + l6.w_q, in.data() + l6.b_proj, mm * sizeof(float));
+        memcpy(abi + l6.b_proj, in.data() + l6.b_proj + mm, nb * sizeof(float));
+    }
 }
 
 // torch.norm of the three parameter segments (003_train_vqa_arch2/002_train_baseline.lua:400-407 logs them every 100
@@ -610,21 +630,22 @@ extern "C" int nvqa_param_norms(nvqa_ctx *c, float out[3])
     if (!c || !out) { set_error("NULL argument"); return -1; }
     NVQA_HIP(hipSetDevice(c->device));
     const int NB = 256;
-    if (!c->norm_part) NVQA_HIP(hipMalloc((void **)&c->norm_part, 3 * NB * sizeof(double)));
-    size_t off = 0;
-    for (int sgm = 0; sgm < 3; ++sgm) {
-        hipLaunchKernelGGL(k_sumsq, dim3(NB), dim3(256), 0, c->s, c->P + off, c->lo.seg[sgm], c->norm_part + sgm * NB);
-        off += c->lo.seg[sgm];
-    }
+    if (!c->norm_part) NVQA_HIP(hipMalloc((void **)&c->norm_part, 4 * NB * sizeof(double)));
+    // (offset, length, segment) of the device vector; arch 6 keeps b_proj, a decoder tensor, behind the multimodal ones
+    const size_t s0 = c->lo.seg[0], s1 = c->lo.seg[1], s2 = c->lo.seg[2];
+    const size_t nb = c->d.arch == NVQA_ARCH_AE1_WP ? (size_t)c->d.V + 1 : 0;
+    const size_t piece[4][3] = {{0, s0, 0}, {s0, s1 - nb, 1}, {s0 + s1 - nb, s2, 2}, {s0 + s1 - nb + s2, nb, 1}};
+    const int np = nb ? 4 : 3;
+    for (int i = 0; i < np; ++i)
+        hipLaunchKernelGGL(k_sumsq, dim3(NB), dim3(256), 0, c->s, c->P + piece[i][0], piece[i][1], c->norm_part + i * NB);
     NVQA_HIP(hipGetLastError());
-    std::vector<double> h(3 * NB);
-    NVQA_HIP(hipMemcpyAsync(h.data(), c->norm_part, 3 * NB * sizeof(double), hipMemcpyDeviceToHost, c->s));
+    std::vector<double> h(4 * NB);
+    NVQA_HIP(hipMemcpyAsync(h.data(), c->norm_part, np * NB * sizeof(double), hipMemcpyDeviceToHost, c->s));
     NVQA_HIP(hipStreamSynchronize(c->s));
-    for (int sgm = 0; sgm < 3; ++sgm) {
-        double t = 0;
-        for (int b = 0; b < NB; ++b) t += h[sgm * NB + b];
-        out[sgm] = (float)sqrt(t);
-    }
+    double t[3] = {0, 0, 0};
+    for (int i = 0; i < np; ++i)
+        for (int b = 0; b < NB; ++b) t[piece[i][2]] += h[i * NB + b];
+    for (int sgm = 0; sgm < 3; ++sgm) out[sgm] = (float)sqrt(t[sgm]);
     return check_persist(c);
 }
 
@@ -1737,6 +1758,11 @@ extern "C" int nvqa_set_precision(nvqa_ctx *c, int bf16)
 extern "C" int nvqa_set_grad_scales(nvqa_ctx *c, const float scales[3])
 {
     if (!c || !scales) { set_error("NULL argument"); return -1; }
+    if (c->d.arch == NVQA_ARCH_AE1_WP && !(scales[0] == scales[1] && scales[1] == scales[2])) {
+        // the device keeps b_proj behind the multimodal tensors (ae.hip): a scale chosen by offset would reach the wrong tensor
+        set_error("nvqa_set_grad_scales: per-segment gradient scales are not supported on an arch1 weak-paired auto-encoder context");
+        return -1;
+    }
     for (int i = 0; i < 3; ++i) c->gscale[i] = scales[i];
     return 0;
 }
@@ -1755,8 +1781,8 @@ extern "C" int nvqa_rmsprop_update(nvqa_ctx *c, float lr, float alpha, float eps
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
     if (!c->have_grads) { set_error("nvqa_rmsprop_update before any nvqa_step"); return -1; }
-    if (c->d.arch == NVQA_ARCH_AE2_WP) { // it would decay the frozen lookup table
-        set_error("nvqa_rmsprop_update: not available on a weak-paired auto-encoder context (frozen lookup; nvqa_adam_update)");
+    if (c->d.arch == NVQA_ARCH_AE2_WP || c->d.arch == NVQA_ARCH_AE1_WP) { // AE2_WP: it would decay the frozen lookup table; AE1_WP: the scripts run Adam only
+        set_error("nvqa_rmsprop_update: not available on a weak-paired auto-encoder context (nvqa_adam_update)");
         return -1;
     }
     NVQA_HIP(hipSetDevice(c->device));

@@ -14,7 +14,7 @@
 namespace nvqa {
 
 void set_error(const char *fmt, ...);
-int ae_create(nvqa_ctx *c);  // ae.hip: the buffers of an NVQA_ARCH_AE1 / AE2 / AE2_WP context (instead of the VQA step's)
+int ae_create(nvqa_ctx *c);  // ae.hip: the buffers of an NVQA_ARCH_AE1 / AE2 / AE2_WP / AE1_WP context (instead of the VQA step's)
 void ae_destroy(nvqa_ctx *c);
 float ae_last_loss(const nvqa_ctx *c); // loss of the last nvqa_ae_step / nvqa_ae_evaluate (after a synchronisation)
 int ae_wp_init(nvqa_ctx *c, uint64_t seed, float lo, float hi); // NVQA_ARCH_AE2_WP: the projection's part of nvqa_init_params
@@ -75,6 +75,8 @@ enum ProfId {
     PF_ADAM,         // nvqa_adam_update
     PF_AE_WP_PROJ_FWD, // weak-paired AE: feature L2 norm + x0 = f^ W_p^T + b_p
     PF_AE_WP_PROJ_BWD, // weak-paired AE: dW_p, db_p
+    PF_AE1WP_BRIDGE_FWD, // arch1 weak-paired AE: D_Q / D_V, the two split-K projections, the finisher into the decoder's state slot
+    PF_AE1WP_BRIDGE_BWD, // arch1 weak-paired AE: dh0 product, dqp / dvp, dW_q, dW_v, db_q, db_v, dj into the encoder's last step, df^
     PF_COUNT
 };
 
@@ -238,5 +240,5 @@ struct nvqa_ctx {
 
 namespace nvqa {
 // a text auto-encoder context (ae.hip runs its step; the VQA entry points refuse it)
-static inline bool is_ae(const nvqa_dims &d) { return d.arch == NVQA_ARCH_AE1 || d.arch == NVQA_ARCH_AE2 || d.arch == NVQA_ARCH_AE2_WP; }
+static inline bool is_ae(const nvqa_dims &d) { return d.arch == NVQA_ARCH_AE1 || d.arch == NVQA_ARCH_AE2 || d.arch == NVQA_ARCH_AE2_WP || d.arch == NVQA_ARCH_AE1_WP; }
 } // namespace nvqa

@@ -3,7 +3,9 @@ and 001_train_arch2_text_autoencoder.lua) on the library's NVQA_ARCH_AE1 / NVQA_
 training loop with its log line and learning-rate decay, eval_split, and the export that VQATrainer.init_from_autoencoder
 reads (002_convert_text_model_arch1.lua:27-39; arch2: the table of lua/convert_ae_arch2.lua).
 The weak-paired auto-encoder of the second stage (004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua) runs on an
-NVQA_ARCH_AE2_WP context: WeakPairedDataLoader and WeakPairedAETrainer."""
+NVQA_ARCH_AE2_WP context: WeakPairedDataLoader and WeakPairedAETrainer; its arch1 counterpart
+(004_train_arch1_weakpaired_autoencoder_{vgg,inc}.lua, misc/AutoEncoder_vqa_arch.lua) on an NVQA_ARCH_AE1_WP context:
+WeakPairedAE1Trainer."""
 import json
 
 import numpy as np
@@ -349,3 +351,170 @@ class WeakPairedAETrainer:
         w, b = self.ctx.ae_wp_get_projection()
         t7.save(path, {"encoder": x[:seg[0]].copy(), "lookup_table": np.ascontiguousarray(x[seg[0] + seg[1]:].reshape(d.V + 1, d.E)),
                        "cnn_w": np.concatenate([w.ravel(), b]), "layout": t7.LAYOUT_MARK})
+
+
+# 004_train_arch1_weakpaired_autoencoder_{vgg,inc}.lua: batch size and CNN feature width differ (:43, :57); both use lr 3e-5
+WEAKPAIRED1_DEFAULTS = {"vgg": {"batch_size": 16, "I": 4096}, "inc": {"batch_size": 10, "I": 2048}}
+
+
+class WeakPairedAE1Trainer:
+    """The arch1 weak-paired script's loop on an NVQA_ARCH_AE1_WP context: the encoder-skip draw (:296-304), ae1_wp_step
+    (lossFun), the log line, the learning-rate decay and Adam over [encoder | decoder | multimodal] (clamp, then weight decay,
+    :335-341).  The lookup table is frozen and lives outside the flat vector.
+    dims: binding.Dims with arch = ARCH_AE1_WP, T = seq_length, L = 1, I = the CNN feature width, C = 2R, A = 0.
+
+    The skip draw replaces Lua's `math.random() <= 0.5`, whose stream cannot be reproduced: a numpy generator seeded by
+    (seed, iter), as WeakPairedAETrainer draws its null sentence.  The bridge (netdef.AxB's two Linear) starts from Torch's
+    nn.Linear default, uniform(-1/sqrt(fan_in), 1/sqrt(fan_in)), drawn here from the seed: the script clones a multimodal_net
+    out of the text checkpoint (:150), a module the text model does not have.  The CNN body is frozen and runs outside the
+    library, so the log line ends with paramsNorm (the script's two cnn figures describe that body)."""
+
+    def __init__(self, dims, device=0, variant="vgg", learning_rate=3e-5, learning_rate_decay_start=-1,
+                 learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
+                 grad_clip=0.1, drop_prob=0.5, skip_prob=0.5, seed=123):
+        if dims.arch != binding.ARCH_AE1_WP:
+            raise ValueError("WeakPairedAE1Trainer needs dims.arch = ARCH_AE1_WP (6)")
+        if variant not in WEAKPAIRED1_DEFAULTS:
+            raise ValueError("variant: 'vgg' or 'inc'")
+        if dims.L != 1 or dims.C != 2 * dims.R:
+            raise ValueError("ARCH_AE1_WP: L must be 1 and C must be 2R (AutoEncoder_vqa_arch.lua:24,33)")
+        self.dims = dims
+        self.variant = variant
+        self.ctx = binding.Context(dims, device)
+        self.learning_rate = learning_rate
+        self.decay_start, self.decay_every = learning_rate_decay_start, learning_rate_decay_every
+        self.alpha, self.beta, self.eps = optim_alpha, optim_beta, optim_epsilon
+        self.weight_decay, self.grad_clip = weight_decay, grad_clip
+        self.drop_prob, self.skip_prob, self.seed = drop_prob, skip_prob, seed
+        self.mean_vector = None
+        self.iter = 1
+        self.ctx.init_params(seed, -0.08, 0.08)
+        x = self.ctx.get_params()
+        x[-self.ctx.segments()[2]:] = self.bridge_init(dims, seed)
+        self.ctx.set_params(x)
+
+    @staticmethod
+    def default_dims(variant, T, V, E=512, R=512):
+        """the scripts' dims: batch 16 / 10, I = 4096 / 2048, rnn_size = input_encoding_size = 512, one layer"""
+        w = WEAKPAIRED1_DEFAULTS[variant]
+        return binding.Dims(binding.ARCH_AE1_WP, w["batch_size"], T, V, E, R, 1, w["I"], 2 * R, 0)
+
+    @staticmethod
+    def bridge_init(dims, seed):
+        """[W_q (2R x 2R) | b_q | W_v (2R x I) | b_v]: each Linear's weight and bias uniform(-1/sqrt(fan_in), 1/sqrt(fan_in))"""
+        rng = np.random.default_rng([seed, 0x6272])
+        n, out = 2 * dims.R, []
+        for fan_in in (2 * dims.R, dims.I):
+            k = 1.0 / np.sqrt(fan_in)
+            out += [rng.uniform(-k, k, n * fan_in), rng.uniform(-k, k, n)]
+        return np.concatenate(out).astype(np.float32)
+
+    def init_from_text(self, path):
+        """-start_from_text: encoder, decoder and lookup table of the arch1 text auto-encoder, an
+        AETrainer(ARCH_AE1).export_params table [encoder | decoder | lookup] of the same B-independent dims.  The bridge keeps
+        its initialisation."""
+        t = t7.load(path)
+        if t.get("layout") != t7.LAYOUT_MARK:
+            raise ValueError("text model table has no layout = 'nvqa' marker (AETrainer.export_params writes one)")
+        src = np.asarray(t["params"], np.float32).ravel()
+        d, seg = self.dims, self.ctx.segments()
+        n_lk = (d.V + 1) * d.E
+        if src.size != seg[0] + seg[1] + n_lk:
+            raise ValueError(f"text model has {src.size} values, the model wants {seg[0] + seg[1] + n_lk} = [encoder | decoder | lookup]")
+        x = self.ctx.get_params()
+        x[:seg[0] + seg[1]] = src[:seg[0] + seg[1]]
+        self.ctx.set_params(x)
+        self.ctx.ae1_wp_set_lookup(src[seg[0] + seg[1]:].reshape(d.V + 1, d.E))
+
+    def set_mean_vector(self, v):
+        """the corpus-mean sentence vector [2R] the skipped encoder is replaced by (-lstm_average_path's /mean_vector): an array,
+        or the path of an HDF5 file holding /mean_vector"""
+        if isinstance(v, str):
+            with h5.File(v) as f:
+                v = f.read("mean_vector")
+        v = np.asarray(v, np.float32).ravel()
+        if v.size != 2 * self.dims.R:
+            raise ValueError(f"mean vector has {v.size} values, the model wants 2R = {2 * self.dims.R}")
+        self.mean_vector = v
+        return v
+
+    def mean_sentence_vector(self, loader, split="train", max_sentences=-1):
+        """The mean over a split's sentences of the evaluate-mode [c_T | h_T] (nvqa_ae1_wp_encode), accumulated in float64; the
+        reference reads it from a file and ships no script that writes one.  Sets and returns it."""
+        data = loader.labels[split]
+        n = data.shape[0] if max_sentences <= 0 else min(max_sentences, data.shape[0])
+        acc, used = np.zeros(2 * self.dims.R, np.float64), 0
+        for i in range(0, n, self.dims.B):
+            rows = data[i:min(i + self.dims.B, n)]
+            rows = rows[(rows != 0).any(axis=1)]
+            if rows.shape[0] == 0:
+                continue
+            acc += self.ctx.ae1_wp_encode(rows).astype(np.float64).sum(axis=0)
+            used += rows.shape[0]
+        if used == 0:
+            raise ValueError("no sentence to encode")
+        return self.set_mean_vector(acc / used)
+
+    def skip_encoder(self, it=None):
+        """True when iteration `it` skips the encoder (probability skip_prob)"""
+        it = self.iter if it is None else it
+        return bool(np.random.default_rng([self.seed, it]).random() <= self.skip_prob)
+
+    def current_lr(self):
+        lr = self.learning_rate
+        if self.decay_start >= 0 and self.iter > self.decay_start:
+            lr *= 0.5 ** ((self.iter - self.decay_start) / self.decay_every)
+        return lr
+
+    def train_step(self, tokens, feats):
+        """lossFun + log line + update of one iteration; returns (loss, # updates, paramsNorm, skipped, the log line)."""
+        skip = self.skip_encoder()
+        if skip and self.mean_vector is None:
+            raise ValueError("the encoder is skipped in this iteration: set_mean_vector / mean_sentence_vector first")
+        dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.seed, self.iter)
+        if skip:
+            loss = self.ctx.ae1_wp_step(feats, tokens, enc_state=np.tile(self.mean_vector, (self.dims.B, 1)), dropout=dr)
+        else:
+            loss = self.ctx.ae1_wp_step(feats, tokens, enc_tokens=tokens, dropout=dr)
+        norm, count = self.ctx.adam_update(self.current_lr(), self.alpha, self.beta, self.eps, self.weight_decay, self.grad_clip,
+                                           stats=True)
+        line = "iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f" % (self.iter, loss, count, norm)
+        self.iter += 1
+        return loss, count, norm, skip, line
+
+    def train(self, loader, iters, log=print):
+        losses = []
+        for _ in range(iters):
+            labels, feats, _ = loader.get_batch("train", self.dims.B)
+            out = self.train_step(labels, feats)
+            losses.append(out[0])
+            if log:
+                log(out[-1])
+        return losses
+
+    def eval_split(self, loader, split="val", val_sentences_use=-1):
+        """eval_split (:212-275): forward{feats, labels, labels, 0} -- the encoder runs on the captions -- with the arch2
+        scripts' stopping rule (n grows by batch_size; a wrap or n >= val_sentences_use ends the loop)."""
+        loader.reset_iterator(split)
+        losses, preds, used, n = [], [], 0, 0
+        end = self.dims.V + 1
+        while True:
+            labels, feats, bounds = loader.get_batch(split, self.dims.B)
+            loss, samples = self.ctx.ae1_wp_evaluate(feats, labels, enc_tokens=labels, samples=True)
+            losses.append(loss)
+            for p, a in zip(decode_sequence(loader.ix_to_word, samples, end), decode_sequence(loader.ix_to_word, labels, end)):
+                used += 1
+                preds.append({"seqNo": used, "prediction": p, "actual": a})
+            n += self.dims.B
+            if bounds["wrapped"] or n >= val_sentences_use:
+                break
+        return float(np.mean(losses)), preds
+
+    def export_for_vqa(self, path):
+        """005_convert_weakpaired_model_arch1.lua: {lookup = W_lk^T [E x (V+1)], encoder = the encoder's flat parameters,
+        multimodal = [W_q | b_q | W_v | b_v] flat}, plus layout = 'nvqa': what
+        VQATrainer.init_from_autoencoder(..., with_multimodal=True) reads on an arch1 trainer with set_fusion(1)."""
+        x = self.ctx.get_params()
+        seg = self.ctx.segments()
+        t7.save(path, {"lookup": np.ascontiguousarray(self.ctx.ae1_wp_get_lookup().T), "encoder": x[:seg[0]].copy(),
+                       "multimodal": x[seg[0] + seg[1]:].copy(), "layout": t7.LAYOUT_MARK})

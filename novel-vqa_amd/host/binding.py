@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_PKG, "libnvqa.so")
 COMM_ID_BYTES = 128
 
 
-ARCH1, ARCH2, ARCH_AE1, ARCH_AE2, ARCH_AE2_WP = 1, 2, 3, 4, 5
+ARCH1, ARCH2, ARCH_AE1, ARCH_AE2, ARCH_AE2_WP, ARCH_AE1_WP = 1, 2, 3, 4, 5, 6
 
 
 class NvqaError(RuntimeError):
@@ -87,6 +87,11 @@ SYMBOLS = {
     "nvqa_ae_wp_get_projection": (ctypes.c_int, [_vp, _f32p, _f32p]),
     "nvqa_ae_wp_get_projection_grads": (ctypes.c_int, [_vp, _f32p, _f32p]),
     "nvqa_ae_wp_projection_adam": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
+    "nvqa_ae1_wp_step": (ctypes.c_int, [_vp, _f32p, _i32p, _f32p, _i32p, ctypes.POINTER(Dropout), _f32p, _f32p]),
+    "nvqa_ae1_wp_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _i32p, _f32p, _i32p]),
+    "nvqa_ae1_wp_encode": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p]),
+    "nvqa_ae1_wp_set_lookup": (ctypes.c_int, [_vp, _f32p]),
+    "nvqa_ae1_wp_get_lookup": (ctypes.c_int, [_vp, _f32p]),
     "nvqa_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_profile_reset": (ctypes.c_int, [_vp]),
     "nvqa_profile_count": (ctypes.c_int, [_vp]),
@@ -348,6 +353,56 @@ class Context:
         out = np.zeros(2, np.float32) if stats else None
         self._check(self.lib.nvqa_ae_wp_projection_adam(self._h, lr, beta1, beta2, eps, wd, clamp, _f32(out)))
         return (float(out[0]), int(out[1])) if stats else None
+
+    # ---- arch1 weak-paired auto-encoder (arch ARCH_AE1_WP) --------------------------
+    def ae1_wp_step(self, feats, tokens, enc_tokens=None, enc_state=None, dropout=None, want_loss=True, want_dfeats=False):
+        """nvqa_ae1_wp_step: feats [B x I], tokens [B x D] for the decoder and criterion, and exactly one of enc_tokens [B x D]
+        (the encoder runs) and enc_state [B x 2R] (encoder_skip_flag = 1).  Returns the loss (or None); with want_dfeats
+        (loss or None, d(loss)/d(f^) [B x I])."""
+        d = self.dims
+        f = np.ascontiguousarray(feats, np.float32).reshape(d.B, d.I)
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(d.B, d.T)
+        et = None if enc_tokens is None else np.ascontiguousarray(enc_tokens, np.int32).reshape(d.B, d.T)
+        es = None if enc_state is None else np.ascontiguousarray(enc_state, np.float32).reshape(d.B, 2 * d.R)
+        df = np.empty((d.B, d.I), np.float32) if want_dfeats else None
+        loss = ctypes.c_float(0)
+        dr = ctypes.byref(dropout) if dropout is not None else None
+        self._check(self.lib.nvqa_ae1_wp_step(self._h, _f32(f), _i32(et), _f32(es), _i32(tok), dr,
+                                              ctypes.byref(loss) if want_loss else None, _f32(df)))
+        out = float(loss.value) if want_loss else None
+        return (out, df) if want_dfeats else out
+
+    def ae1_wp_evaluate(self, feats, tokens, enc_tokens, samples=False):
+        """nvqa_ae1_wp_evaluate of n = len(tokens) rows: (evaluate-mode loss, greedy samples [n x D] or None)."""
+        d = self.dims
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(-1, d.T)
+        n = tok.shape[0]
+        f = np.ascontiguousarray(feats, np.float32).reshape(n, d.I)
+        et = np.ascontiguousarray(enc_tokens, np.int32).reshape(n, d.T)
+        out = np.empty((n, d.T), np.int32) if samples else None
+        loss = ctypes.c_float(0)
+        self._check(self.lib.nvqa_ae1_wp_evaluate(self._h, n, _f32(f), _i32(et), _i32(tok), ctypes.byref(loss), _i32(out)))
+        return float(loss.value), out
+
+    def ae1_wp_encode(self, enc_tokens):
+        """nvqa_ae1_wp_encode: the evaluate-mode [c_T | h_T] [n x 2R] of n = len(enc_tokens) <= B rows."""
+        d = self.dims
+        et = np.ascontiguousarray(enc_tokens, np.int32).reshape(-1, d.T)
+        out = np.empty((et.shape[0], 2 * d.R), np.float32)
+        self._check(self.lib.nvqa_ae1_wp_encode(self._h, et.shape[0], _i32(et), _f32(out)))
+        return out
+
+    def ae1_wp_set_lookup(self, w):
+        d = self.dims
+        w = np.ascontiguousarray(w, np.float32).reshape(d.V + 1, d.E)
+        self._check(self.lib.nvqa_ae1_wp_set_lookup(self._h, _f32(w)))
+
+    def ae1_wp_get_lookup(self):
+        """the frozen W_lk [(V+1) x E]"""
+        d = self.dims
+        w = np.empty((d.V + 1, d.E), np.float32)
+        self._check(self.lib.nvqa_ae1_wp_get_lookup(self._h, _f32(w)))
+        return w
 
     def set_fusion(self, mode):
         """0 netdef.AxB, 1 netdef.AskipB, 2 netdef.A_B (W_o becomes [A x 2C]: right after creation only)."""

@@ -73,6 +73,13 @@ int nvqa_ae_wp_get_projection(nvqa_ctx *ctx, float *w_out, float *b_out);
 int nvqa_ae_wp_get_projection_grads(nvqa_ctx *ctx, float *w_out, float *b_out);
 int nvqa_ae_wp_projection_adam(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                                float stats_out[2]);
+int nvqa_ae1_wp_step(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const float *enc_state,
+                     const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out);
+int nvqa_ae1_wp_evaluate(nvqa_ctx *ctx, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                         float *loss_out, int32_t *samples_out);
+int nvqa_ae1_wp_encode(nvqa_ctx *ctx, int32_t n, const int32_t *enc_tokens, float *state_out);
+int nvqa_ae1_wp_set_lookup(nvqa_ctx *ctx, const float *w);
+int nvqa_ae1_wp_get_lookup(nvqa_ctx *ctx, float *w_out);
 int nvqa_profile_enable(nvqa_ctx *ctx, int enable);
 int nvqa_profile_reset(nvqa_ctx *ctx);
 int nvqa_profile_count(const nvqa_ctx *ctx);

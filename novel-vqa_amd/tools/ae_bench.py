@@ -10,8 +10,12 @@ with the text script's zero image rows (nvqa_ae_step on an AE2 context) and its 
 random post-ReLU-like features [B x I] (--I, default 4096), the encoder fed the null sentence in a share --null-share of the
 steps (a fixed draw per step) and the captions otherwise, then nvqa_adam_update on [encoder | decoder] (the script's default
 -finetune_cnn_after -1 never updates the projection).  The reference shape is --B 20 --null-share 0.5.
+--arch 6: the arch1 weak-paired auto-encoder (004_train_arch1_weakpaired_autoencoder_vgg.lua, NVQA_ARCH_AE1_WP):
+nvqa_ae1_wp_step on the same features, the encoder skipped (enc_state = one vector repeated over the batch) in a share
+--null-share of the steps and run on the captions otherwise, then nvqa_adam_update on [encoder | decoder | multimodal].  The
+reference shape is --B 16 --null-share 0.5 (inc: --B 10 --I 2048).
 
-    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5] [--I 4096 --null-share 0.5] [--blocks 5 --steps 10 --warmup 5]
+    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--I 4096 --null-share 0.5] [--blocks 5 --steps 10 --warmup 5]
                                            [--out FILE]
 """
 import argparse
@@ -37,13 +41,16 @@ def step_flops(B, T, V, E, R, L, arch=1, te=None, I=0):
     lstm = sum(2 * B * 4 * R * ((E if l == 0 else R) + R) for l in range(L))
     if arch == 5:
         return 3 * ((te + T + 1) * lstm + (T + 1) * 2.0 * B * R * (V + 1)) + 4.0 * B * E * I
+    if arch == 6:  # te encoder steps (0: skipped); the bridge: forward and weight gradients of both Linear, dj when the encoder ran
+        bridge = 4.0 * B * 2 * R * (2 * R + I) + (2.0 * B * 2 * R * 2 * R if te else 0.0)
+        return 3 * ((te + T + 1) * lstm + (T + 1) * 2.0 * B * R * (V + 1)) + bridge
     fwd = (2 * T + 1 + (2 if arch == 2 else 0)) * lstm + (T + 1) * 2.0 * B * R * (V + 1)
     return 3 * fwd
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", type=int, default=1, choices=(1, 2, 5))
+    ap.add_argument("--arch", type=int, default=1, choices=(1, 2, 5, 6))
     ap.add_argument("--B", type=int, default=1000)
     ap.add_argument("--D", type=int, default=16)
     ap.add_argument("--V", type=int, default=14773)
@@ -59,12 +66,19 @@ def main():
     a = ap.parse_args()
     pkg = ge.load_package()
     b = pkg.binding
-    arch = {1: b.ARCH_AE1, 2: b.ARCH_AE2, 5: b.ARCH_AE2_WP}[a.arch]
-    I = a.I if a.arch == 5 else 0
-    dims = b.Dims(arch, a.B, a.D, a.V, a.E, a.R, a.L, I, 0, 0)
-    lr = {1: 1e-5, 2: 5e-5, 5: 1e-5}[a.arch]
+    arch = {1: b.ARCH_AE1, 2: b.ARCH_AE2, 5: b.ARCH_AE2_WP, 6: b.ARCH_AE1_WP}[a.arch]
+    I = a.I if a.arch in (5, 6) else 0
+    dims = b.Dims(arch, a.B, a.D, a.V, a.E, a.R, a.L, I, 2 * a.R if a.arch == 6 else 0, 0)
+    lr = {1: 1e-5, 2: 5e-5, 5: 1e-5, 6: 3e-5}[a.arch]
     ctx = b.Context(dims, 0)
     ctx.init_params(123, -0.08, 0.08)
+    enc_state = None
+    if a.arch == 6:  # the bridge and the frozen lookup as WeakPairedAE1Trainer sets them up
+        x = ctx.get_params()
+        x[-ctx.segments()[2]:] = pkg.ae.WeakPairedAE1Trainer.bridge_init(dims, 123)
+        ctx.set_params(x)
+        ctx.ae1_wp_set_lookup(np.random.default_rng(2).uniform(-0.08, 0.08, (a.V + 1, a.E)).astype(np.float32))
+        enc_state = np.tile(np.random.default_rng(3).uniform(-0.5, 0.5, 2 * a.R).astype(np.float32), (a.B, 1))
     rng = np.random.default_rng(0)
     batches = []
     for _ in range(8):
@@ -74,7 +88,7 @@ def main():
             tok[i, :n] = rng.integers(1, a.V + 1, n)
         batches.append(tok)
     feats = []
-    if a.arch == 5:
+    if a.arch in (5, 6):
         for _ in batches:
             f = rng.uniform(0, 1, (a.B, I)).astype(np.float32)
             f[rng.uniform(0, 1, (a.B, I)) < 0.5] = 0.0
@@ -90,6 +104,11 @@ def main():
         if a.arch == 5:
             ctx.ae_wp_step(feats[k], batches[k], enc_tokens=None if null[it[0] % null.size] else batches[k], dropout=dr,
                            want_loss=False)
+        elif a.arch == 6:
+            if null[it[0] % null.size]:
+                ctx.ae1_wp_step(feats[k], batches[k], enc_state=enc_state, dropout=dr, want_loss=False)
+            else:
+                ctx.ae1_wp_step(feats[k], batches[k], enc_tokens=batches[k], dropout=dr, want_loss=False)
         else:
             ctx.ae_step(batches[k], dr, want_loss=False)
         ctx.adam_update(lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
@@ -108,6 +127,8 @@ def main():
     timed = range(a.warmup + 1, a.warmup + a.blocks * a.steps + 1)  # the iteration numbers of the timed steps
     if a.arch == 5:
         loss = ctx.ae_wp_step(feats[0], batches[0], enc_tokens=batches[0], dropout=b.Dropout(1, 0.5, 123, 0))
+    elif a.arch == 6:
+        loss = ctx.ae1_wp_step(feats[0], batches[0], enc_tokens=batches[0], dropout=b.Dropout(1, 0.5, 123, 0))
     else:
         loss = ctx.ae_step(batches[0], b.Dropout(1, 0.5, 123, 0))
     # profiled pass (events around every launch group: slower, reported per group only)
@@ -130,16 +151,19 @@ def main():
     if a.arch == 5:  # the timed steps' own batches and encoder lengths
         fl = float(np.mean([step_flops(a.B, tmaxes[i % len(batches)], a.V, a.E, a.R, a.L, 5,
                                        te=2 if null[i % null.size] else tmaxes[i % len(batches)] + 2, I=I) for i in timed]))
+    elif a.arch == 6:
+        fl = float(np.mean([step_flops(a.B, tmaxes[i % len(batches)], a.V, a.E, a.R, a.L, 6,
+                                       te=0 if null[i % null.size] else tmaxes[i % len(batches)], I=I) for i in timed]))
     else:
         fl = float(np.mean([step_flops(a.B, T, a.V, a.E, a.R, a.L, a.arch) for T in tmaxes]))
-    line = {"workload": "ae_arch%d_%s" % (a.arch, "weakpaired" if a.arch == 5 else "text"), "B": a.B, "D": a.D, "V": a.V,
+    line = {"workload": "ae_arch%d_%s" % (a.arch, "weakpaired" if a.arch in (5, 6) else "text"), "B": a.B, "D": a.D, "V": a.V,
             "E": a.E, "R": a.R, "L": a.L, "ms_per_step": round(ms, 4), "block_ms": [round(x, 4) for x in block_ms],
             "block_spread_pct": round(100.0 * (max(block_ms) - min(block_ms)) / ms, 2),
             "sentences_per_s": round(a.B / (ms * 1e-3), 1), "loss": loss,
             "tflop_per_step": round(fl / 1e12, 4), "achieved_tflops": round(fl / (ms * 1e-3) / 1e12, 2),
             "fraction_of_f32_mfma_peak": round(fl / (ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
             "profile": prof}
-    if a.arch == 5:
+    if a.arch in (5, 6):
         line.update(I=I, null_share=a.null_share, null_steps_timed=int(sum(null[i % null.size] for i in timed)))
     s = json.dumps(line)
     print(s)
