@@ -263,6 +263,16 @@ int nvqa_ae_step_images(nvqa_ctx *ctx, const float *images, const int32_t *token
                         float *loss_out, float *dimages_out);
 int nvqa_ae_evaluate_images(nvqa_ctx *ctx, int32_t n, const float *images, const int32_t *tokens, float *loss_out,
                             int32_t *samples_out);
+/* The bf16 operand mode of the NVQA_ARCH_AE1 / NVQA_ARCH_AE2 step: bf16 = 1 rounds both operands of
+ * every dense product -- the time-batched i2h and the recurrent h2h products, their d(input) / d(h) counterparts in BPTT, all
+ * LSTM weight gradients, the vocabulary projection, its dH_top and dW_proj -- to bf16 (round-to-nearest-even) and accumulates
+ * in f32, in nvqa_ae_step* and nvqa_ae_evaluate* alike.  Parameters, activations, the logits the softmax reads, the cell, the
+ * lookup, the dropout masks (applied before the rounding), bias sums, the lookup gradient, Adam and everything at this ABI
+ * stay f32.  May be switched between any two steps; 0 (the default) is the f32 path, bit for bit.
+ * A switch of its own on purpose: nvqa_set_precision(ctx, 1) stays an error on every auto-encoder context (above), and this
+ * call is an error on a VQA context (use nvqa_set_precision there) and on the weak-paired contexts below (at the scripts'
+ * batch sizes of 10 - 20 rows their step is bound by its launches; the image projection and the state bridge stay f32). */
+int nvqa_ae_set_precision(nvqa_ctx *ctx, int bf16);
 /* ---- weak-paired auto-encoder (NVQA_ARCH_AE2_WP contexts) ---- */
 /* 004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua with misc/AutoEncoderNull.lua.  The CNN body is frozen and runs
  * outside: feats [B x I] are its output (vgg: post-ReLU fc7 as nvqa_vgg16_fc7 returns it, I = 4096; inc: I = 2048).  The

@@ -46,6 +46,7 @@
 #include "gemm_f32.h"
 #include "nvqa_ctx.h"
 #include "prof.h"
+#include "wgrad_bf16.h"
 
 using namespace nvqa;
 
@@ -97,6 +98,17 @@ struct AeState {
     bool bridge = false;        // the bridge of ae_bridge.h sits between the LSTMs; decoder state slots are shifted by one
     bool feats = false;         // wp || bridge: features, encoder tokens of their own, frozen lookup
     bool skip = false;          // the current step got enc_state instead of enc_tokens (te = 0)
+    // the bf16 operand mode of AE1 / AE2 (nvqa_ae_set_precision)
+    bool bf16 = false;          // both operands of every dense product rounded to bf16 (nearest even), f32 accumulate
+    bool p16 = false;           // bf16 && R % 8 == 0: the projection group reads bf16 images (below) instead of rounding f32 operands
+    int ld16 = 0;               // leading dimension of the vocabulary-wide images (V + 1 rounded up to 8 bf16; the padding stays zero)
+    unsigned short *Htd16 = nullptr; // [(D + 1) B][R] image of Htd
+    unsigned short *G16 = nullptr;   // [(D + 1) B][ld16] image of (softmax - onehot) / n (the f32 logits are kept as they are)
+    unsigned short *Wp16 = nullptr;  // [V + 1][R] image of W_proj, made per step (the weights move)
+    unsigned short *WpT16 = nullptr; // [R][ld16] its transpose: K-contiguous for dH_top
+    float *rowlse = nullptr;         // [(D + 1) B] log-sum-exp of a logits row
+    int32_t *rowtgt = nullptr;       // [(D + 1) B] its target column, -1 = none: db_proj sums the f32 (softmax - onehot) / n from these
+    float inv_n = 0.f;               // the last criterion's 1 / n
     BridgePlan plan;
     float *jbuf = nullptr, *h_j = nullptr; // [B x 2R] j = [c_T | h_T] (device) and the pinned staging of enc_state
     float *qd = nullptr, *vd = nullptr, *qc = nullptr, *ic = nullptr; // [B x 2R], [B x I], [B x 2R] x 2
@@ -201,8 +213,10 @@ __global__ void k_ae2_assemble(const int32_t *tok, const int32_t *direct, const 
 // inter-layer / top-h dropout (forward: out = scale * in; backward: the same scale on the gradient).
 // kind 0: input of layer l >= 1 at chain rows [r0, r0 + n): src row r is the output of chain step r / B (slot + 1 is added
 //         by the caller's pointer), site NVQA_SITE_AE_LSTM; kind 1: top h of decoder step s = row / B, site NVQA_SITE_AE_TOP.
+// IMG (bf16 operand mode, kind 1): the result also goes out as a bf16 image, the projection products' operand.
+template <bool IMG = false>
 __global__ void k_ae_drop(const float *src, float *dst, size_t n, int R, int B, int D, int L, int l, int tmax, int r0, int kind,
-                          Drop dr)
+                          Drop dr, unsigned short *dst16 = nullptr)
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int r = r0 + (int)(i / R), j = (int)(i % R), q = r / B, b = r % B;
@@ -216,6 +230,7 @@ __global__ void k_ae_drop(const float *src, float *dst, size_t n, int R, int B, 
             }
         }
         dst[i] = s * src[i];
+        if constexpr (IMG) dst16[i] = __builtin_bit_cast(unsigned short, (__bf16)(s * src[i]));
     }
 }
 
@@ -252,8 +267,13 @@ __device__ __forceinline__ void ae_lse_combine(float &m, float &s, float m2, flo
 // (= V+1) at the first null (or s = D), nothing after it.  Statistics with an online max / sum-exp (one read of the row);
 // target rows then get (softmax - onehot) / n in place, rows without a target zeros (grad != 0).  nvalid: rows b >= nvalid
 // carry no loss (nvqa_ae_evaluate with n < B).  Row losses go to rowloss; their sum is taken by k_ae_loss in a fixed order.
+// IMG (bf16 operand mode, grad != 0): the f32 logits stay as they are; (softmax - onehot) / n goes out rounded to bf16 into the
+// image g16 [rows][ld16] (padding columns and rows without a target zero), and the row's log-sum-exp and target are kept for
+// k_ae_colsum_dlogits_part, which sums the f32 values for db_proj.
+template <bool IMG>
 __global__ __launch_bounds__(256) void k_ae_softmax(float *logits, int ldl, int Vp1, const int32_t *tok, int B, int D, int nvalid,
-                                                    float inv_n, int grad, float *rowloss)
+                                                    float inv_n, int grad, float *rowloss, unsigned short *g16, int ld16,
+                                                    float *rowlse, int32_t *rowtgt)
 {
     __shared__ float sm[8], ss[8];
     __shared__ float sh_lse;
@@ -272,6 +292,12 @@ __global__ __launch_bounds__(256) void k_ae_softmax(float *logits, int ldl, int 
     }
     if (tgt < 0) {
         if (threadIdx.x == 0) rowloss[row] = 0.f;
+        if constexpr (IMG) {
+            if (threadIdx.x == 0) rowtgt[row] = -1;
+            uint4 *y = reinterpret_cast<uint4 *>(g16 + (size_t)row * ld16);
+            for (int i = threadIdx.x; i < ld16 / 8; i += blockDim.x) y[i] = make_uint4(0u, 0u, 0u, 0u);
+            return;
+        }
         if (grad) {
             float4 *x4 = reinterpret_cast<float4 *>(x);
             for (int i = threadIdx.x; i < ldl / 4; i += blockDim.x) x4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -305,10 +331,31 @@ __global__ __launch_bounds__(256) void k_ae_softmax(float *logits, int ldl, int 
         const float lse = M + logf(S);
         sh_lse = lse;
         rowloss[row] = lse - x[tgt];
+        if constexpr (IMG) { rowlse[row] = lse; rowtgt[row] = tgt; }
     }
     __syncthreads();
     if (!grad) return;
     const float lse = sh_lse;
+    if constexpr (IMG) {
+        uint4 *y = reinterpret_cast<uint4 *>(g16 + (size_t)row * ld16);
+        for (int i = threadIdx.x; i < ld16 / 8; i += blockDim.x) {
+            float e[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float4 v = 8 * i + 4 * h < ldl ? x4[2 * i + h] : make_float4(0.f, 0.f, 0.f, 0.f);
+                e[4 * h] = v.x; e[4 * h + 1] = v.y; e[4 * h + 2] = v.z; e[4 * h + 3] = v.w;
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int c = 8 * i + k;
+                e[k] = c < Vp1 ? (expf(e[k] - lse) - (c == tgt ? 1.f : 0.f)) * inv_n : 0.f;
+            }
+            const u32x2 lo = __builtin_bit_cast(u32x2, pack_bf16(make_float4(e[0], e[1], e[2], e[3])));
+            const u32x2 hi = __builtin_bit_cast(u32x2, pack_bf16(make_float4(e[4], e[5], e[6], e[7])));
+            y[i] = make_uint4(lo[0], lo[1], hi[0], hi[1]);
+        }
+        return;
+    }
     float4 *y4 = reinterpret_cast<float4 *>(x);
     for (int i = threadIdx.x; i < n4; i += blockDim.x) {
         const float4 v = y4[i];
@@ -387,6 +434,61 @@ __global__ void k_ae_colsum_final(const float *part, int S, int N, float *out, f
     for (int i = 0; i < S; ++i) s += part[(size_t)i * N + n];
     out[n] = s;
     if (out2) out2[n] = s;
+}
+
+// bf16 operand mode: k_ae_colsum_part over d(logits) = (softmax - onehot) / n, formed here in f32 from the logits and the rows'
+// log-sum-exp / target as k_ae_softmax forms it (only its bf16 image is stored): db_proj sums what the f32 path sums, in its order
+__global__ void k_ae_colsum_dlogits_part(const float *X, const float *rowlse, const int32_t *rowtgt, float inv_n, int M, int N, int ld,
+                                         int rps, float *part)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const int m0 = blockIdx.y * rps, m1 = min(M, m0 + rps);
+    auto val = [&](int m) {
+        const int t = rowtgt[m];
+        return t < 0 ? 0.f : (expf(X[(size_t)m * ld + n] - rowlse[m]) - (n == t ? 1.f : 0.f)) * inv_n;
+    };
+    float s0 = 0.f, s1 = 0.f;
+    int m = m0;
+    for (; m + 1 < m1; m += 2) { s0 += val(m); s1 += val(m + 1); }
+    if (m < m1) s0 += val(m);
+    part[(size_t)blockIdx.y * N + n] = s0 + s1;
+}
+
+// bf16 operand mode: the two bf16 images of W_proj [Vp1][R] (R % 8 == 0), one 64 x 64 tile per workgroup through LDS:
+// W16 [Vp1][R] (K = R contiguous: the logits product) and WT16 [R][ld16] (K = V + 1 contiguous: dH_top), whose padding
+// columns [Vp1, ld16) are written as zeros.  16-byte global loads and stores on both sides.
+__global__ __launch_bounds__(256) void k_ae_wproj_images(const float *W, int Vp1, int R, int ld16, unsigned short *W16,
+                                                         unsigned short *WT16)
+{
+    __shared__ unsigned t[64][33]; // [v][r pairs], an odd pitch in words
+    const int v0 = blockIdx.x * 64, r0 = blockIdx.y * 64, tid = threadIdx.x;
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+        const int vl = (tid >> 3) + 32 * ps, rl = 8 * (tid & 7), v = v0 + vl, r = r0 + rl;
+        u32x2 lo = {0u, 0u}, hi = {0u, 0u};
+        if (v < Vp1 && r < R) {
+            const float4 *p = reinterpret_cast<const float4 *>(W + (size_t)v * R + r);
+            lo = __builtin_bit_cast(u32x2, pack_bf16(p[0]));
+            hi = __builtin_bit_cast(u32x2, pack_bf16(p[1]));
+            *reinterpret_cast<uint4 *>(W16 + (size_t)v * R + r) = make_uint4(lo[0], lo[1], hi[0], hi[1]);
+        }
+        t[vl][rl / 2] = lo[0]; t[vl][rl / 2 + 1] = lo[1]; t[vl][rl / 2 + 2] = hi[0]; t[vl][rl / 2 + 3] = hi[1];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+        const int vq = tid & 7, rl = (tid >> 3) + 32 * ps, v = v0 + 8 * vq, r = r0 + rl;
+        if (v >= ld16 || r >= R) continue;
+        unsigned w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned a = t[8 * vq + 2 * j][rl >> 1], b = t[8 * vq + 2 * j + 1][rl >> 1];
+            const unsigned sh = 16 * (rl & 1);
+            w[j] = ((a >> sh) & 0xffffu) | (((b >> sh) & 0xffffu) << 16);
+        }
+        *reinterpret_cast<uint4 *>(WT16 + (size_t)r * ld16 + v) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
 }
 
 // split-K slabs [Z][n] -> out[n], fixed order
@@ -544,24 +646,41 @@ typedef Cfg<16, 128, 128, 32, 4, 2, 1, 1> AeCfgWide;
 typedef Cfg<32, 128, 128, 32, 2, 2, 1, 1> AeCfgLongK;
 typedef Cfg<16, 64, 64, 64, 4, 1, 2, 1> AeCfgGates;  // = CfgLstmFwd
 typedef Cfg<16, 64, 32, 64, 4, 2, 1, 1> AeCfgStepBwd; // = CfgNarrow
+// bf16 operand mode, projection group: both operands bf16 in memory, K-contiguous (gemm_f32.h BF = 2: sizes in pairs of bf16)
+typedef Cfg<16, 128, 128, 32, 4, 2, 1, 1, 0, 0, 2, 1> AeCfgImg; // = CfgDx0B
 
 #define AE_LAUNCH(CFG, AM, BM, GATES, EPI, SEG, g, e) NVQA_HIP((launch_gemm<CFG, AM, BM, GATES, EPI, SEG>(c->s, g, e)))
+// a product of the AE1 / AE2 chain: in the bf16 operand mode the BF = 1 instance of the same configuration (f32 in memory, both
+// operands rounded to bf16 at the fragment read, one bf16 MFMA per four f32 ones, f32 accumulate); else the f32 kernel as ever
+#define AE_LAUNCH_P(CFG, AM, BM, GATES, EPI, SEG, g, e)                          \
+    do {                                                                         \
+        if (c->ae->bf16) AE_LAUNCH(WithBF<CFG>::type, AM, BM, GATES, EPI, SEG, g, e); \
+        else AE_LAUNCH(CFG, AM, BM, GATES, EPI, SEG, g, e);                      \
+    } while (0)
 
-static int colsum(nvqa_ctx *c, const float *X, int M, int N, int ld, float *out, float *out2)
+// dlogits (bf16 operand mode): X = the logits, summed as (softmax - onehot) / n through the rows' log-sum-exp and target
+static int colsum(nvqa_ctx *c, const float *X, int M, int N, int ld, float *out, float *out2, bool dlogits = false)
 {
     AeState &a = *c->ae;
     int S = std::min(64, std::max(1, M / 256));
     const int rps = (M + S - 1) / S;
     S = (M + rps - 1) / rps;
     if ((size_t)S * N > a.colpart_floats) { set_error("ae: column-sum scratch too small"); return -1; }
-    hipLaunchKernelGGL(k_ae_colsum_part, dim3((N + 255) / 256, S), dim3(256), 0, c->s, X, M, N, ld, rps, a.colpart);
+    if (dlogits)
+        hipLaunchKernelGGL(k_ae_colsum_dlogits_part, dim3((N + 255) / 256, S), dim3(256), 0, c->s, X, (const float *)a.rowlse,
+                           (const int32_t *)a.rowtgt, a.inv_n, M, N, ld, rps, a.colpart);
+    else
+        hipLaunchKernelGGL(k_ae_colsum_part, dim3((N + 255) / 256, S), dim3(256), 0, c->s, X, M, N, ld, rps, a.colpart);
     hipLaunchKernelGGL(k_ae_colsum_final, dim3((N + 255) / 256), dim3(256), 0, c->s, a.colpart, S, N, out, out2);
     NVQA_HIP(hipGetLastError());
     return 0;
 }
 
 // out [M x N] = A^T B summed over K rows: A stored [K][M] (lda), B stored [K][N] (ldb); split-K into slabs, fixed-order sum
-static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb, int M, int N, int K, float *out)
+// bf16 operand mode: the K-major gfx950 kernel of wgrad_bf16.h instead, which rounds the f32 rows to bf16 on their way into LDS
+// or, given A16 / B16 (both), stages from bf16 images with the same leading dimensions
+static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb, int M, int N, int K, float *out,
+                 const unsigned short *A16 = nullptr, const unsigned short *B16 = nullptr)
 {
     AeState &a = *c->ae;
     if (K <= 0) {
@@ -571,11 +690,20 @@ static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb,
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
     int Z = std::max(1, std::min(16, 512 / std::max(tiles, 1)));
     while (Z > 1 && (size_t)Z * M * N > a.slab_floats) --Z;
-    const int kslice = ((K + Z - 1) / Z + 31) / 32 * 32;
+    const int kq = a.bf16 ? NVQA_WB_BK : 32;
+    const int kslice = ((K + Z - 1) / Z + kq - 1) / kq * kq;
     Z = (K + kslice - 1) / kslice;
-    GemmArgs g = ae_args(A, lda, Bm, ldb, M, N, K, kslice);
-    const EpiStore e{Z > 1 ? a.slabs : out, N, (size_t)M * N};
-    AE_LAUNCH(AeCfgLongK, A_MC, B_NC, false, EpiStore, 0, g, e);
+    if (a.bf16) {
+        const WgradBf16Args g{A, Bm, A16, B16, Z > 1 ? a.slabs : out, Z > 1 ? (size_t)M * N : 0, lda, ldb, N, M, N, K, kslice};
+        const dim3 grid((M + NVQA_WB_BM - 1) / NVQA_WB_BM, (N + NVQA_WB_BN - 1) / NVQA_WB_BN, Z);
+        if (A16 && B16) hipLaunchKernelGGL((k_wgrad_bf16<true, true>), grid, dim3(256), NVQA_WB_LDS_BYTES, c->s, g);
+        else hipLaunchKernelGGL((k_wgrad_bf16<false, false>), grid, dim3(256), NVQA_WB_LDS_BYTES, c->s, g);
+        NVQA_HIP(hipGetLastError());
+    } else {
+        GemmArgs g = ae_args(A, lda, Bm, ldb, M, N, K, kslice);
+        const EpiStore e{Z > 1 ? a.slabs : out, N, (size_t)M * N};
+        AE_LAUNCH(AeCfgLongK, A_MC, B_NC, false, EpiStore, 0, g, e);
+    }
     if (Z > 1) {
         hipLaunchKernelGGL(k_ae_slab_sum, dim3(1024), dim3(256), 0, c->s, a.slabs, Z, (size_t)M * N, out);
         NVQA_HIP(hipGetLastError());
@@ -694,7 +822,7 @@ void ae_destroy(nvqa_ctx *c)
 {
     if (!c->ae) return;
     AeState &a = *c->ae;
-    void *ptrs[] = {a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
+    void *ptrs[] = {a.Htd16, a.G16, a.Wp16, a.WpT16, a.rowlse, a.rowtgt, a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
                     a.logits, a.rowloss, a.loss, a.slabs, a.colpart, a.img, a.etok, a.feat, a.wp_x, a.wp_g, a.wp_m, a.wp_v,
                     a.wp_part, a.jbuf, a.qd, a.vd, a.qc, a.ic, a.dqp, a.dvp, a.dh0, a.dfeat, a.br_slabs};
     for (void *p : ptrs)
@@ -728,7 +856,7 @@ static int ae_i2h(nvqa_ctx *c, int l, int q0, int q1, bool dec)
     GemmArgs g = ae_args(X, in, c->P + w_i2h_of(c, l, dec), in, M, 4 * R, in);
     const EpiBias2 e{a.Gt[l] + (size_t)q0 * B * 4 * R, 4 * R, c->P + (dec ? c->lo.d_b_i2h[l] : c->lo.b_i2h[l]),
                      c->P + (dec ? c->lo.d_b_h2h[l] : c->lo.b_h2h[l])};
-    AE_LAUNCH(AeCfgWide, A_KC, B_KC, false, EpiBias2, 0, g, e);
+    AE_LAUNCH_P(AeCfgWide, A_KC, B_KC, false, EpiBias2, 0, g, e);
     return 0;
 }
 
@@ -753,7 +881,7 @@ static int ae_fwd_step(nvqa_ctx *c, int l, int q, const Drop &dr)
     GemmArgs g = ae_args(hprev, R, c->P + w_h2h_of(c, l, dec), R, B, R, 0);
     g.R = R;
     g.A2 = hprev; g.lda2 = R; g.B2 = c->P + w_h2h_of(c, l, dec); g.ldb2 = R; g.K2 = h_in ? R : 0;
-    AE_LAUNCH(AeCfgGates, A_KC, B_KC, true, EpiLstmFwd, 1, g, e);
+    AE_LAUNCH_P(AeCfgGates, A_KC, B_KC, true, EpiLstmFwd, 1, g, e);
     return 0;
 }
 
@@ -763,9 +891,9 @@ static int ae_layer_input(nvqa_ctx *c, int l, int q0, int q1, const Drop &dr)
     AeState &a = *c->ae;
     const int B = c->d.B, R = c->d.R;
     const size_t n = (size_t)(q1 - q0) * B * R;
-    hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s,
+    hipLaunchKernelGGL(k_ae_drop<false>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s,
                        a.Hs[l - 1] + (size_t)(q0 + 1) * B * R, a.U[l] + (size_t)q0 * B * R, n, R, B, a.dstr, c->d.L, l, a.te,
-                       q0 * B, 0, dr);
+                       q0 * B, 0, dr, (unsigned short *)nullptr);
     NVQA_HIP(hipGetLastError());
     return 0;
 }
@@ -776,15 +904,27 @@ static int ae_project(nvqa_ctx *c, int s0, int s1, const Drop &dr)
     AeState &a = *c->ae;
     const int B = c->d.B, R = c->d.R, L = c->d.L, Vp1 = c->d.V + 1;
     const size_t n = (size_t)(s1 - s0) * B * R;
-    hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s,
-                       a.Hs[L - 1] + (size_t)(a.te + 1 + (a.bridge ? 1 : 0) + s0) * B * R, a.Htd + (size_t)s0 * B * R, n, R, B, a.dstr, L, 0, 0,
-                       s0 * B, 1, dr);
+    const float *htop = a.Hs[L - 1] + (size_t)(a.te + 1 + (a.bridge ? 1 : 0) + s0) * B * R;
+    const dim3 dgrid((unsigned)std::min<size_t>((n + 255) / 256, 4096));
+    if (a.p16)
+        hipLaunchKernelGGL(k_ae_drop<true>, dgrid, dim3(256), 0, c->s, htop, a.Htd + (size_t)s0 * B * R, n, R, B, a.dstr, L, 0, 0,
+                           s0 * B, 1, dr, a.Htd16 + (size_t)s0 * B * R);
+    else
+        hipLaunchKernelGGL(k_ae_drop<false>, dgrid, dim3(256), 0, c->s, htop, a.Htd + (size_t)s0 * B * R, n, R, B, a.dstr, L, 0, 0,
+                           s0 * B, 1, dr, (unsigned short *)nullptr);
     NVQA_HIP(hipGetLastError());
     const int M = (s1 - s0) * B;
     ProfScope ps(c, PF_AE_PROJ_FWD, 2.0 * M * (double)Vp1 * R);
+    if (a.p16) { // both operands from their bf16 images (sizes in pairs of bf16); the f32 logits as ever
+        GemmArgs g = ae_args(reinterpret_cast<const float *>(a.Htd16 + (size_t)s0 * B * R), R / 2, reinterpret_cast<const float *>(a.Wp16),
+                             R / 2, M, Vp1, R / 2);
+        const EpiAeBias e{a.logits + (size_t)s0 * B * a.ldl, a.ldl, c->P + c->lo.b_proj};
+        AE_LAUNCH(AeCfgImg, A_KC, B_KC, false, EpiAeBias, 0, g, e);
+        return 0;
+    }
     GemmArgs g = ae_args(a.Htd + (size_t)s0 * B * R, R, c->P + c->lo.w_proj, R, M, Vp1, R);
     const EpiAeBias e{a.logits + (size_t)s0 * B * a.ldl, a.ldl, c->P + c->lo.b_proj};
-    AE_LAUNCH(AeCfgWide, A_KC, B_KC, false, EpiAeBias, 0, g, e);
+    AE_LAUNCH_P(AeCfgWide, A_KC, B_KC, false, EpiAeBias, 0, g, e);
     return 0;
 }
 
@@ -908,6 +1048,12 @@ static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool 
     const nvqa_dims &d = c->d;
     const int B = d.B, L = d.L, Q = a.te + a.tmax + 1, Vp1 = d.V + 1;
     if (a.wp) NVQA_TRY(ae_wp_project(c));
+    if (a.p16) { // this step's bf16 images of W_proj (greedy decoding reuses them: the weights do not move before the next step)
+        ProfScope ps(c, PF_AE_WPROJ_IMG, 0, (double)Vp1 * d.R * 8);
+        hipLaunchKernelGGL(k_ae_wproj_images, dim3((a.ld16 + 63) / 64, (d.R + 63) / 64), dim3(256), 0, c->s, c->P + c->lo.w_proj, Vp1,
+                           d.R, a.ld16, a.Wp16, a.WpT16);
+        NVQA_HIP(hipGetLastError());
+    }
     NVQA_TRY(ae_embed(c, 0, Q, nullptr, dr));
     for (int l = 0; l < L; ++l) {
         if (l > 0) NVQA_TRY(ae_layer_input(c, l, 0, Q, dr));
@@ -920,10 +1066,16 @@ static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool 
     }
     NVQA_TRY(ae_project(c, 0, a.tmax + 1, dr));
     const int rows = (a.tmax + 1) * B;
+    a.inv_n = 1.0f / (float)ncount;
     {
-        ProfScope ps(c, PF_AE_SOFTMAX, 0, (double)rows * a.ldl * 4 * (grad ? 3 : 1));
-        hipLaunchKernelGGL(k_ae_softmax, dim3(rows), dim3(256), 0, c->s, a.logits, a.ldl, Vp1, a.tok, B, a.D, nvalid,
-                           1.0f / (float)ncount, grad ? 1 : 0, a.rowloss);
+        ProfScope ps(c, PF_AE_SOFTMAX, 0, (double)rows * a.ldl * 4 * (grad ? (a.p16 ? 2.5 : 3) : 1));
+        if (a.p16 && grad)
+            hipLaunchKernelGGL(k_ae_softmax<true>, dim3(rows), dim3(256), 0, c->s, a.logits, a.ldl, Vp1, a.tok, B, a.D, nvalid,
+                               1.0f / (float)ncount, 1, a.rowloss, a.G16, a.ld16, a.rowlse, a.rowtgt);
+        else
+            hipLaunchKernelGGL(k_ae_softmax<false>, dim3(rows), dim3(256), 0, c->s, a.logits, a.ldl, Vp1, a.tok, B, a.D, nvalid,
+                               1.0f / (float)ncount, grad ? 1 : 0, a.rowloss, (unsigned short *)nullptr, 0, (float *)nullptr,
+                               (int32_t *)nullptr);
         hipLaunchKernelGGL(k_ae_loss, dim3(1), dim3(256), 0, c->s, a.rowloss, rows, 1.0f / (float)ncount, a.loss);
         NVQA_HIP(hipGetLastError());
     }
@@ -939,11 +1091,21 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
     const int rows = (T + 1) * B;
     // projection: dH_top (through drop_final) into the decoder rows of dHx, dW_proj, db_proj
     if (TE > 0) NVQA_HIP(hipMemsetAsync(a.dHx, 0, (size_t)TE * B * R * 4, c->s)); // the encoder's rows: no loss reaches them directly
-    {
+    if (a.p16) {
+        // from the bf16 images: dH_top = G16 WpT16^T (K = V + 1 contiguous in both, zero padding up to ld16), dW_proj = G16^T Htd16
+        // (K = rows, both K-major); db_proj sums the f32 values (k_ae_colsum_dlogits_part) in colsum's order
+        ProfScope ps(c, PF_AE_PROJ_BWD, 4.0 * rows * (double)Vp1 * R);
+        GemmArgs g = ae_args(reinterpret_cast<const float *>(a.G16), a.ld16 / 2, reinterpret_cast<const float *>(a.WpT16), a.ld16 / 2,
+                             rows, R, a.ld16 / 2);
+        const EpiAeTop e{a.dHx + (size_t)TE * B * R, R, B, a.dstr, dr};
+        AE_LAUNCH(AeCfgImg, A_KC, B_KC, false, EpiAeTop, 0, g, e);
+        NVQA_TRY(wgrad(c, a.logits, a.ld16, a.Htd, R, Vp1, R, rows, c->G + c->lo.w_proj, a.G16, a.Htd16));
+        NVQA_TRY(colsum(c, a.logits, rows, Vp1, a.ldl, c->G + c->lo.b_proj, nullptr, true));
+    } else {
         ProfScope ps(c, PF_AE_PROJ_BWD, 4.0 * rows * (double)Vp1 * R);
         GemmArgs g = ae_args(a.logits, a.ldl, c->P + c->lo.w_proj, R, rows, R, Vp1);
         const EpiAeTop e{a.dHx + (size_t)TE * B * R, R, B, a.dstr, dr};
-        AE_LAUNCH(AeCfgLongK, A_KC, B_NC, false, EpiAeTop, 0, g, e);
+        AE_LAUNCH_P(AeCfgLongK, A_KC, B_NC, false, EpiAeTop, 0, g, e);
         NVQA_TRY(wgrad(c, a.logits, a.ldl, a.Htd, R, Vp1, R, rows, c->G + c->lo.w_proj));
         NVQA_TRY(colsum(c, a.logits, rows, Vp1, a.ldl, c->G + c->lo.b_proj, nullptr));
     }
@@ -967,7 +1129,7 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
             e.R = R; e.B = B; e.T = a.QM; e.s = q; e.lm1 = 0; e.dr = dr; e.has_upper = 0;
             GemmArgs g = ae_args(last ? a.Gt[l] : a.Gt[l] + (size_t)(q + 1) * B * 4 * R, 4 * R, c->P + w_h2h_of(c, l, dec_next), R,
                                  B, R, last ? 0 : 4 * R);
-            AE_LAUNCH(AeCfgStepBwd, A_KC, B_NC, false, EpiLstmBwd, 0, g, e);
+            AE_LAUNCH_P(AeCfgStepBwd, A_KC, B_NC, false, EpiLstmBwd, 0, g, e);
             }
             if (a.bridge && q == TE) NVQA_TRY(ae_bridge_backward(c, dr, want_df));
         }
@@ -980,7 +1142,7 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
                 if (q1 <= q0) continue;
                 GemmArgs g = ae_args(a.Gt[l] + (size_t)q0 * B * 4 * R, 4 * R, c->P + w_i2h_of(c, l, ph == 1), in, (q1 - q0) * B, in, 4 * R);
                 const EpiStore e{a.dX + (size_t)q0 * B * in, in, 0};
-                AE_LAUNCH(AeCfgWide, A_KC, B_NC, false, EpiStore, 0, g, e);
+                AE_LAUNCH_P(AeCfgWide, A_KC, B_NC, false, EpiStore, 0, g, e);
             }
         }
         {   // weight and bias gradients of both phases
@@ -1001,8 +1163,8 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
         }
         if (l > 0) { // d(h of layer l-1) through the inter-layer Dropout: the external term of layer l-1's chain
             const size_t n = (size_t)Q * B * R;
-            hipLaunchKernelGGL(k_ae_drop, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s, a.dX, a.dHx,
-                               n, R, B, a.dstr, L, l, TE, 0, 0, dr);
+            hipLaunchKernelGGL(k_ae_drop<false>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s, a.dX, a.dHx,
+                               n, R, B, a.dstr, L, l, TE, 0, 0, dr, (unsigned short *)nullptr);
             NVQA_HIP(hipGetLastError());
         }
     }
@@ -1263,6 +1425,43 @@ static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const i
 }
 
 } // namespace nvqa
+
+// The bf16 operand mode of the AE1 / AE2 step.  A switch of its own: nvqa_set_precision(ctx, 1) stays
+// refused on every auto-encoder context.
+extern "C" int nvqa_ae_set_precision(nvqa_ctx *c, int bf16)
+{
+    if (!c) { set_error("ctx is NULL"); return -1; }
+    if (!is_ae(c->d) || !c->ae) {
+        set_error("nvqa_ae_set_precision: an NVQA_ARCH_AE1 / NVQA_ARCH_AE2 context expected (arch %d); the VQA step's switch is nvqa_set_precision", c->d.arch);
+        return -1;
+    }
+    if (c->ae->feats) {
+        set_error("nvqa_ae_set_precision: not available on a weak-paired auto-encoder context (arch %d): at the scripts' batch sizes "
+                  "the step is bound by its launches, and the image projection and the state bridge stay f32", c->d.arch);
+        return -1;
+    }
+    if (bf16 != 0 && bf16 != 1) { set_error("nvqa_ae_set_precision: precision must be 0 (f32) or 1 (bf16 operands)"); return -1; }
+    AeState &a = *c->ae;
+    if (bf16) {
+        NVQA_HIP(hipSetDevice(c->device));
+        NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_bf16<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES));
+        NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_bf16<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES));
+        if (c->d.R % 8 == 0 && !a.G16) { // the images of the projection group, on first use: an f32-only context never holds them
+            const size_t B = c->d.B, R = c->d.R, Vp1 = (size_t)c->d.V + 1, rows = ((size_t)a.D + 1) * B;
+            a.ld16 = (int)((Vp1 + 7) / 8 * 8);
+            AE_ALLOC(a.Htd16, rows * R);
+            AE_ALLOC(a.Wp16, Vp1 * R);
+            AE_ALLOC(a.WpT16, R * a.ld16);
+            AE_ALLOC(a.rowlse, rows);
+            AE_ALLOC(a.rowtgt, rows);
+            AE_ALLOC(a.G16, rows * a.ld16);
+            NVQA_HIP(hipDeviceSynchronize()); // (the zero fills ran on the null stream)
+        }
+    }
+    a.bf16 = bf16 != 0;
+    a.p16 = a.bf16 && a.G16 != nullptr;
+    return 0;
+}
 
 // AE2: images = NULL (the text script's zero image rows)
 extern "C" int nvqa_ae_step(nvqa_ctx *c, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out)

@@ -51,7 +51,7 @@ static const char *kProfNames[PF_COUNT] = {
     "ae_emb_fwd",    "ae_gemm_i2h",   "ae_lstm_step_fwd", "ae_gemm_proj_fwd", "ae_softmax_ce", "ae_gemm_proj_bwd",
     "ae_lstm_step_bwd", "ae_gemm_dgrad", "ae_gemm_wgrad", "ae_emb_bwd",      "adam",
     "ae_wp_proj_fwd", "ae_wp_proj_bwd",
-    "ae1wp_bridge_fwd", "ae1wp_bridge_bwd"};
+    "ae1wp_bridge_fwd", "ae1wp_bridge_bwd", "ae_wproj_images"};
 
 
 static void prof_collect(nvqa_ctx *c)

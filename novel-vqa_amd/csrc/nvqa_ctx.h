@@ -77,6 +77,7 @@ enum ProfId {
     PF_AE_WP_PROJ_BWD, // weak-paired AE: dW_p, db_p
     PF_AE1WP_BRIDGE_FWD, // arch1 weak-paired AE: D_Q / D_V, the two split-K projections, the finisher into the decoder's state slot
     PF_AE1WP_BRIDGE_BWD, // arch1 weak-paired AE: dh0 product, dqp / dvp, dW_q, dW_v, db_q, db_v, dj into the encoder's last step, df^
+    PF_AE_WPROJ_IMG,     // AE bf16 operand mode: the step's two bf16 images of W_proj
     PF_COUNT
 };
 

@@ -89,11 +89,12 @@ ARCH_DEFAULTS = {
 class AETrainer:
     """The training script's loop on the library: ae_step (lossFun), the log line, the learning-rate decay and the
     Adam (or RMSprop) update.  dims: binding.Dims with arch = ARCH_AE1 or ARCH_AE2, T = seq_length, I = C = A = 0
-    (the arch2 script forces 1 layer, :104; the library takes any L).  learning_rate None: the script's default."""
+    (the arch2 script forces 1 layer, :104; the library takes any L).  learning_rate None: the script's default.
+    bf16: the step's bf16 operand mode (Context.ae_set_precision), for either arch."""
 
     def __init__(self, dims, device=0, learning_rate=None, learning_rate_decay_start=-1, learning_rate_decay_every=50000,
                  optim="adam", optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6, grad_clip=0.1,
-                 drop_prob=0.5, seed=123):
+                 drop_prob=0.5, seed=123, bf16=False):
         if dims.arch not in ARCH_DEFAULTS:
             raise ValueError("AETrainer needs dims.arch = ARCH_AE1 (3) or ARCH_AE2 (4)")
         if learning_rate is None:
@@ -109,7 +110,10 @@ class AETrainer:
         self.weight_decay, self.grad_clip = weight_decay, grad_clip
         self.drop_prob, self.seed = drop_prob, seed
         self.iter = 1
+        self.bf16 = bool(bf16)
         self.ctx.init_params(seed, -0.08, 0.08)
+        if self.bf16:  # bf16 operands for every dense product of the step and of eval_split (nvqa_ae_set_precision)
+            self.ctx.ae_set_precision(1)
 
     def current_lr(self):
         """:342-347"""
@@ -235,7 +239,9 @@ class WeakPairedAETrainer:
     def __init__(self, dims, device=0, variant="vgg", learning_rate=None, learning_rate_decay_start=-1,
                  learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
                  grad_clip=0.1, drop_prob=0.5, rand_val=0.5, finetune_cnn_after=-1, cnn_optim_alpha=0.8, cnn_optim_beta=0.999,
-                 cnn_learning_rate=1e-5, cnn_weight_decay=0.0, seed=123):
+                 cnn_learning_rate=1e-5, cnn_weight_decay=0.0, seed=123, bf16=False):
+        if bf16:
+            raise ValueError("bf16: the weak-paired auto-encoders have no bf16 operand mode (their step is launch-bound)")
         if dims.arch != binding.ARCH_AE2_WP:
             raise ValueError("WeakPairedAETrainer needs dims.arch = ARCH_AE2_WP (5)")
         if variant not in WEAKPAIRED_DEFAULTS:
@@ -371,7 +377,9 @@ class WeakPairedAE1Trainer:
 
     def __init__(self, dims, device=0, variant="vgg", learning_rate=3e-5, learning_rate_decay_start=-1,
                  learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
-                 grad_clip=0.1, drop_prob=0.5, skip_prob=0.5, seed=123):
+                 grad_clip=0.1, drop_prob=0.5, skip_prob=0.5, seed=123, bf16=False):
+        if bf16:
+            raise ValueError("bf16: the weak-paired auto-encoders have no bf16 operand mode (their step is launch-bound)")
         if dims.arch != binding.ARCH_AE1_WP:
             raise ValueError("WeakPairedAE1Trainer needs dims.arch = ARCH_AE1_WP (6)")
         if variant not in WEAKPAIRED1_DEFAULTS:

@@ -80,6 +80,7 @@ SYMBOLS = {
     "nvqa_ae_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _i32p]),
     "nvqa_ae_step_images": (ctypes.c_int, [_vp, _f32p, _i32p, ctypes.POINTER(Dropout), _f32p, _f32p]),
     "nvqa_ae_evaluate_images": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _f32p, _i32p]),
+    "nvqa_ae_set_precision": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_adam_update": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_ae_wp_step": (ctypes.c_int, [_vp, _f32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_wp_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _i32p, _f32p, _i32p]),
@@ -296,6 +297,12 @@ class Context:
             img = np.ascontiguousarray(images, np.float32).reshape(n, d.E)
             self._check(self.lib.nvqa_ae_evaluate_images(self._h, n, _f32(img), _i32(tokens), ctypes.byref(loss), _i32(out)))
         return float(loss.value), out
+
+    def ae_set_precision(self, bf16):
+        """nvqa_ae_set_precision: 1 = both operands of every dense product of the ARCH_AE1 / ARCH_AE2 step rounded to bf16,
+        f32 accumulate; 0 = f32.  (set_precision(1) stays refused on an auto-encoder context; this one is refused on the
+        weak-paired and the VQA contexts.)"""
+        self._check(self.lib.nvqa_ae_set_precision(self._h, int(bf16)))
 
     def adam_update(self, lr, beta1=0.8, beta2=0.999, eps=1e-8, wd=0.0, clamp=0.0, stats=False):
         """clamp -> + wd x -> adam in one pass; stats=True returns (paramsNorm, # updates) of the log line."""

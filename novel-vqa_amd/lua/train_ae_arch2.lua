@@ -41,6 +41,7 @@ cmd:option('-checkpoint_path', '', 'folder to save checkpoints into (empty = thi
 cmd:option('-id', '', 'an id identifying this run/job')
 cmd:option('-seed', 123, 'random number generator seed to use')
 cmd:option('-gpuid', 0, 'which MI355X to use')
+cmd:option('-bf16', 0, '1 = bf16 operands for every dense product of the step, f32 accumulate (nvqa_ae_set_precision)')
 opt = cmd:parse(arg)
 torch.manualSeed(opt.seed)
 
@@ -80,6 +81,7 @@ opt.num_layers = 1
 opt.nhimage, opt.common_embedding_size, opt.num_output = 0, 0, 0
 local ctx = nvqa.create(4, opt, vocab_size, seq_length, opt.gpuid)
 nvqa.check(nvqa.lib.nvqa_init_params(ctx, opt.seed, -0.08, 0.08))
+nvqa.check(nvqa.lib.nvqa_ae_set_precision(ctx, opt.bf16))
 local n_params = tonumber(nvqa.lib.nvqa_param_count(ctx))
 
 local function eval_split(split)                    -- eval_split (:148-204): mean of the per-batch losses

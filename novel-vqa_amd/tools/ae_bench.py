@@ -14,9 +14,11 @@ steps (a fixed draw per step) and the captions otherwise, then nvqa_adam_update 
 nvqa_ae1_wp_step on the same features, the encoder skipped (enc_state = one vector repeated over the batch) in a share
 --null-share of the steps and run on the captions otherwise, then nvqa_adam_update on [encoder | decoder | multimodal].  The
 reference shape is --B 16 --null-share 0.5 (inc: --B 10 --I 2048).
+--bf16 (--arch 1 | 2): the step's bf16 operand mode (nvqa_ae_set_precision); the line then carries "bf16": 1 and the step's
+fraction of the bf16 MFMA roofline as well.
 
-    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--I 4096 --null-share 0.5] [--blocks 5 --steps 10 --warmup 5]
-                                           [--out FILE]
+    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--bf16] [--I 4096 --null-share 0.5]
+                                           [--blocks 5 --steps 10 --warmup 5] [--out FILE]
 """
 import argparse
 import json
@@ -32,6 +34,7 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md "Peak FP32 (matrix)"
+BF16_MFMA_PEAK_TFLOPS = 16 * FP32_MFMA_PEAK_TFLOPS  # the same row: the f32 rate is 1/16 of the BF16 MFMA rate (~2.5 PF dense)
 
 
 def step_flops(B, T, V, E, R, L, arch=1, te=None, I=0):
@@ -62,8 +65,11 @@ def main():
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.bf16 and a.arch not in (1, 2):
+        ap.error("--bf16: the weak-paired auto-encoders have no bf16 operand mode")
     pkg = ge.load_package()
     b = pkg.binding
     arch = {1: b.ARCH_AE1, 2: b.ARCH_AE2, 5: b.ARCH_AE2_WP, 6: b.ARCH_AE1_WP}[a.arch]
@@ -72,6 +78,8 @@ def main():
     lr = {1: 1e-5, 2: 5e-5, 5: 1e-5, 6: 3e-5}[a.arch]
     ctx = b.Context(dims, 0)
     ctx.init_params(123, -0.08, 0.08)
+    if a.bf16:
+        ctx.ae_set_precision(1)
     enc_state = None
     if a.arch == 6:  # the bridge and the frozen lookup as WeakPairedAE1Trainer sets them up
         x = ctx.get_params()
@@ -163,6 +171,8 @@ def main():
             "tflop_per_step": round(fl / 1e12, 4), "achieved_tflops": round(fl / (ms * 1e-3) / 1e12, 2),
             "fraction_of_f32_mfma_peak": round(fl / (ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
             "profile": prof}
+    if a.bf16:
+        line.update(bf16=1, fraction_of_bf16_mfma_peak=round(fl / (ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4))
     if a.arch in (5, 6):
         line.update(I=I, null_share=a.null_share, null_steps_timed=int(sum(null[i % null.size] for i in timed)))
     s = json.dumps(line)
