@@ -188,6 +188,10 @@ int nvqa_param_norms(nvqa_ctx *ctx, float out[3]);
  * (R = 512, E in {200, 512}; BPTT: L <= 2), 0 when it takes the per-level kernels (other shapes, NVQA_PERSIST=0, or after a
  * reported time-out). */
 int nvqa_persistent_state(const nvqa_ctx *ctx, int out[2]);
+/* How many f32-mode weight-gradient products this context has launched so far, by route: out[0] the f32 MFMA chain
+ * (NVQA_WGRAD_SPLIT=0, or a shape the six-term kernels do not take), out[1] k_wgrad_split (NVQA_WGRAD_KERNEL=1), out[2]
+ * k_wgrad_split2 (the default).  The two six-term kernels give the same bits; the counters say which one ran. */
+int nvqa_wgrad_routes(const nvqa_ctx *ctx, int64_t out[3]);
 /* Per-segment gradient scale applied before the clamp: {lr_scale, lr_scale, 1} reproduces
  * -lr_scale of 003_train_ae_based_wp.lua:30,344. */
 int nvqa_set_grad_scales(nvqa_ctx *ctx, const float scales[3]);

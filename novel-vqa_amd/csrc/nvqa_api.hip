@@ -20,6 +20,7 @@
 #include "kernels.h"
 #include "wgrad_bf16.h"
 #include "wgrad_split.h"
+#include "wgrad_split2.h"
 #include "nvqa_ctx.h"
 #include "persist_host.h"
 
@@ -327,6 +328,7 @@ static int create_impl(nvqa_ctx *c)
     NVQA_TRY(dalloc(&c->slabs, c->slab_floats));
     NVQA_TRY(dalloc(&c->chain_slabs, (size_t)L * 2 * NVQA_BWD_ZMAX * ((B + 63) / 64 * 64) * ((R + 63) / 64 * 64)));
     c->wgrad_split_on = env_on("NVQA_WGRAD_SPLIT"); // 0: the f32 weight gradients as the exact f32 MFMA chain (wgrad_split.h)
+    c->wgrad_kernel = env_int("NVQA_WGRAD_KERNEL", 2) == 1 ? 1 : 2; // 1: k_wgrad_split, the 128 x 128 form (same bits as the default, wgrad_split2.h)
     c->fold_i2h = env_on("NVQA_FOLD_I2H"); // 0: layer 0's input projection as a separate time-batched GEMM (A/B runs of the per-level path)
     {   // persistent forward LSTM (lstm_persist.h) where the shape is eligible; NVQA_PERSIST=0: one launch per wavefront level
         c->persist_on = env_on("NVQA_PERSIST");
@@ -559,6 +561,13 @@ extern "C" int nvqa_sync(nvqa_ctx *c)
     NVQA_HIP(hipSetDevice(c->device));
     NVQA_HIP(hipStreamSynchronize(c->s));
     return check_persist(c);
+}
+
+extern "C" int nvqa_wgrad_routes(const nvqa_ctx *c, int64_t out[3])
+{
+    if (!c || !out) { set_error("NULL argument"); return -1; }
+    for (int i = 0; i < 3; ++i) out[i] = c->wgrad_launches[i];
+    return 0;
 }
 
 extern "C" int nvqa_persistent_state(const nvqa_ctx *c, int out[2])
@@ -798,13 +807,25 @@ static int wgrad_split(nvqa_ctx *c, const float *A, int lda, const float *Bm, in
         const double kfrac = c->d.B % NVQA_WS_BK == 0 ? c->batch_len_frac : 1.0;
         ProfScope ps(c, PF_GEMM_WGRAD, 2.0 * M * N * K, ((double)K * (M + N) * kfrac + (double)ks * M * N) * 4, st);
         WgradSplitArgs g{A, Bm, ks == 1 ? dW : slabs, ks == 1 ? 0 : (size_t)M * N, c->nrows, c->d.B, lda, ldb, N, M, N, K};
-        const dim3 grid((M + NVQA_WS_BM - 1) / NVQA_WS_BM, (N + NVQA_WS_BN - 1) / NVQA_WS_BN, ks);
-        static bool attr = false;
-        if (!attr) {
-            NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_split, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS_LDS_BYTES));
-            attr = true;
+        if (c->wgrad_kernel == 2 && wgrad_split2_takes(M, N, K, lda, ldb, c->d.B)) {
+            // the same slabs, bit for bit, from 256 x 128 tiles with a pipelined K loop (wgrad_split2.h); ks stays as chosen above
+            static bool attr2 = false;
+            if (!attr2) {
+                NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_split2, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS2_LDS_BYTES));
+                attr2 = true;
+            }
+            hipLaunchKernelGGL(k_wgrad_split2, dim3(wgrad_split2_blocks(M, N, ks)), dim3(NVQA_WS2_THREADS), NVQA_WS2_LDS_BYTES, st, g, ks);
+            c->wgrad_launches[2] += 1;
+        } else {
+            const dim3 grid((M + NVQA_WS_BM - 1) / NVQA_WS_BM, (N + NVQA_WS_BN - 1) / NVQA_WS_BN, ks);
+            static bool attr = false;
+            if (!attr) {
+                NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_split, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS_LDS_BYTES));
+                attr = true;
+            }
+            hipLaunchKernelGGL(k_wgrad_split, grid, dim3(256), NVQA_WS_LDS_BYTES, st, g);
+            c->wgrad_launches[1] += 1;
         }
-        hipLaunchKernelGGL(k_wgrad_split, grid, dim3(256), NVQA_WS_LDS_BYTES, st, g);
         NVQA_HIP(hipGetLastError());
     }
     if (ks == 1) return 0;
@@ -822,6 +843,7 @@ static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb,
 {
     if (c->bf16 && M % 4 == 0 && N % 4 == 0) return wgrad_bf16(c, A, A16, lda, Bm, B16, ldb, M, N, K, dW, slabs, st);
     if (!c->bf16 && c->wgrad_split_on && wgrad_split_takes(M, N, K, lda, ldb, c->d.B)) return wgrad_split(c, A, lda, Bm, ldb, M, N, K, dW, slabs, st);
+    if (!c->bf16) c->wgrad_launches[0] += 1; // (bf16 mode lands here only where M or N is no multiple of 4: not an f32-mode product)
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
     int ks = 1;
     while (ks < 16 && tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2; // tools/kbench11: 2048 x 200 x 13312: 16 slices 115 us, 8 slices 129 us

@@ -181,6 +181,8 @@ struct nvqa_ctx {
     float *chain_slabs = nullptr; // [L][2][NVQA_BWD_Z][B][R] split-K partials of the BPTT level products
     bool bf16 = false;            // nvqa_set_precision: GEMM operands rounded to bf16, bf16 MFMA, f32 accumulate
     bool wgrad_split_on = true;   // f32 mode: weight gradients as six bf16 MFMA terms per product (wgrad_split.h); NVQA_WGRAD_SPLIT=0: the f32 MFMA chain
+    int wgrad_kernel = 2;         // which six-term kernel: 2 = k_wgrad_split2 (wgrad_split2.h), NVQA_WGRAD_KERNEL=1: k_wgrad_split (same bits)
+    long long wgrad_launches[3] = {0, 0, 0}; // weight-gradient products so far by route: f32 chain, k_wgrad_split, k_wgrad_split2 (nvqa_wgrad_routes)
     bool fold_i2h = true;         // layer-0 input projection as a first K segment of the level kernel; NVQA_FOLD_I2H=0: separate time-batched GEMM
     bool batch_uniform = false;   // current batch: all lengths equal (known on the host)
     float batch_len_frac = 1.f;   // current batch: filled share of its B x T (row, step) slots (host batches: exact; dataset route: the dataset's mean)

@@ -60,6 +60,7 @@ SYMBOLS = {
     "nvqa_set_ref_quirks": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_param_norms": (ctypes.c_int, [_vp, _f32p]),
     "nvqa_persistent_state": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
+    "nvqa_wgrad_routes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     "nvqa_set_grad_scales": (ctypes.c_int, [_vp, _f32p]),
     "nvqa_dataset_load": (ctypes.c_int, [_vp, ctypes.c_int64, _i32p, _i32p, _i32p, _i32p,
                                          ctypes.c_int64, _f32p, ctypes.c_int]),
@@ -444,6 +445,12 @@ class Context:
         out = (ctypes.c_int * 2)()
         self._check(self.lib.nvqa_persistent_state(self._h, out))
         return {"fwd": bool(out[0]), "bwd": bool(out[1])}
+
+    def wgrad_routes(self):
+        """Weight-gradient products launched so far by route: {'f32_chain', 'split', 'split2'} (NVQA_WGRAD_SPLIT / NVQA_WGRAD_KERNEL)."""
+        out = (ctypes.c_int64 * 3)()
+        self._check(self.lib.nvqa_wgrad_routes(self._h, out))
+        return {"f32_chain": int(out[0]), "split": int(out[1]), "split2": int(out[2])}
 
     # ---- dataset ------------------------------------------------------------------
     def dataset_load(self, questions, lengths, img_pos, answers, feats, l2_normalize=False):
