@@ -250,7 +250,7 @@ int nvqa_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const float *images, const in
 
 /* ---- text auto-encoder (NVQA_ARCH_AE1 / NVQA_ARCH_AE2 contexts) ---- */
 /* On an auto-encoder context nvqa_step*, nvqa_forward, nvqa_evaluate, nvqa_set_fusion, nvqa_set_ref_quirks,
- * nvqa_dataset_load, nvqa_comm_init and nvqa_set_precision(ctx, 1) return an error.
+ * nvqa_dataset_load, nvqa_comm_init (data parallel: nvqa_ae_comm_init, below) and nvqa_set_precision(ctx, 1) return an error.
  * One training forward + LanguageModelCriterion + backward (lossFun of 001_train_arch1_text_autoencoder.lua:212-245):
  * tokens [B x D] left-aligned, 1..V, 0 = null.  Gradients stay on the device (nvqa_get_grads, nvqa_adam_update,
  * nvqa_rmsprop_update); *loss_out (may be NULL) = the criterion's mean over the positions that carry a loss. */
@@ -277,6 +277,30 @@ int nvqa_ae_evaluate_images(nvqa_ctx *ctx, int32_t n, const float *images, const
  * call is an error on a VQA context (use nvqa_set_precision there) and on the weak-paired contexts below (at the scripts'
  * batch sizes of 10 - 20 rows their step is bound by its launches; the image projection and the state bridge stay f32). */
 int nvqa_ae_set_precision(nvqa_ctx *ctx, int bf16);
+/* Data parallel for NVQA_ARCH_AE1 / NVQA_ARCH_AE2 contexts (f32 and the bf16 operand mode).  Same id /
+ * rank / world contract and the same collective-library rule as nvqa_comm_init (nvqa_comm_unique_id, nvqa_comm_library,
+ * NVQA_RCCL_LIB).  A call of its own on purpose, as nvqa_ae_set_precision is: nvqa_comm_init stays an error on every auto-encoder
+ * context.  An error on a VQA context, on the weak-paired contexts (batches of 16 - 20 rows, steps bound by their launches), on
+ * a context that already has a communicator, and for a bad rank / world.
+ * With a communicator nvqa_ae_step / nvqa_ae_step_images end with the gradient of the GLOBAL batch: with n_r the criterion's
+ * count on rank r (predictions that carry a loss) and N = sum n_r, nvqa_get_grads returns sum_r (n_r / N) G_r on every rank --
+ * the ranks' counts differ, so the plain mean of their gradients is not that -- and nvqa_adam_update / nvqa_rmsprop_update clamp
+ * and apply that value (the clamp after the mean), with the same stats_out on every rank.  N is formed on the device (a one-float
+ * all-reduce under the forward pass); the gradient travels as one all-reduce per bucket behind the kernels that finish it, in
+ * the same order on every rank: W_proj | b_proj first (under the whole BPTT chain), then per layer, top down, the decoder's and
+ * the encoder's LSTM slice, then the lookup table; a two-float exchange closes the step.  loss_out / nvqa_get_loss return the
+ * global batch's loss sum n_r loss_r / N once that has drained.  dimages_out is this rank's rows of d(loss_r)/d(images) times
+ * n_r world / N: scaled as the rank's own gradient is BEFORE the exchange, so that whatever the caller back-propagates from it
+ * and then averages over the ranks is again the global batch's gradient (d(global loss)/d(own rows) = dimages_out / world).
+ * tmax stays rank-local: the reference's model depends on the batch (the encoder runs to the batch's last non-null column and
+ * feeds 0 -> 1 before it), so every rank runs its own rows exactly as a single-GPU step would, and the exchange forms the
+ * count-weighted mean.  That equals the step on the concatenated batch whenever all ranks have the same tmax.
+ * nvqa_ae_evaluate* issue no collective: they are rank-local, and one rank may evaluate while the others do not.  Dropout masks
+ * stay keyed by (seed, step, site, rank-local element): distinct seeds per rank are the caller's job.
+ * A step is collective: every rank must call it the same number of times.  When nvqa_ae_step* returns an error on one rank
+ * before its collectives were issued (an all-null batch, a token outside 0..V), the other ranks block in the count's
+ * all-reduce: treat a step error on any rank as fatal for the whole job. */
+int nvqa_ae_comm_init(nvqa_ctx *ctx, int rank, int world, const void *id);
 /* ---- weak-paired auto-encoder (NVQA_ARCH_AE2_WP contexts) ---- */
 /* 004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua with misc/AutoEncoderNull.lua.  The CNN body is frozen and runs
  * outside: feats [B x I] are its output (vgg: post-ReLU fc7 as nvqa_vgg16_fc7 returns it, I = 4096; inc: I = 2048).  The

@@ -34,6 +34,9 @@
 // reads slot te + 1 + s and writes te + 2 + s, slot te + 1 = the bridge's output.  The backward pass stops the recurrent
 // product behind decoder step 0, runs the bridge's backward there, and starts the encoder's last step from its dc_T / dh_T.
 // With the encoder skipped (encoder_skip_flag = 1) te = 0, j is the caller's and the encoder's gradient segment is zeroed.
+// Data parallel (AE1 / AE2 with nvqa_ae_comm_init): the criterion's kernels scale by a rank weight
+// n_r world / N read from device memory (N = the ranks' summed criterion counts, exchanged under the forward pass), and the
+// backward pass hands each bucket of the gradient to the communication stream as soon as it is final.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -85,6 +88,13 @@ struct AeState {
     float *rowloss = nullptr;   // [(D + 1) B]
     float *loss = nullptr;      // device scalar
     float *h_loss = nullptr;    // pinned
+    // data parallel (nvqa_ae_comm_init): dpw = {n_r, N, w_r = n_r world / N, 1.0f} on the device.  The
+    // criterion's kernels read their rank weight through wcur: dpw + 3 (exactly 1) without a communicator and in evaluate mode,
+    // dpw + 2 in a data-parallel step, where the communication stream writes it under the forward pass
+    float *dpw = nullptr;
+    const float *wcur = nullptr;
+    bool dp_wait = false;       // this step's rank weight is still on its way: the compute stream waits in front of the softmax
+    bool loss_global = false;   // the last loss is a data-parallel step's: the exchanged sum in h_dp_status[2]
     int32_t *etok = nullptr;    // AE2_WP: [B x D] encoder tokens of the current batch (device; 0 rows = the null sentence)
     int32_t *h_etok = nullptr;  // AE2_WP: pinned staging
     float *feat = nullptr;      // AE2_WP: [B x I] features, L2-normalised in place (f^, kept for dW_p)
@@ -272,8 +282,8 @@ __device__ __forceinline__ void ae_lse_combine(float &m, float &s, float m2, flo
 // k_ae_colsum_dlogits_part, which sums the f32 values for db_proj.
 template <bool IMG>
 __global__ __launch_bounds__(256) void k_ae_softmax(float *logits, int ldl, int Vp1, const int32_t *tok, int B, int D, int nvalid,
-                                                    float inv_n, int grad, float *rowloss, unsigned short *g16, int ld16,
-                                                    float *rowlse, int32_t *rowtgt)
+                                                    float inv_n, const float *rank_w, int grad, float *rowloss,
+                                                    unsigned short *g16, int ld16, float *rowlse, int32_t *rowtgt)
 {
     __shared__ float sm[8], ss[8];
     __shared__ float sh_lse;
@@ -336,6 +346,7 @@ __global__ __launch_bounds__(256) void k_ae_softmax(float *logits, int ldl, int 
     __syncthreads();
     if (!grad) return;
     const float lse = sh_lse;
+    const float rw = rank_w[0]; // data parallel: n_r world / N, so that the ranks' sum / world is the global batch's gradient; else 1
     if constexpr (IMG) {
         uint4 *y = reinterpret_cast<uint4 *>(g16 + (size_t)row * ld16);
         for (int i = threadIdx.x; i < ld16 / 8; i += blockDim.x) {
@@ -348,7 +359,7 @@ __global__ __launch_bounds__(256) void k_ae_softmax(float *logits, int ldl, int 
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int c = 8 * i + k;
-                e[k] = c < Vp1 ? (expf(e[k] - lse) - (c == tgt ? 1.f : 0.f)) * inv_n : 0.f;
+                e[k] = c < Vp1 ? (expf(e[k] - lse) - (c == tgt ? 1.f : 0.f)) * inv_n * rw : 0.f;
             }
             const u32x2 lo = __builtin_bit_cast(u32x2, pack_bf16(make_float4(e[0], e[1], e[2], e[3])));
             const u32x2 hi = __builtin_bit_cast(u32x2, pack_bf16(make_float4(e[4], e[5], e[6], e[7])));
@@ -363,14 +374,15 @@ __global__ __launch_bounds__(256) void k_ae_softmax(float *logits, int ldl, int 
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int c = 4 * i + k;
-            e[k] = c < Vp1 ? (expf(e[k] - lse) - (c == tgt ? 1.f : 0.f)) * inv_n : 0.f;
+            e[k] = c < Vp1 ? (expf(e[k] - lse) - (c == tgt ? 1.f : 0.f)) * inv_n * rw : 0.f;
         }
         y4[i] = make_float4(e[0], e[1], e[2], e[3]);
     }
 }
 
-// sum of the row losses in a fixed order (256 strided partials, then a tree) / n
-__global__ __launch_bounds__(256) void k_ae_loss(const float *rowloss, int nrows, float inv_n, float *out)
+// sum of the row losses in a fixed order (256 strided partials, then a tree) / n, times the rank weight (1 but in a
+// data-parallel step, where the ranks' sum / world is then the global batch's loss)
+__global__ __launch_bounds__(256) void k_ae_loss(const float *rowloss, int nrows, float inv_n, const float *rank_w, float *out)
 {
     __shared__ float sh[256];
     float s = 0.f;
@@ -381,8 +393,14 @@ __global__ __launch_bounds__(256) void k_ae_loss(const float *rowloss, int nrows
         if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[0] = sh[0] * inv_n;
+    if (threadIdx.x == 0) out[0] = sh[0] * inv_n * rank_w[0];
 }
+
+// data parallel: cnt = {n_r, N, w_r, 1}.  k_ae_set_count writes this rank's criterion count, k_ae_rank_weight forms
+// w_r = n_r world / N behind the all-reduce of the count, both on the communication stream.  n_r world and N are whole numbers
+// below 2^24, so ranks with equal counts get exactly 1.
+__global__ void k_ae_set_count(float *cnt, float n) { cnt[0] = n; }
+__global__ void k_ae_rank_weight(float *cnt, float world) { cnt[2] = cnt[0] * world / cnt[1]; }
 
 // greedy decoding: argmax of one decoder step's logits (first maximum, as torch.max on the CPU), 1-based; recorded as the
 // sample of step s - 1 (sample() records the token fed at t >= 2) and fed to the next step
@@ -438,15 +456,16 @@ __global__ void k_ae_colsum_final(const float *part, int S, int N, float *out, f
 
 // bf16 operand mode: k_ae_colsum_part over d(logits) = (softmax - onehot) / n, formed here in f32 from the logits and the rows'
 // log-sum-exp / target as k_ae_softmax forms it (only its bf16 image is stored): db_proj sums what the f32 path sums, in its order
-__global__ void k_ae_colsum_dlogits_part(const float *X, const float *rowlse, const int32_t *rowtgt, float inv_n, int M, int N, int ld,
-                                         int rps, float *part)
+__global__ void k_ae_colsum_dlogits_part(const float *X, const float *rowlse, const int32_t *rowtgt, float inv_n, const float *rank_w,
+                                         int M, int N, int ld, int rps, float *part)
 {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     const int m0 = blockIdx.y * rps, m1 = min(M, m0 + rps);
+    const float w = rank_w[0];
     auto val = [&](int m) {
         const int t = rowtgt[m];
-        return t < 0 ? 0.f : (expf(X[(size_t)m * ld + n] - rowlse[m]) - (n == t ? 1.f : 0.f)) * inv_n;
+        return t < 0 ? 0.f : (expf(X[(size_t)m * ld + n] - rowlse[m]) - (n == t ? 1.f : 0.f)) * inv_n * w;
     };
     float s0 = 0.f, s1 = 0.f;
     int m = m0;
@@ -668,7 +687,7 @@ static int colsum(nvqa_ctx *c, const float *X, int M, int N, int ld, float *out,
     if ((size_t)S * N > a.colpart_floats) { set_error("ae: column-sum scratch too small"); return -1; }
     if (dlogits)
         hipLaunchKernelGGL(k_ae_colsum_dlogits_part, dim3((N + 255) / 256, S), dim3(256), 0, c->s, X, (const float *)a.rowlse,
-                           (const int32_t *)a.rowtgt, a.inv_n, M, N, ld, rps, a.colpart);
+                           (const int32_t *)a.rowtgt, a.inv_n, a.wcur, M, N, ld, rps, a.colpart);
     else
         hipLaunchKernelGGL(k_ae_colsum_part, dim3((N + 255) / 256, S), dim3(256), 0, c->s, X, M, N, ld, rps, a.colpart);
     hipLaunchKernelGGL(k_ae_colsum_final, dim3((N + 255) / 256), dim3(256), 0, c->s, a.colpart, S, N, out, out2);
@@ -810,6 +829,12 @@ int ae_create(nvqa_ctx *c)
     AE_ALLOC(a.logits, (D + 1) * B * (size_t)a.ldl);
     AE_ALLOC(a.rowloss, (D + 1) * B);
     AE_ALLOC(a.loss, 4);
+    AE_ALLOC(a.dpw, 4);
+    {
+        const float one[2] = {1.f, 1.f};
+        NVQA_HIP(hipMemcpy(a.dpw + 2, one, 8, hipMemcpyHostToDevice));
+    }
+    a.wcur = a.dpw + 3;
     a.slab_floats = (size_t)8 * 4 * R * std::max(E, R);
     if (a.bridge) a.slab_floats = std::max(a.slab_floats, (size_t)2 * R * std::max<size_t>(2 * R, d.I)); // dW_q, dW_v: at least one slab
     AE_ALLOC(a.slabs, a.slab_floats);
@@ -823,7 +848,7 @@ void ae_destroy(nvqa_ctx *c)
     if (!c->ae) return;
     AeState &a = *c->ae;
     void *ptrs[] = {a.Htd16, a.G16, a.Wp16, a.WpT16, a.rowlse, a.rowtgt, a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
-                    a.logits, a.rowloss, a.loss, a.slabs, a.colpart, a.img, a.etok, a.feat, a.wp_x, a.wp_g, a.wp_m, a.wp_v,
+                    a.logits, a.rowloss, a.loss, a.dpw, a.slabs, a.colpart, a.img, a.etok, a.feat, a.wp_x, a.wp_g, a.wp_m, a.wp_v,
                     a.wp_part, a.jbuf, a.qd, a.vd, a.qc, a.ic, a.dqp, a.dvp, a.dh0, a.dfeat, a.br_slabs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1067,19 +1092,27 @@ static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool 
     NVQA_TRY(ae_project(c, 0, a.tmax + 1, dr));
     const int rows = (a.tmax + 1) * B;
     a.inv_n = 1.0f / (float)ncount;
+    const bool dp = grad && c->comm; // a data-parallel step: rank weight from the exchange, loss partial into the closing one
+    a.wcur = dp ? a.dpw + 2 : a.dpw + 3;
+    a.loss_global = dp;
+    if (a.dp_wait) { // the count's all-reduce had the whole forward pass to finish
+        NVQA_HIP(hipStreamWaitEvent(c->s, c->evComm, 0));
+        a.dp_wait = false;
+    }
     {
         ProfScope ps(c, PF_AE_SOFTMAX, 0, (double)rows * a.ldl * 4 * (grad ? (a.p16 ? 2.5 : 3) : 1));
         if (a.p16 && grad)
             hipLaunchKernelGGL(k_ae_softmax<true>, dim3(rows), dim3(256), 0, c->s, a.logits, a.ldl, Vp1, a.tok, B, a.D, nvalid,
-                               1.0f / (float)ncount, 1, a.rowloss, a.G16, a.ld16, a.rowlse, a.rowtgt);
+                               1.0f / (float)ncount, a.wcur, 1, a.rowloss, a.G16, a.ld16, a.rowlse, a.rowtgt);
         else
             hipLaunchKernelGGL(k_ae_softmax<false>, dim3(rows), dim3(256), 0, c->s, a.logits, a.ldl, Vp1, a.tok, B, a.D, nvalid,
-                               1.0f / (float)ncount, grad ? 1 : 0, a.rowloss, (unsigned short *)nullptr, 0, (float *)nullptr,
+                               1.0f / (float)ncount, a.wcur, grad ? 1 : 0, a.rowloss, (unsigned short *)nullptr, 0, (float *)nullptr,
                                (int32_t *)nullptr);
-        hipLaunchKernelGGL(k_ae_loss, dim3(1), dim3(256), 0, c->s, a.rowloss, rows, 1.0f / (float)ncount, a.loss);
+        hipLaunchKernelGGL(k_ae_loss, dim3(1), dim3(256), 0, c->s, a.rowloss, rows, 1.0f / (float)ncount, a.wcur,
+                           dp ? c->dp_status + 2 : a.loss);
         NVQA_HIP(hipGetLastError());
     }
-    NVQA_HIP(hipMemcpyAsync(a.h_loss, a.loss, 4, hipMemcpyDeviceToHost, c->s));
+    if (!dp) NVQA_HIP(hipMemcpyAsync(a.h_loss, a.loss, 4, hipMemcpyDeviceToHost, c->s));
     return 0;
 }
 
@@ -1109,6 +1142,9 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
         NVQA_TRY(wgrad(c, a.logits, a.ldl, a.Htd, R, Vp1, R, rows, c->G + c->lo.w_proj));
         NVQA_TRY(colsum(c, a.logits, rows, Vp1, a.ldl, c->G + c->lo.b_proj, nullptr));
     }
+    // data parallel (no-ops without a communicator): W_proj | b_proj is final first and is the largest bucket but for the lookup
+    // table; it travels under the whole BPTT chain.  The LSTM slices follow layer by layer, the lookup table last (ae_step_impl joins).
+    NVQA_TRY(ae_comm_reduce(c, c->lo.w_proj, c->lo.b_proj + (size_t)Vp1 - c->lo.w_proj, 1));
     for (int l = L - 1; l >= 0; --l) {
         const int in = l == 0 ? E : R;
         NVQA_HIP(hipMemsetAsync(a.dc, 0, (size_t)B * R * 4, c->s));
@@ -1161,6 +1197,10 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
                                 c->G + (ph ? c->lo.d_b_h2h[l] : c->lo.b_h2h[l])));
             }
         }
+        if (!a.feats) { // this layer's slices of the decoder and the encoder segment, under the layers below / the lookup gradient
+            NVQA_TRY(ae_comm_reduce(c, c->lo.d_w_i2h[l], c->lo.d_b_h2h[l] + 4 * (size_t)R - c->lo.d_w_i2h[l], 3 + l));
+            NVQA_TRY(ae_comm_reduce(c, c->lo.w_i2h[l], c->lo.b_h2h[l] + 4 * (size_t)R - c->lo.w_i2h[l], 3 + l));
+        }
         if (l > 0) { // d(h of layer l-1) through the inter-layer Dropout: the external term of layer l-1's chain
             const size_t n = (size_t)Q * B * R;
             hipLaunchKernelGGL(k_ae_drop<false>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->s, a.dX, a.dHx,
@@ -1187,6 +1227,7 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
         hipLaunchKernelGGL(k_ae_lk_sum, dim3(nu), dim3(nt), 0, c->s, a.lk_tok, a.lk_tc, a.lk_part, E, c->G + c->lo.w_lk);
         NVQA_HIP(hipGetLastError());
     }
+    NVQA_TRY(ae_comm_reduce(c, c->lo.w_lk, (size_t)Vp1 * E, 2));
     return 0;
 }
 
@@ -1298,7 +1339,12 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *ima
     return 0;
 }
 
-float ae_last_loss(const nvqa_ctx *c) { return c->ae ? *c->ae->h_loss : 0.f; }
+// (a data-parallel step: the sum over the ranks of loss_r n_r world / N, over world = the global batch's loss)
+float ae_last_loss(const nvqa_ctx *c)
+{
+    if (!c->ae) return 0.f;
+    return c->ae->loss_global ? c->h_dp_status[2] * (1.0f / (float)c->world) : *c->ae->h_loss;
+}
 
 // AE2_WP part of nvqa_init_params: W_p = uniform(lo, hi) from the seed, b_p = 0 (build_cnn, misc/net_utils.lua:38-40), and a
 // fresh start of the projection's Adam
@@ -1374,8 +1420,22 @@ static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens,
     const Drop dr = ae_drop(dropout, true);
     int ncount = 0;
     NVQA_TRY(ae_upload(c, c->d.B, tokens, images, !c->ae->feats, &ncount, feats, enc_tokens, enc_state));
+    if (c->comm) {
+        // The ranks' criterion counts differ, and the mean of their means is not the global batch's mean: N = sum n_r is formed on
+        // the device, on the communication stream (idle: the last step joined it, and ae_upload has drained the compute stream, so
+        // nothing reads the old weight any more), under the forward pass.  No host ever sees another rank's count.
+        AeState &a = *c->ae;
+        hipLaunchKernelGGL(k_ae_set_count, dim3(1), dim3(1), 0, c->sc, a.dpw, (float)ncount);
+        NVQA_HIP(hipGetLastError());
+        NVQA_TRY(ae_comm_count(c, a.dpw));
+        hipLaunchKernelGGL(k_ae_rank_weight, dim3(1), dim3(1), 0, c->sc, a.dpw, (float)c->world);
+        NVQA_HIP(hipGetLastError());
+        NVQA_HIP(hipEventRecord(c->evComm, c->sc));
+        a.dp_wait = true;
+    }
     NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
     NVQA_TRY(ae_backward(c, dr, dfeats_out != nullptr));
+    NVQA_TRY(ae_comm_join(c));
     c->have_grads = true;
     if (dfeats_out) {
         NVQA_HIP(hipMemcpyAsync(dfeats_out, c->ae->dfeat, (size_t)c->d.B * c->d.I * 4, hipMemcpyDeviceToHost, c->s));
@@ -1385,7 +1445,7 @@ static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens,
         NVQA_HIP(hipMemcpyAsync(dimages_out, c->ae->dX, (size_t)c->d.B * c->d.E * 4, hipMemcpyDeviceToHost, c->s));
     if (loss_out || dimages_out) {
         NVQA_HIP(hipStreamSynchronize(c->s));
-        if (loss_out) *loss_out = *c->ae->h_loss;
+        if (loss_out) *loss_out = ae_last_loss(c);
     }
     return 0;
 }

@@ -2047,6 +2047,31 @@ extern "C" const char *nvqa_comm_library(void)
     return r ? r->resolved.c_str() : nullptr;
 }
 
+// the common end of nvqa_comm_init and nvqa_ae_comm_init: load the collective library, say once per process which one it is,
+// create the communicator and attach it to the context
+static int comm_attach(nvqa_ctx *c, int rank, int world, const void *id)
+{
+    const Rccl *r = load_rccl();
+    if (!r) return -1;
+    {
+        static bool said = false; // once per process: which collective library the data-parallel path runs on
+        if (!said && !env_int("NVQA_QUIET", 0)) {
+            fprintf(stderr, "[nvqa] rank %d/%d: collective library %s\n", rank, world, r->resolved.c_str());
+            said = true;
+        }
+    }
+    Id128 idv;
+    memcpy(idv.b, id, 128);
+    void *comm = nullptr;
+    const int rc = r->CommInitRank(&comm, world, idv, rank);
+    if (rc) { set_error("ncclCommInitRank: %s", r->GetErrorString ? r->GetErrorString(rc) : "?"); return -1; }
+    c->comm = comm;
+    c->rccl = r;
+    c->rank = rank;
+    c->world = world;
+    return 0;
+}
+
 extern "C" int nvqa_comm_init(nvqa_ctx *c, int rank, int world, const void *id)
 {
     if (!c || !id) { set_error("NULL argument"); return -1; }
@@ -2090,24 +2115,42 @@ extern "C" int nvqa_comm_init(nvqa_ctx *c, int rank, int world, const void *id)
             }
         }
     }
-    const Rccl *r = load_rccl();
-    if (!r) return -1;
-    {
-        static bool said = false; // once per process: which collective library the data-parallel path runs on
-        if (!said && !env_int("NVQA_QUIET", 0)) {
-            fprintf(stderr, "[nvqa] rank %d/%d: collective library %s\n", rank, world, r->resolved.c_str());
-            said = true;
-        }
+    return comm_attach(c, rank, world, id);
+}
+
+// Data parallel for the text auto-encoders (NVQA_ARCH_AE1 / NVQA_ARCH_AE2).  A call of its own, as
+// nvqa_ae_set_precision is: nvqa_comm_init stays refused on every auto-encoder context.  An auto-encoder context holds one stream
+// (ae_create), so the communication stream, the events and the status words of the VQA exchange are made here, on first use.
+extern "C" int nvqa_ae_comm_init(nvqa_ctx *c, int rank, int world, const void *id)
+{
+    if (!c || !id) { set_error("NULL argument"); return -1; }
+    if (c->d.arch != NVQA_ARCH_AE1 && c->d.arch != NVQA_ARCH_AE2) {
+        if (is_ae(c->d))
+            set_error("nvqa_ae_comm_init: not available on a weak-paired auto-encoder context (arch %d): at the scripts' batch sizes "
+                      "of 16 - 20 rows the step is bound by its launches", c->d.arch);
+        else
+            set_error("nvqa_ae_comm_init: an NVQA_ARCH_AE1 / NVQA_ARCH_AE2 context expected (arch %d); the VQA step's call is nvqa_comm_init", c->d.arch);
+        return -1;
     }
-    Id128 idv;
-    memcpy(idv.b, id, 128);
-    void *comm = nullptr;
-    const int rc = r->CommInitRank(&comm, world, idv, rank);
-    if (rc) { set_error("ncclCommInitRank: %s", r->GetErrorString ? r->GetErrorString(rc) : "?"); return -1; }
-    c->comm = comm;
-    c->rccl = r;
-    c->rank = rank;
-    c->world = world;
+    if (world < 1 || rank < 0 || rank >= world) { set_error("bad rank/world %d/%d", rank, world); return -1; }
+    if (c->comm) { set_error("nvqa_ae_comm_init: the context already has a communicator"); return -1; }
+    NVQA_HIP(hipSetDevice(c->device));
+    if (!c->sc) NVQA_HIP(hipStreamCreateWithFlags(&c->sc, hipStreamNonBlocking));
+    for (int i = 0; i < 3 + NVQA_MAX_LAYERS; ++i)
+        if (!c->evSeg[i]) NVQA_HIP(hipEventCreateWithFlags(&c->evSeg[i], hipEventDisableTiming));
+    if (!c->evComm) NVQA_HIP(hipEventCreateWithFlags(&c->evComm, hipEventDisableTiming));
+    if (!c->dp_status) {
+        NVQA_TRY(dalloc(&c->dp_status, 4));
+        NVQA_HIP(hipMemset(c->dp_status, 0, 16));
+    }
+    if (!c->h_dp_status) {
+        NVQA_HIP(hipHostMalloc((void **)&c->h_dp_status, 4 * sizeof(float), hipHostMallocDefault));
+        memset(c->h_dp_status, 0, 16);
+    }
+    NVQA_TRY(comm_attach(c, rank, world, id));
+    // The auto-encoder step never sets a status word (it has no persistent launch), so the words do not alternate: word 1 is this
+    // context's, for good, and word 2 behind it carries the loss partial through the same closing all-reduce (ae_comm_join).
+    c->dp_slot = 1;
     return 0;
 }
 
@@ -2151,6 +2194,38 @@ static int reduce_join(nvqa_ctx *c)
         if (rc) { set_error("ncclAllReduce (status): %s", r->GetErrorString ? r->GetErrorString(rc) : "?"); return -1; }
         NVQA_HIP(hipMemcpyAsync(c->h_dp_status, c->dp_status + c->dp_slot, 4, hipMemcpyDeviceToHost, c->sc)); // this step's word only: word 1 of the host copy is k_rmsprop's sticky count
     }
+    NVQA_HIP(hipEventRecord(c->evComm, c->sc));
+    NVQA_HIP(hipStreamWaitEvent(c->s, c->evComm, 0));
+    return 0;
+}
+
+// ae.hip's side of the exchange (the loader and the communicator live in this file)
+int nvqa::ae_comm_reduce(nvqa_ctx *c, size_t off, size_t count, int ev) { return reduce_range(c, off, count, ev); }
+
+// The step's first collective: n_r -> N = sum of the ranks' criterion counts, then w_r = n_r world / N (k_ae_rank_weight's
+// launch is the caller's, behind this on the communication stream).  cnt[0] = n_r (written on the communication stream by the
+// caller), cnt[1] = N.
+int nvqa::ae_comm_count(nvqa_ctx *c, float *cnt)
+{
+    const Rccl *r = rccl_of(c);
+    const int rc = r->AllReduce(cnt, cnt + 1, 1, /*ncclFloat32*/ 7, /*ncclSum*/ 0, c->comm, c->sc);
+    if (rc) { set_error("ncclAllReduce (count): %s", r->GetErrorString ? r->GetErrorString(rc) : "?"); return -1; }
+    return 0;
+}
+
+// reduce_join for the auto-encoder step: the closing all-reduce carries two floats, the status word (dp_status[1], always zero
+// here, read by k_adam / k_rmsprop as ever) and the rank's loss partial loss_r w_r (dp_status[2]); their sums go to the host copy's
+// words 0 and 2 (word 1 is the update kernels' sticky count).
+int nvqa::ae_comm_join(nvqa_ctx *c)
+{
+    if (!c->comm) return 0;
+    NVQA_HIP(hipEventRecord(c->evSeg[0], c->s));
+    NVQA_HIP(hipStreamWaitEvent(c->sc, c->evSeg[0], 0));
+    const Rccl *r = rccl_of(c);
+    const int rc = r->AllReduce(c->dp_status + 1, c->dp_status + 1, 2, /*ncclFloat32*/ 7, /*ncclSum*/ 0, c->comm, c->sc);
+    if (rc) { set_error("ncclAllReduce (status, loss): %s", r->GetErrorString ? r->GetErrorString(rc) : "?"); return -1; }
+    NVQA_HIP(hipMemcpyAsync(c->h_dp_status, c->dp_status + 1, 4, hipMemcpyDeviceToHost, c->sc));
+    NVQA_HIP(hipMemcpyAsync(c->h_dp_status + 2, c->dp_status + 2, 4, hipMemcpyDeviceToHost, c->sc));
     NVQA_HIP(hipEventRecord(c->evComm, c->sc));
     NVQA_HIP(hipStreamWaitEvent(c->s, c->evComm, 0));
     return 0;

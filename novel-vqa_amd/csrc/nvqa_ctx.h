@@ -18,6 +18,11 @@ int ae_create(nvqa_ctx *c);  // ae.hip: the buffers of an NVQA_ARCH_AE1 / AE2 / 
 void ae_destroy(nvqa_ctx *c);
 float ae_last_loss(const nvqa_ctx *c); // loss of the last nvqa_ae_step / nvqa_ae_evaluate (after a synchronisation)
 int ae_wp_init(nvqa_ctx *c, uint64_t seed, float lo, float hi); // NVQA_ARCH_AE2_WP: the projection's part of nvqa_init_params
+// nvqa_api.hip: the auto-encoder step's collectives (nvqa_ae_comm_init; no-ops but ae_comm_count without a communicator).
+// ae_comm_reduce: all-reduce of G[off, off + count) on the communication stream behind event evSeg[ev] of the compute stream
+int ae_comm_reduce(nvqa_ctx *c, size_t off, size_t count, int ev);
+int ae_comm_count(nvqa_ctx *c, float *cnt); // cnt[1] = sum over the ranks of cnt[0], on the communication stream
+int ae_comm_join(nvqa_ctx *c);              // closing exchange {status word, loss partial}; the compute stream waits for it
 // nvqa_api.hip: k_l2norm_rows (kernels.h) over rows [0, n) of F [n x I] in place (the weak-paired auto-encoder's features)
 int l2norm_rows_launch(hipStream_t s, float *F, int n, int I);
 

@@ -15,9 +15,13 @@ from . import binding, h5, t7
 
 class DataLoader:
     """misc/DataLoader.lua: sentences of `labels/<split>` ([N x D], 0 = null), iterated in order.
-    `labels` may be given directly as {split: array} instead of an h5 file; ix_to_word comes from the json file."""
+    `labels` may be given directly as {split: array} instead of an h5 file; ix_to_word comes from the json file.
+    rank / world (data parallel): get_batch draws rank-disjoint sentences, see there."""
 
-    def __init__(self, h5_file=None, json_file=None, labels=None, ix_to_word=None):
+    def __init__(self, h5_file=None, json_file=None, labels=None, ix_to_word=None, rank=0, world=1):
+        self.rank, self.world = int(rank), int(world)
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f"rank {rank} outside 0..{world - 1}")
         if labels is None:
             with h5.File(h5_file) as f:
                 labels = {s: np.asarray(f.read(f"labels/{s}")) for s in ("train", "val", "test") if self._has(f, s)}
@@ -43,10 +47,20 @@ class DataLoader:
     def reset_iterator(self, split):
         self.iterators[split] = 1
 
-    def get_batch(self, split, batch_size):
+    def get_batch(self, split, batch_size, rank_stride=True):
         """getBatch (:58-89).  Returns (labels [batch_size x D], bounds dict(it_pos_now, it_max, wrapped)).
         On a wrap the rows up to the split's end are followed by the split's first rows and the iterator goes back to 1,
-        so the next batch starts with those first rows again (the reference's behaviour, kept)."""
+        so the next batch starts with those first rows again (the reference's behaviour, kept).
+        world > 1: the iterator walks the split in strides of world * batch_size rows, as one process with that batch would,
+        and this rank gets rows [rank * batch_size, (rank + 1) * batch_size) of each stride: the ranks' batches are disjoint,
+        their union is the single-process batch, and every rank wraps in the same iteration.  rank_stride=False walks the split
+        as a single process does, the same rows on every rank (AETrainer.eval_split)."""
+        if self.world > 1 and rank_stride:
+            rows, bounds = self._global_batch(split, batch_size * self.world)
+            return rows[self.rank * batch_size:(self.rank + 1) * batch_size].copy(), bounds
+        return self._global_batch(split, batch_size)
+
+    def _global_batch(self, split, batch_size):
         data = self.labels[split]
         max_index = data.shape[0]
         it = self.iterators[split]
@@ -90,11 +104,14 @@ class AETrainer:
     """The training script's loop on the library: ae_step (lossFun), the log line, the learning-rate decay and the
     Adam (or RMSprop) update.  dims: binding.Dims with arch = ARCH_AE1 or ARCH_AE2, T = seq_length, I = C = A = 0
     (the arch2 script forces 1 layer, :104; the library takes any L).  learning_rate None: the script's default.
-    bf16: the step's bf16 operand mode (Context.ae_set_precision), for either arch."""
+    bf16: the step's bf16 operand mode (Context.ae_set_precision), for either arch.
+    rank (data parallel, comm_init): the parameters come from `seed` on every rank (identical replicas), the dropout masks
+    from seed + 1000 * rank, as in VQATrainer; dims.B is the batch per rank.  With a communicator the log line's loss,
+    # updates and paramsNorm are the global values, so every rank prints the same line."""
 
     def __init__(self, dims, device=0, learning_rate=None, learning_rate_decay_start=-1, learning_rate_decay_every=50000,
                  optim="adam", optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6, grad_clip=0.1,
-                 drop_prob=0.5, seed=123, bf16=False):
+                 drop_prob=0.5, seed=123, bf16=False, rank=0):
         if dims.arch not in ARCH_DEFAULTS:
             raise ValueError("AETrainer needs dims.arch = ARCH_AE1 (3) or ARCH_AE2 (4)")
         if learning_rate is None:
@@ -109,11 +126,20 @@ class AETrainer:
         self.alpha, self.beta, self.eps = optim_alpha, optim_beta, optim_epsilon
         self.weight_decay, self.grad_clip = weight_decay, grad_clip
         self.drop_prob, self.seed = drop_prob, seed
+        self.rank, self.world = int(rank), 1
+        self.dropout_seed = seed + 1000 * self.rank  # ranks hold different sentences: identical masks would correlate them
         self.iter = 1
         self.bf16 = bool(bf16)
         self.ctx.init_params(seed, -0.08, 0.08)
         if self.bf16:  # bf16 operands for every dense product of the step and of eval_split (nvqa_ae_set_precision)
             self.ctx.ae_set_precision(1)
+
+    def comm_init(self, rank, world, comm_id):
+        """Join a data-parallel job (Context.ae_comm_init); rank must be the constructor's, which seeded the dropout masks."""
+        if rank != self.rank:
+            raise ValueError(f"comm_init(rank={rank}) on a trainer built with rank={self.rank}")
+        self.ctx.ae_comm_init(rank, world, comm_id)
+        self.world = int(world)
 
     def current_lr(self):
         """:342-347"""
@@ -124,7 +150,7 @@ class AETrainer:
 
     def train_step(self, tokens):
         """lossFun + log line + update of one iteration; returns (loss, # updates, paramsNorm, the log line)."""
-        dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.seed, self.iter)
+        dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.dropout_seed, self.iter)
         loss = self.ctx.ae_step(tokens, dr)
         lr = self.current_lr()
         if self.optim == "adam":
@@ -154,13 +180,18 @@ class AETrainer:
         val_sentences_use > 0) once that many sentences were used; predictions are the greedy decodes through ix_to_word.
         (The arch1 reference's counter `n` is never incremented there, so only the wrap ends its loop.)
         ARCH_AE2 (001_train_arch2_text_autoencoder.lua:192-195): n grows by batch_size after every batch and the loop
-        ends once n >= val_sentences_use, so a non-positive val_sentences_use evaluates one batch, as there."""
+        ends once n >= val_sentences_use, so a non-positive val_sentences_use evaluates one batch, as there.
+        Data parallel: evaluation is rank-local (no collective) and walks the split without the rank stride, so with a
+        DataLoader(rank=r, world=n) every rank evaluates the same rows and reports the same loss, as the Lua twins do."""
         loader.reset_iterator(split)
         losses, preds, used, n = [], [], 0, 0
         end = self.dims.V + 1
         ae2 = self.dims.arch == binding.ARCH_AE2
         while True:
-            batch, bounds = loader.get_batch(split, self.dims.B)
+            if getattr(loader, "world", 1) > 1:
+                batch, bounds = loader.get_batch(split, self.dims.B, rank_stride=False)
+            else:
+                batch, bounds = loader.get_batch(split, self.dims.B)
             loss, samples = self.ctx.ae_evaluate(batch, samples=True)
             losses.append(loss)
             for p, a in zip(decode_sequence(loader.ix_to_word, samples, end), decode_sequence(loader.ix_to_word, batch, end)):

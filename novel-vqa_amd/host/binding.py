@@ -82,6 +82,7 @@ SYMBOLS = {
     "nvqa_ae_step_images": (ctypes.c_int, [_vp, _f32p, _i32p, ctypes.POINTER(Dropout), _f32p, _f32p]),
     "nvqa_ae_evaluate_images": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _f32p, _i32p]),
     "nvqa_ae_set_precision": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "nvqa_ae_comm_init": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "nvqa_adam_update": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_ae_wp_step": (ctypes.c_int, [_vp, _f32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_wp_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _i32p, _f32p, _i32p]),
@@ -304,6 +305,13 @@ class Context:
         f32 accumulate; 0 = f32.  (set_precision(1) stays refused on an auto-encoder context; this one is refused on the
         weak-paired and the VQA contexts.)"""
         self._check(self.lib.nvqa_ae_set_precision(self._h, int(bf16)))
+
+    def ae_comm_init(self, rank, world, comm_id):
+        """nvqa_ae_comm_init: data parallel for an ARCH_AE1 / ARCH_AE2 context; comm_id from comm_unique_id() of rank 0.
+        Afterwards ae_step ends with the global batch's gradient and loss, the ranks' gradients weighted by their criterion
+        counts (comm_init stays refused on an auto-encoder context; this one is refused on the weak-paired and VQA contexts)."""
+        buf = ctypes.create_string_buffer(bytes(comm_id), COMM_ID_BYTES)
+        self._check(self.lib.nvqa_ae_comm_init(self._h, rank, world, ctypes.cast(buf, _vp)))
 
     def adam_update(self, lr, beta1=0.8, beta2=0.999, eps=1e-8, wd=0.0, clamp=0.0, stats=False):
         """clamp -> + wd x -> adam in one pass; stats=True returns (paramsNorm, # updates) of the log line."""

@@ -64,6 +64,7 @@ int nvqa_ae_step_images(nvqa_ctx *ctx, const float *images, const int32_t *token
 int nvqa_ae_evaluate_images(nvqa_ctx *ctx, int32_t n, const float *images, const int32_t *tokens, float *loss_out,
                             int32_t *samples_out);
 int nvqa_ae_set_precision(nvqa_ctx *ctx, int bf16);
+int nvqa_ae_comm_init(nvqa_ctx *ctx, int rank, int world, const void *id);
 int nvqa_adam_update(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                      float stats_out[2]);
 int nvqa_ae_wp_step(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,

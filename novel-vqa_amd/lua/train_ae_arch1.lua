@@ -8,6 +8,15 @@ NVQA_ARCH_AE1 (include/nvqa.h).  Instead of the thin nn checkpoint it writes the
 002_convert_text_model_arch1.lua makes ({lookup = W_lk^T, encoder}) plus layout = 'nvqa', which train_arch1_ae.lua reads
 without -encoder_perm.  Needs LuaJIT + torch + hdf5 + cjson; NOT executable in the build image, where
 novel-vqa_amd/host/ae.py (AETrainer) is the executed twin.
+
+Data parallel (absent in the reference): -world N -rank r -comm_id_file F runs one process per GPU (nvqa_ae_comm_init).
+Rank 0 writes the 128-byte communicator id to F, the others wait for it and read it; -batch_size is the batch PER RANK, the
+training iterator walks strides of world * batch_size rows of which rank r takes its block, the dropout masks come from
+seed + 1000 * rank, and the step ends with the global batch's gradient and loss, so every rank prints the same log line.
+Validation is rank-local over the same rows on every rank; rank 0 alone writes the export tables.  -world 1 (the default)
+creates no communicator.  F must not exist when the job starts: a rank above 0 reads it as soon as it is there, and an id left by
+an earlier run would make ncclCommInitRank wait for ranks that never come.  Rank 0 removes a stale F first thing, before it
+loads the data, and removes its own F again when the communicator stands; start rank 0 first, or use a fresh name per job.
 ]]--
 require 'torch'
 require 'hdf5'
@@ -40,7 +49,12 @@ cmd:option('-id', '', 'an id identifying this run/job')
 cmd:option('-seed', 123, 'random number generator seed to use')
 cmd:option('-gpuid', 0, 'which MI355X to use')
 cmd:option('-bf16', 0, '1 = bf16 operands for every dense product of the step, f32 accumulate (nvqa_ae_set_precision)')
+cmd:option('-rank', 0, 'data parallel: this process\'s rank, 0 .. world - 1')
+cmd:option('-world', 1, 'data parallel: number of processes (1 = no communicator)')
+cmd:option('-comm_id_file', '', 'data parallel: file through which rank 0 hands the communicator id to the other ranks')
 opt = cmd:parse(arg)
+assert(opt.world >= 1 and opt.rank >= 0 and opt.rank < opt.world, 'bad -rank / -world')
+if opt.world > 1 and opt.rank == 0 and opt.comm_id_file ~= '' then os.remove(opt.comm_id_file) end  -- a stale id of an earlier run
 torch.manualSeed(opt.seed)
 
 -- data (misc/DataLoader.lua:6-31) ------------------------------------------------------------------------------------
@@ -80,6 +94,24 @@ local ctx = nvqa.create(3, opt, vocab_size, seq_length, opt.gpuid)
 nvqa.check(nvqa.lib.nvqa_init_params(ctx, opt.seed, -0.08, 0.08))
 nvqa.check(nvqa.lib.nvqa_ae_set_precision(ctx, opt.bf16))
 local n_params = tonumber(nvqa.lib.nvqa_param_count(ctx))
+if opt.world > 1 then                               -- the parameters above came from -seed on every rank: identical replicas
+  assert(opt.comm_id_file ~= '', '-world > 1 needs -comm_id_file')
+  local id = ffi.new('char[128]')
+  if opt.rank == 0 then
+    nvqa.check(nvqa.lib.nvqa_comm_unique_id(id))
+    local fh = assert(io.open(opt.comm_id_file .. '.tmp', 'wb')); fh:write(ffi.string(id, 128)); fh:close()
+    assert(os.rename(opt.comm_id_file .. '.tmp', opt.comm_id_file))
+  else
+    local fh = io.open(opt.comm_id_file, 'rb')
+    while not fh do os.execute('sleep 0.1'); fh = io.open(opt.comm_id_file, 'rb') end
+    local bytes = fh:read(128); fh:close()
+    assert(bytes and #bytes == 128, 'short communicator id in ' .. opt.comm_id_file)
+    ffi.copy(id, bytes, 128)
+  end
+  nvqa.check(nvqa.lib.nvqa_ae_comm_init(ctx, opt.rank, opt.world, id))
+  if opt.rank == 0 then os.remove(opt.comm_id_file) end  -- every rank has read it: ncclCommInitRank returns when all have joined
+end
+local dropout_seed = opt.seed + 1000 * opt.rank     -- ranks hold different sentences: identical masks would correlate them
 
 local function eval_split(split)                    -- eval_split (:148-194): mean of the per-batch losses
   iterators[split] = 1
@@ -95,6 +127,7 @@ local function eval_split(split)                    -- eval_split (:148-194): me
 end
 
 local function export(path)                          -- 002_convert_text_model_arch1.lua:27-39 + layout = 'nvqa'
+  if opt.rank ~= 0 then return end                   -- identical replicas: one writer
   local x = torch.FloatTensor(n_params)
   nvqa.check(nvqa.lib.nvqa_get_params(ctx, nvqa.fptr(x)))
   local seg = ffi.new('size_t[3]'); nvqa.check(nvqa.lib.nvqa_segments(ctx, seg))
@@ -107,8 +140,9 @@ end
 local iter, loss0 = 1, nil
 local loss, stats = ffi.new('float[1]'), ffi.new('float[2]')
 while true do
-  local batch = getBatch('train', opt.batch_size)
-  nvqa.check(nvqa.lib.nvqa_ae_step(ctx, nvqa.iptr(batch), nvqa.dropout(1, opt.drop_prob_ae, opt.seed, iter), loss))
+  local batch = getBatch('train', opt.batch_size * opt.world)
+  if opt.world > 1 then batch = batch:narrow(1, opt.rank * opt.batch_size + 1, opt.batch_size):contiguous() end
+  nvqa.check(nvqa.lib.nvqa_ae_step(ctx, nvqa.iptr(batch), nvqa.dropout(1, opt.drop_prob_ae, dropout_seed, iter), loss))
   local learning_rate = opt.learning_rate
   if iter > opt.learning_rate_decay_start and opt.learning_rate_decay_start >= 0 then
     local frac = (iter - opt.learning_rate_decay_start) / opt.learning_rate_decay_every

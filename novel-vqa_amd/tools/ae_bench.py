@@ -16,8 +16,14 @@ nvqa_ae1_wp_step on the same features, the encoder skipped (enc_state = one vect
 reference shape is --B 16 --null-share 0.5 (inc: --B 10 --I 2048).
 --bf16 (--arch 1 | 2): the step's bf16 operand mode (nvqa_ae_set_precision); the line then carries "bf16": 1 and the step's
 fraction of the bf16 MFMA roofline as well.
+--world N (--arch 1 | 2): data parallel (nvqa_ae_comm_init) as ONE process, rank 0 of N, on whatever collective library
+NVQA_RCCL_LIB names -- on a one-GPU machine the stand-in tests/shim/libnccl_shim.so, whose all-reduce returns N x send
+(NCCL_SHIM_CUS = n gives it the footprint and the duration of a collective over 150 GB/s links); any other library is
+refused, since a real one would wait for the N - 1 ranks this tool never starts.  A second context of the same
+shape without a communicator is timed in the same job, the two alternating block by block; the line carries both
+("ms_per_step" without, "ms_per_step_world" with the communicator), their difference and the communicator context's profile.
 
-    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--bf16] [--I 4096 --null-share 0.5]
+    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--bf16] [--I 4096 --null-share 0.5] [--world N]
                                            [--blocks 5 --steps 10 --warmup 5] [--out FILE]
 """
 import argparse
@@ -66,8 +72,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--bf16", action="store_true")
+    ap.add_argument("--world", type=int, default=1)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.world < 1 or (a.world > 1 and a.arch not in (1, 2)):
+        ap.error("--world: data parallel is for --arch 1 | 2 (the weak-paired contexts refuse a communicator)")
     if a.bf16 and a.arch not in (1, 2):
         ap.error("--bf16: the weak-paired auto-encoders have no bf16 operand mode")
     pkg = ge.load_package()
@@ -87,6 +96,21 @@ def main():
         ctx.set_params(x)
         ctx.ae1_wp_set_lookup(np.random.default_rng(2).uniform(-0.08, 0.08, (a.V + 1, a.E)).astype(np.float32))
         enc_state = np.tile(np.random.default_rng(3).uniform(-0.5, 0.5, 2 * a.R).astype(np.float32), (a.B, 1))
+    ctxw = None
+    if a.world > 1:  # the same shape and parameters with a communicator: rank 0 of --world
+        ctxw = b.Context(dims, 0)
+        # one process is one rank: a real collective library would wait in ncclCommInitRank for world - 1 ranks that never come
+        import ctypes
+        lib_path = ctxw.comm_library()
+        if not hasattr(ctypes.CDLL(lib_path), "nccl_shim_calls"):
+            ctxw.close()
+            ctx.close()
+            sys.exit(f"--world {a.world}: {lib_path} is not the one-process stand-in (tests/shim/libnccl_shim.so); set "
+                     "NVQA_RCCL_LIB to it -- with a real collective library this single rank would hang waiting for the others")
+        ctxw.init_params(123, -0.08, 0.08)
+        if a.bf16:
+            ctxw.ae_set_precision(1)
+        ctxw.ae_comm_init(0, a.world, ctxw.comm_unique_id())
     rng = np.random.default_rng(0)
     batches = []
     for _ in range(8):
@@ -105,7 +129,7 @@ def main():
     null = np.random.default_rng(1).random(4096) < a.null_share
     it = [0]
 
-    def one_step():
+    def one_step(ctx=ctx):
         it[0] += 1
         k = it[0] % len(batches)
         dr = b.Dropout(1, 0.5, 123, it[0])
@@ -121,16 +145,22 @@ def main():
             ctx.ae_step(batches[k], dr, want_loss=False)
         ctx.adam_update(lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
 
-    for _ in range(a.warmup):
-        one_step()
-    ctx.sync()
-    block_ms = []
-    for _ in range(a.blocks):
+    def timed_block(c):
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            one_step()
-        ctx.sync()
-        block_ms.append((time.perf_counter() - t0) * 1e3 / a.steps)
+            one_step(c)
+        c.sync()
+        return (time.perf_counter() - t0) * 1e3 / a.steps
+
+    for c in (ctx, ctxw) if ctxw else (ctx,):
+        for _ in range(a.warmup):
+            one_step(c)
+        c.sync()
+    block_ms, block_ms_world = [], []
+    for _ in range(a.blocks):  # (--world: the two contexts alternate, so that drift hits both alike)
+        block_ms.append(timed_block(ctx))
+        if ctxw:
+            block_ms_world.append(timed_block(ctxw))
     ms = float(np.median(block_ms))
     timed = range(a.warmup + 1, a.warmup + a.blocks * a.steps + 1)  # the iteration numbers of the timed steps
     if a.arch == 5:
@@ -140,20 +170,34 @@ def main():
     else:
         loss = ctx.ae_step(batches[0], b.Dropout(1, 0.5, 123, 0))
     # profiled pass (events around every launch group: slower, reported per group only)
-    ctx.profile_enable(True)
-    for _ in range(3):
-        one_step()
-    ctx.sync()
-    ctx.profile_reset()
     nprof = 5
-    for _ in range(nprof):
-        one_step()
-    ctx.sync()
-    prof = {k: {"ms_per_step": v["ms"] / nprof, "launches_per_step": v["launches"] / nprof,
-                "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["flops"] > 0 and v["ms"] > 0 else None,
-                "gb_s": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["bytes"] > 0 and v["ms"] > 0 else None}
-            for k, v in ctx.profile().items() if v["launches"] > 0}
-    ctx.profile_enable(False)
+
+    def profiled(c):
+        c.profile_enable(True)
+        for _ in range(3):
+            one_step(c)
+        c.sync()
+        c.profile_reset()
+        for _ in range(nprof):
+            one_step(c)
+        c.sync()
+        out = {k: {"ms_per_step": v["ms"] / nprof, "launches_per_step": v["launches"] / nprof,
+                   "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["flops"] > 0 and v["ms"] > 0 else None,
+                   "gb_s": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["bytes"] > 0 and v["ms"] > 0 else None}
+               for k, v in c.profile().items() if v["launches"] > 0}
+        c.profile_enable(False)
+        return out
+
+    prof = profiled(ctx)
+    world_part = {}
+    if ctxw:
+        msw = float(np.median(block_ms_world))
+        world_part = {"world": a.world, "comm_library": ctxw.comm_library(), "ms_per_step_world": round(msw, 4),
+                      "block_ms_world": [round(x, 4) for x in block_ms_world],
+                      "exchange_exposed_ms": round(msw - ms, 4),
+                      "exchanged_mbytes_per_step": round(4e-6 * ctxw.param_count, 2),
+                      "loss_world": ctxw.ae_step(batches[0], b.Dropout(1, 0.5, 123, 0)), "profile_world": profiled(ctxw)}
+        ctxw.close()
     ctx.close()
     tmaxes = [int(np.nonzero(t.any(0))[0][-1]) + 1 for t in batches]
     if a.arch == 5:  # the timed steps' own batches and encoder lengths
@@ -171,6 +215,7 @@ def main():
             "tflop_per_step": round(fl / 1e12, 4), "achieved_tflops": round(fl / (ms * 1e-3) / 1e12, 2),
             "fraction_of_f32_mfma_peak": round(fl / (ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
             "profile": prof}
+    line.update(world_part)
     if a.bf16:
         line.update(bf16=1, fraction_of_bf16_mfma_peak=round(fl / (ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4))
     if a.arch in (5, 6):
