@@ -21,6 +21,9 @@
  *   nvqa_forward                   eval-mode forward + argmax      004_eval_model.lua:202-233
  *   nvqa_dataset_load /            dataset[...] tensors + dataset:next_batch() gather
  *   nvqa_step_indices              002_train_baseline.lua:93-121,195-222
+ *   nvqa_ae_corpus_load /          the label tensors of misc/DataLoader.lua + its linear walk (getBatch): the text
+ *   nvqa_ae_step_rows /            auto-encoders' corpus resident in HBM, a step named by B row ids
+ *   nvqa_ae_evaluate_rows          001_train_autoencoder/misc/DataLoader.lua
  *   nvqa_comm_*                    (absent in the reference: data-parallel gradient all-reduce)
  *
  * Conventions: plain C, POD arguments only.  All pointers are caller-owned
@@ -250,7 +253,7 @@ int nvqa_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const float *images, const in
 
 /* ---- text auto-encoder (NVQA_ARCH_AE1 / NVQA_ARCH_AE2 contexts) ---- */
 /* On an auto-encoder context nvqa_step*, nvqa_forward, nvqa_evaluate, nvqa_set_fusion, nvqa_set_ref_quirks,
- * nvqa_dataset_load, nvqa_comm_init (data parallel: nvqa_ae_comm_init, below) and nvqa_set_precision(ctx, 1) return an error.
+ * nvqa_dataset_load (the resident corpus: nvqa_ae_corpus_load, below), nvqa_comm_init (data parallel: nvqa_ae_comm_init, below) and nvqa_set_precision(ctx, 1) return an error.
  * One training forward + LanguageModelCriterion + backward (lossFun of 001_train_arch1_text_autoencoder.lua:212-245):
  * tokens [B x D] left-aligned, 1..V, 0 = null.  Gradients stay on the device (nvqa_get_grads, nvqa_adam_update,
  * nvqa_rmsprop_update); *loss_out (may be NULL) = the criterion's mean over the positions that carry a loss. */
@@ -301,6 +304,21 @@ int nvqa_ae_set_precision(nvqa_ctx *ctx, int bf16);
  * before its collectives were issued (an all-null batch, a token outside 0..V), the other ranks block in the count's
  * all-reduce: treat a step error on any rank as fatal for the whole job. */
 int nvqa_ae_comm_init(nvqa_ctx *ctx, int rank, int world, const void *id);
+/* The resident corpus of NVQA_ARCH_AE1 / NVQA_ARCH_AE2 contexts: the text scripts walk a corpus that
+ * never changes, so it lives in HBM and a step is named by B row ids.  An error on a VQA context and on the weak-paired contexts.
+ * nvqa_ae_corpus_load: tokens [n_rows x D], 0..V, 0 = null, left-aligned as nvqa_ae_step takes them; every token is checked
+ * before any device state is touched.  A failed load leaves a previously loaded corpus in place; a successful one replaces it
+ * (after the context's stream has drained). */
+int nvqa_ae_corpus_load(nvqa_ctx *ctx, int64_t n_rows, const int32_t *tokens);
+/* nvqa_ae_step on rows[0..B) of the corpus (0-based; any order, repeats allowed): the same kernels on the same lookup index, which
+ * is built on the device, so loss, gradients and updates equal nvqa_ae_step on the gathered rows bit for bit.  AE2: zero image
+ * rows, as the text script feeds.  With loss_out = NULL and no communicator the call only enqueues: it waits for nothing on the
+ * device.  With a communicator (nvqa_ae_comm_init) it is nvqa_ae_step's collective step, and the two may be mixed freely. */
+int nvqa_ae_step_rows(nvqa_ctx *ctx, const int64_t *rows, const nvqa_dropout *dropout, float *loss_out);
+/* nvqa_ae_evaluate on rows[0..n) of the corpus, n <= B */
+int nvqa_ae_evaluate_rows(nvqa_ctx *ctx, int32_t n, const int64_t *rows, float *loss_out, int32_t *samples_out);
+/* out[0] = training steps fed from host tokens so far (nvqa_ae_step*), out[1] = training steps fed from the resident corpus */
+int nvqa_ae_step_routes(const nvqa_ctx *ctx, int64_t out[2]);
 /* ---- weak-paired auto-encoder (NVQA_ARCH_AE2_WP contexts) ---- */
 /* 004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua with misc/AutoEncoderNull.lua.  The CNN body is frozen and runs
  * outside: feats [B x I] are its output (vgg: post-ReLU fc7 as nvqa_vgg16_fc7 returns it, I = 4096; inc: I = 2048).  The

@@ -38,6 +38,7 @@
 // n_r world / N read from device memory (N = the ranks' summed criterion counts, exchanged under the forward pass), and the
 // backward pass hands each bucket of the gradient to the communication stream as soon as it is final.
 #include <math.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -128,6 +129,20 @@ struct AeState {
     size_t slab_floats = 0;
     float *colpart = nullptr;   // column-sum partials
     size_t colpart_floats = 0;
+    // the resident corpus of AE1 / AE2 (nvqa_ae_corpus_load): tokens on the device, and per row on the host
+    // what the launch plan of a step needs -- no step reads a token back
+    int32_t *corpus = nullptr;         // [corpus_rows x D] (device)
+    int64_t corpus_rows = 0;
+    std::vector<uint16_t> row_last;    // 1 + the row's last non-null column (0: a null row): tmax of a batch = their max
+    std::vector<uint16_t> row_cnt;     // the row's criterion count = its non-null tokens + 1
+    int32_t *lk_hist = nullptr;        // [QM][V + 2] rows per (chain step, token) of the device index build, zeroed per step
+    int32_t *lk_base = nullptr;        // [QM][V + 2] a token's rows in the chain steps before q
+    int32_t *lk_tot = nullptr;         // [V + 2] a token's rows, then (k_ae_lk_scan) the token's first slot of lk_pos
+    int32_t *lk_chb = nullptr;         // [V + 2] the token's first chunk
+    int32_t *lk_cnt = nullptr;         // {nu, nch} of the device-built index
+    bool lk_dev = false;               // the current step's index was built on the device: nu / nch are lk_cnt's, not h_lk's
+    hipEvent_t step_ev = nullptr;      // data parallel: the compute stream's position at the start of a resident step
+    int64_t routes[2] = {0, 0};        // training steps fed from host tokens / from the resident corpus (nvqa_ae_step_routes)
 };
 
 static int ae_alloc(void **p, size_t bytes)
@@ -526,9 +541,11 @@ __global__ void k_ae_slab_sum(const float *slabs, int Z, size_t n, float *out)
 // token summing all its rows serially took 13 ms at the default shape: the START token alone has B rows, the padding
 // token 1 thousands.)  Rows of tokens absent from the batch were zeroed by the caller.
 #define NVQA_AE_LK_CHUNK 16
+// cnt (the device-built index of a resident step): the launch's grid is an upper bound, workgroups past *cnt return
 __global__ void k_ae_lk_part(const int32_t *lk_start, const int32_t *lk_pos, const float *X0, const float *dX, int B, int D,
-                             int E, int tmax, Drop dr, float *part)
+                             int E, int tmax, Drop dr, float *part, const int32_t *cnt)
 {
+    if (cnt && (int)blockIdx.x >= cnt[0]) return;
     const int p0 = lk_start[blockIdx.x], p1 = lk_start[blockIdx.x + 1];
     for (int e = threadIdx.x; e < E; e += blockDim.x) {
         float s = 0.f;
@@ -543,8 +560,9 @@ __global__ void k_ae_lk_part(const int32_t *lk_start, const int32_t *lk_pos, con
     }
 }
 // AE2 (plain LookupTable): pass 1 is the plain sum of the chunk's d(input) rows
-__global__ void k_ae2_lk_part(const int32_t *lk_start, const int32_t *lk_pos, const float *dX, int E, float *part)
+__global__ void k_ae2_lk_part(const int32_t *lk_start, const int32_t *lk_pos, const float *dX, int E, float *part, const int32_t *cnt)
 {
+    if (cnt && (int)blockIdx.x >= cnt[0]) return;
     const int p0 = lk_start[blockIdx.x], p1 = lk_start[blockIdx.x + 1];
     for (int e = threadIdx.x; e < E; e += blockDim.x) {
         float s = 0.f;
@@ -552,14 +570,152 @@ __global__ void k_ae2_lk_part(const int32_t *lk_start, const int32_t *lk_pos, co
         part[(size_t)blockIdx.x * E + e] = s;
     }
 }
-__global__ void k_ae_lk_sum(const int32_t *lk_tok, const int32_t *lk_tc, const float *part, int E, float *dW)
+__global__ void k_ae_lk_sum(const int32_t *lk_tok, const int32_t *lk_tc, const float *part, int E, float *dW, const int32_t *cnt)
 {
+    if (cnt && (int)blockIdx.x >= cnt[0]) return;
     const int u = lk_tok[blockIdx.x], c0 = lk_tc[blockIdx.x], c1 = lk_tc[blockIdx.x + 1];
     for (int e = threadIdx.x; e < E; e += blockDim.x) {
         float s = 0.f;
         for (int k = c0; k < c1; ++k) s += part[(size_t)k * E + e];
         dW[(size_t)(u - 1) * E + e] = s;
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The resident corpus (nvqa_ae_corpus_load / nvqa_ae_step_rows): the batch is gathered from the corpus in
+// HBM by row ids that travel as kernel arguments, and the lookup gradient's index above is built here instead of on the host --
+// the same four arrays, entry for entry, so the lookup gradient keeps its bits.
+// ------------------------------------------------------------------------------------------------------------------
+// tok rows [b0, b0 + nb) of the batch = corpus rows ids.q[0 .. nb), rows from n on zero (nvqa_ae_evaluate_rows with n < B)
+__global__ void k_ae_gather_rows(const int32_t *corpus, QIdxArg ids, int b0, int nb, int n, int D, int32_t *tok)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nb * D) return;
+    const int bl = i / D, t = i % D, b = b0 + bl;
+    tok[(size_t)b * D + t] = b < n ? corpus[(size_t)ids.q[bl] * D + t] : 0;
+}
+
+// the token the lookup gradient books chain row (q, b) under (ae_upload's index loop): START = V + 1 at the decoder's first step
+// (AE2: also at encoder step 1; its chain step 0, the image row, is never asked for), 0 -> 1
+__device__ __forceinline__ int ae_chain_token(const int32_t *tok, int b, int q, int te, int D, int V, bool ae2)
+{
+    int v;
+    if (q == te || (ae2 && q == 1)) v = V + 1;
+    else if (q < te) v = tok[(size_t)b * D + q - (ae2 ? 2 : 0)];
+    else v = tok[(size_t)b * D + q - te - 1];
+    return v == 0 ? 1 : v;
+}
+
+// hist[q][v] = rows of chain step q that carry token v (W = V + 2 bins per step).  Integer counts: their order does not matter.
+__global__ void k_ae_lk_hist(const int32_t *tok, int B, int D, int V, int te, int ae2, int r_lo, int np, int32_t *hist)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= np) return;
+    const int r = r_lo + i, q = r / B, b = r % B;
+    atomicAdd(hist + (size_t)q * (V + 2) + ae_chain_token(tok, b, q, te, D, V, ae2 != 0), 1);
+}
+
+// per token: base[q][v] = its rows in the chain steps before q, tot[v] = all its rows.  One thread per token.
+__global__ void k_ae_lk_prefix(const int32_t *__restrict__ hist, int V, int q_lo, int Q, int32_t *__restrict__ base,
+                               int32_t *__restrict__ tot)
+{
+    const int v = 1 + blockIdx.x * blockDim.x + threadIdx.x, W = V + 2;
+    if (v > V + 1) return;
+    int run = 0;
+    for (int q = q_lo; q < Q; ++q) {
+        base[(size_t)q * W + v] = run;
+        run += hist[(size_t)q * W + v];
+    }
+    tot[v] = run;
+}
+
+// exclusive scan of one int per thread over a workgroup of NT threads (wave64 shuffles, then the waves' totals through LDS)
+template <int NT>
+__device__ __forceinline__ int ae_block_excl_scan(int x, int *wsum, int *total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += y;
+    }
+    __syncthreads(); // (wsum may still be read from the previous scan)
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < NT / 64; ++k) {
+        if (k < w) off += wsum[k];
+        tot += wsum[k];
+    }
+    *total = tot;
+    return off + inc - x;
+}
+
+// one workgroup over the V + 1 bins, each thread a run of consecutive tokens: the distinct tokens ascending (lk_tok), their first
+// chunk (lk_tc, and chb[v] for k_ae_lk_rank), and tot[v] turned into the token's first slot of lk_pos; cnt = {nu, nch}, and the
+// closing entries lk_tc[nu] = nch, lk_start[nch] = rows.  The chunks' starts themselves are written by k_ae_lk_rank.
+#define NVQA_AE_SCAN_NT 1024
+__global__ __launch_bounds__(NVQA_AE_SCAN_NT) void k_ae_lk_scan(int V, int32_t *tot, int32_t *chb, int32_t *lk_tok, int32_t *lk_tc,
+                                                                int32_t *lk_start, int32_t *cnt)
+{
+    __shared__ int wsum[NVQA_AE_SCAN_NT / 64];
+    const int nb = V + 1, per = (nb + NVQA_AE_SCAN_NT - 1) / NVQA_AE_SCAN_NT;
+    const int v0 = 1 + (int)threadIdx.x * per, v1 = min(v0 + per, nb + 1);
+    int nu = 0, nch = 0, acc = 0;
+    for (int v = v0; v < v1; ++v) {
+        const int n = tot[v];
+        nu += n > 0 ? 1 : 0;
+        nch += (n + NVQA_AE_LK_CHUNK - 1) / NVQA_AE_LK_CHUNK;
+        acc += n;
+    }
+    int nu_all, nch_all, acc_all;
+    int u = ae_block_excl_scan<NVQA_AE_SCAN_NT>(nu, wsum, &nu_all);
+    int ch = ae_block_excl_scan<NVQA_AE_SCAN_NT>(nch, wsum, &nch_all);
+    int at = ae_block_excl_scan<NVQA_AE_SCAN_NT>(acc, wsum, &acc_all);
+    for (int v = v0; v < v1; ++v) {
+        const int n = tot[v];
+        if (n == 0) continue;
+        lk_tok[u] = v;
+        lk_tc[u] = ch;
+        chb[v] = ch;
+        tot[v] = at;
+        ++u;
+        ch += (n + NVQA_AE_LK_CHUNK - 1) / NVQA_AE_LK_CHUNK;
+        at += n;
+    }
+    if (threadIdx.x == 0) {
+        lk_tc[nu_all] = nch_all;
+        lk_start[nch_all] = acc_all;
+        cnt[0] = nu_all;
+        cnt[1] = nch_all;
+    }
+}
+
+// chain row (q, b) goes to slot first[v] + base[q][v] + (rows b' < b of step q with the same token): ascending chain rows inside
+// a token, whatever the schedule.  Workgroup (q, block of 256 rows); the step's tokens pass through LDS 256 at a time.  A row
+// that opens a chunk writes the chunk's start.
+__global__ __launch_bounds__(256) void k_ae_lk_rank(const int32_t *tok, int B, int D, int V, int te, int ae2, int q_lo,
+                                                    const int32_t *base, const int32_t *first, const int32_t *chb, int32_t *lk_start,
+                                                    int32_t *lk_pos)
+{
+    __shared__ int tile[256];
+    const int q = q_lo + blockIdx.x, bg = blockIdx.y * 256, b = bg + (int)threadIdx.x;
+    const int v = b < B ? ae_chain_token(tok, b, q, te, D, V, ae2 != 0) : -1;
+    int rank = 0;
+    for (int j0 = 0; j0 < min(B, bg + 256); j0 += 256) {
+        __syncthreads();
+        const int j = j0 + (int)threadIdx.x;
+        tile[threadIdx.x] = j < B ? ae_chain_token(tok, j, q, te, D, V, ae2 != 0) : 0;
+        __syncthreads();
+        const int lim = min(256, b - j0);
+        for (int k = 0; k < lim; ++k) rank += tile[k] == v ? 1 : 0;
+    }
+    if (b >= B) return;
+    const int p = base[(size_t)q * (V + 2) + v] + rank, slot = first[v] + p;
+    lk_pos[slot] = q * B + b;
+    if (p % NVQA_AE_LK_CHUNK == 0) lk_start[chb[v] + p / NVQA_AE_LK_CHUNK] = slot;
 }
 
 // clamp -> + wd x -> adam (misc/optim_updates.lua:78-111) in one pass, with the log line's statistics of x before the update:
@@ -847,12 +1003,13 @@ void ae_destroy(nvqa_ctx *c)
 {
     if (!c->ae) return;
     AeState &a = *c->ae;
-    void *ptrs[] = {a.Htd16, a.G16, a.Wp16, a.WpT16, a.rowlse, a.rowtgt, a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
+    void *ptrs[] = {a.corpus, a.lk_hist, a.lk_base, a.lk_tot, a.lk_chb, a.lk_cnt, a.Htd16, a.G16, a.Wp16, a.WpT16, a.rowlse, a.rowtgt, a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
                     a.logits, a.rowloss, a.loss, a.dpw, a.slabs, a.colpart, a.img, a.etok, a.feat, a.wp_x, a.wp_g, a.wp_m, a.wp_v,
                     a.wp_part, a.jbuf, a.qd, a.vd, a.qc, a.ic, a.dqp, a.dvp, a.dh0, a.dfeat, a.br_slabs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (a.staged) (void)hipEventDestroy(a.staged);
+    if (a.step_ev) (void)hipEventDestroy(a.step_ev);
     for (int l = 0; l < NVQA_MAX_LAYERS; ++l)
         for (void *p : {(void *)a.Gt[l], (void *)a.Hs[l], (void *)a.Cs[l], (void *)a.U[l]})
             if (p) (void)hipFree(p);
@@ -1219,12 +1376,21 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
     {   // lookup table: both token streams into one gradient (AE2: every chain row but the image's)
         ProfScope ps(c, PF_AE_EMB_BWD, 0, (double)Q * B * E * (a.ae2 ? 4 : 12));
         NVQA_HIP(hipMemsetAsync(c->G + c->lo.w_lk, 0, (size_t)Vp1 * E * 4, c->s));
-        const int nu = a.h_lk[0], nch = a.h_lk[1], nt = std::min(256, (E + 63) / 64 * 64);
+        int nu = a.h_lk[0], nch = a.h_lk[1];
+        const int nt = std::min(256, (E + 63) / 64 * 64);
+        const int32_t *cu = nullptr, *cc = nullptr;
+        if (a.lk_dev) { // nu / nch are on the device: grids of their upper bounds (nch <= nu + rows / chunk), the kernels cut themselves
+            const int np = Q * B - (a.ae2 ? B : 0);
+            nu = std::min(Vp1, np);
+            nch = std::min(np, nu + np / NVQA_AE_LK_CHUNK);
+            cu = a.lk_cnt;
+            cc = a.lk_cnt + 1;
+        }
         if (a.ae2)
-            hipLaunchKernelGGL(k_ae2_lk_part, dim3(nch), dim3(nt), 0, c->s, a.lk_start, a.lk_pos, a.dX, E, a.lk_part);
+            hipLaunchKernelGGL(k_ae2_lk_part, dim3(nch), dim3(nt), 0, c->s, a.lk_start, a.lk_pos, a.dX, E, a.lk_part, cc);
         else
-            hipLaunchKernelGGL(k_ae_lk_part, dim3(nch), dim3(nt), 0, c->s, a.lk_start, a.lk_pos, a.X0, a.dX, B, a.D, E, T, dr, a.lk_part);
-        hipLaunchKernelGGL(k_ae_lk_sum, dim3(nu), dim3(nt), 0, c->s, a.lk_tok, a.lk_tc, a.lk_part, E, c->G + c->lo.w_lk);
+            hipLaunchKernelGGL(k_ae_lk_part, dim3(nch), dim3(nt), 0, c->s, a.lk_start, a.lk_pos, a.X0, a.dX, B, a.D, E, T, dr, a.lk_part, cc);
+        hipLaunchKernelGGL(k_ae_lk_sum, dim3(nu), dim3(nt), 0, c->s, a.lk_tok, a.lk_tc, a.lk_part, E, c->G + c->lo.w_lk, cu);
         NVQA_HIP(hipGetLastError());
     }
     NVQA_TRY(ae_comm_reduce(c, c->lo.w_lk, (size_t)Vp1 * E, 2));
@@ -1331,6 +1497,7 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *ima
         for (int i = 0; i < NP; ++i) pos[at[tokr[i]]++] = r_lo + i;
         a.h_lk[0] = nu;
         a.h_lk[1] = nch;
+        a.lk_dev = false;
         NVQA_HIP(hipMemcpyAsync(a.lk_tok, ut, (size_t)nu * 4, hipMemcpyHostToDevice, c->s));
         NVQA_HIP(hipMemcpyAsync(a.lk_tc, tc, (size_t)(nu + 1) * 4, hipMemcpyHostToDevice, c->s));
         NVQA_HIP(hipMemcpyAsync(a.lk_start, cs, (size_t)(nch + 1) * 4, hipMemcpyHostToDevice, c->s));
@@ -1412,6 +1579,29 @@ static int ae_check_wp(nvqa_ctx *c, const char *fn)
     return 0;
 }
 
+// The data-parallel step's first exchange.  The ranks' criterion counts differ, and the mean of their means is not the global
+// batch's mean: N = sum n_r is formed on the device, on the communication stream, under the forward pass.  No host ever sees
+// another rank's count.  The communication stream is idle (the last step joined it), and nothing may read the old weight any
+// more when k_ae_set_count overwrites it: the host-fed step knows that from ae_upload, which has drained the compute stream;
+// the resident step (edge) drains nothing and makes the communication stream wait for the compute stream's position instead.
+static int ae_dp_count(nvqa_ctx *c, int ncount, bool edge)
+{
+    AeState &a = *c->ae;
+    if (edge) {
+        if (!a.step_ev) NVQA_HIP(hipEventCreateWithFlags(&a.step_ev, hipEventDisableTiming));
+        NVQA_HIP(hipEventRecord(a.step_ev, c->s));
+        NVQA_HIP(hipStreamWaitEvent(c->sc, a.step_ev, 0));
+    }
+    hipLaunchKernelGGL(k_ae_set_count, dim3(1), dim3(1), 0, c->sc, a.dpw, (float)ncount);
+    NVQA_HIP(hipGetLastError());
+    NVQA_TRY(ae_comm_count(c, a.dpw));
+    hipLaunchKernelGGL(k_ae_rank_weight, dim3(1), dim3(1), 0, c->sc, a.dpw, (float)c->world);
+    NVQA_HIP(hipGetLastError());
+    NVQA_HIP(hipEventRecord(c->evComm, c->sc));
+    a.dp_wait = true;
+    return 0;
+}
+
 static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out,
                         float *dimages_out, const float *feats = nullptr, const int32_t *enc_tokens = nullptr,
                         const float *enc_state = nullptr, float *dfeats_out = nullptr)
@@ -1420,23 +1610,12 @@ static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens,
     const Drop dr = ae_drop(dropout, true);
     int ncount = 0;
     NVQA_TRY(ae_upload(c, c->d.B, tokens, images, !c->ae->feats, &ncount, feats, enc_tokens, enc_state));
-    if (c->comm) {
-        // The ranks' criterion counts differ, and the mean of their means is not the global batch's mean: N = sum n_r is formed on
-        // the device, on the communication stream (idle: the last step joined it, and ae_upload has drained the compute stream, so
-        // nothing reads the old weight any more), under the forward pass.  No host ever sees another rank's count.
-        AeState &a = *c->ae;
-        hipLaunchKernelGGL(k_ae_set_count, dim3(1), dim3(1), 0, c->sc, a.dpw, (float)ncount);
-        NVQA_HIP(hipGetLastError());
-        NVQA_TRY(ae_comm_count(c, a.dpw));
-        hipLaunchKernelGGL(k_ae_rank_weight, dim3(1), dim3(1), 0, c->sc, a.dpw, (float)c->world);
-        NVQA_HIP(hipGetLastError());
-        NVQA_HIP(hipEventRecord(c->evComm, c->sc));
-        a.dp_wait = true;
-    }
+    if (c->comm) NVQA_TRY(ae_dp_count(c, ncount, false));
     NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
     NVQA_TRY(ae_backward(c, dr, dfeats_out != nullptr));
     NVQA_TRY(ae_comm_join(c));
     c->have_grads = true;
+    if (!c->ae->feats) c->ae->routes[0] += 1;
     if (dfeats_out) {
         NVQA_HIP(hipMemcpyAsync(dfeats_out, c->ae->dfeat, (size_t)c->d.B * c->d.I * 4, hipMemcpyDeviceToHost, c->s));
         NVQA_HIP(hipStreamSynchronize(c->s));
@@ -1450,15 +1629,11 @@ static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens,
     return 0;
 }
 
-static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, float *loss_out, int32_t *samples_out,
-                            const float *feats = nullptr, const int32_t *enc_tokens = nullptr)
+// evaluate mode on the batch in place (n valid rows): the teacher-forced loss and, on request, greedy decoding
+static int ae_evaluate_run(nvqa_ctx *c, int32_t n, int ncount, float *loss_out, int32_t *samples_out)
 {
-    if (!tokens) { set_error("tokens is NULL"); return -1; }
-    if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
     AeState &a = *c->ae;
     const Drop dr = ae_drop(nullptr, false);
-    int ncount = 0;
-    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount, feats, enc_tokens));
     NVQA_TRY(ae_forward(c, dr, n, ncount, false));
     if (samples_out) {
         // sample(): the encoder state is the one just computed (slot te); the decoder is fed START, then its own argmax
@@ -1484,7 +1659,176 @@ static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const i
     return 0;
 }
 
+static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, float *loss_out, int32_t *samples_out,
+                            const float *feats = nullptr, const int32_t *enc_tokens = nullptr)
+{
+    if (!tokens) { set_error("tokens is NULL"); return -1; }
+    if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
+    int ncount = 0;
+    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount, feats, enc_tokens));
+    return ae_evaluate_run(c, n, ncount, loss_out, samples_out);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// the resident corpus: host side
+// ------------------------------------------------------------------------------------------------------------------
+// the launch plan of a batch of corpus rows from the host tables: tmax, te, the criterion's n.  Nothing is launched: every
+// error of a resident step is raised here, before its first kernel and (data parallel) before its first collective.
+static int ae_rows_plan(nvqa_ctx *c, const char *fn, int n, const int64_t *rows, int *ncount)
+{
+    AeState &a = *c->ae;
+    if (!rows) { set_error("%s: rows is NULL", fn); return -1; }
+    if (!a.corpus) { set_error("%s: no corpus is loaded (nvqa_ae_corpus_load comes first)", fn); return -1; }
+    int tmax = 0, cnt = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t r = rows[i];
+        if (r < 0 || r >= a.corpus_rows) {
+            set_error("%s: rows[%d] = %lld outside 0..%lld (the corpus holds %lld rows)", fn, i, (long long)r,
+                      (long long)a.corpus_rows - 1, (long long)a.corpus_rows);
+            return -1;
+        }
+        tmax = std::max(tmax, (int)a.row_last[r]);
+        cnt += a.row_cnt[r];
+    }
+    if (tmax == 0) { set_error("ae: the batch holds no token (every row is null)"); return -1; }
+    a.tmax = tmax;
+    a.te = a.ae2 ? tmax + 2 : tmax;
+    a.skip = false;
+    a.img_live = false; // AE2: zero image rows, as the text script feeds
+    *ncount = cnt;
+    return 0;
+}
+
+// the batch of ae_rows_plan onto the device: the ids ride in the kernel arguments of the gather (NVQA_QARG_MAX per launch), so
+// no staging buffer has to be waited for; index: the lookup gradient's token -> rows index, built from the gathered tokens
+static int ae_rows_launch(nvqa_ctx *c, int n, const int64_t *rows, bool index)
+{
+    AeState &a = *c->ae;
+    const int B = c->d.B, D = a.D, V = c->d.V;
+    {
+        ProfScope ps(c, PF_AE_EMB, 0, (double)B * D * 8);
+        for (int b0 = 0; b0 < B; b0 += NVQA_QARG_MAX) {
+            const int nb = std::min(NVQA_QARG_MAX, B - b0);
+            QIdxArg ids;
+            for (int k = 0; k < nb; ++k) ids.q[k] = b0 + k < n ? (int32_t)rows[b0 + k] : 0;
+            hipLaunchKernelGGL(k_ae_gather_rows, dim3((unsigned)((nb * D + 255) / 256)), dim3(256), 0, c->s, (const int32_t *)a.corpus, ids,
+                               b0, nb, n, D, a.tok);
+        }
+        NVQA_HIP(hipGetLastError());
+    }
+    if (!index) return 0;
+    const int TE = a.te, Q = TE + a.tmax + 1, q_lo = a.ae2 ? 1 : 0, r_lo = q_lo * B, np = Q * B - r_lo;
+    ProfScope ps(c, PF_AE_EMB_BWD, 0, (double)Q * (V + 2) * 16);
+    NVQA_HIP(hipMemsetAsync(a.lk_hist, 0, (size_t)Q * (V + 2) * 4, c->s)); // every bin this step's kernels read, whatever the last step's Q was
+    hipLaunchKernelGGL(k_ae_lk_hist, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->s, (const int32_t *)a.tok, B, D, V, TE,
+                       a.ae2 ? 1 : 0, r_lo, np, a.lk_hist);
+    hipLaunchKernelGGL(k_ae_lk_prefix, dim3((unsigned)((V + 1 + 255) / 256)), dim3(256), 0, c->s, (const int32_t *)a.lk_hist, V, q_lo, Q,
+                       a.lk_base, a.lk_tot);
+    hipLaunchKernelGGL(k_ae_lk_scan, dim3(1), dim3(NVQA_AE_SCAN_NT), 0, c->s, V, a.lk_tot, a.lk_chb, a.lk_tok, a.lk_tc, a.lk_start,
+                       a.lk_cnt);
+    hipLaunchKernelGGL(k_ae_lk_rank, dim3((unsigned)(Q - q_lo), (unsigned)((B + 255) / 256)), dim3(256), 0, c->s, (const int32_t *)a.tok,
+                       B, D, V, TE, a.ae2 ? 1 : 0, q_lo, (const int32_t *)a.lk_base, (const int32_t *)a.lk_tot, (const int32_t *)a.lk_chb,
+                       a.lk_start, a.lk_pos);
+    NVQA_HIP(hipGetLastError());
+    a.lk_dev = true;
+    return 0;
+}
+
 } // namespace nvqa
+
+extern "C" int nvqa_ae_corpus_load(nvqa_ctx *c, int64_t n_rows, const int32_t *tokens)
+{
+    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_corpus_load"));
+    if (!tokens) { set_error("nvqa_ae_corpus_load: tokens is NULL"); return -1; }
+    AeState &a = *c->ae;
+    const int D = a.D, V = c->d.V;
+    if (n_rows < 1 || n_rows > INT32_MAX) { set_error("nvqa_ae_corpus_load: n_rows = %lld outside 1..2^31-1", (long long)n_rows); return -1; }
+    if (D >= 65535) { set_error("nvqa_ae_corpus_load: seq_length %d does not fit the per-row host tables", D); return -1; }
+    std::vector<uint16_t> last((size_t)n_rows), cnt((size_t)n_rows);
+    for (int64_t r = 0; r < n_rows; ++r) {
+        int lastc = 0, nn = 0;
+        for (int t = 0; t < D; ++t) {
+            const int v = tokens[(size_t)r * D + t];
+            if (v < 0 || v > V) {
+                set_error("nvqa_ae_corpus_load: token %d at (row %lld, column %d) outside 0..%d", v, (long long)r, t, V);
+                return -1;
+            }
+            if (v) { lastc = t + 1; ++nn; }
+        }
+        last[(size_t)r] = (uint16_t)lastc;
+        cnt[(size_t)r] = (uint16_t)(nn + 1); // LanguageModelCriterion's n (ae_upload's loop): every token and the first null, which position D always is
+    }
+    if (!a.lk_cnt) { // the index build's scratch, on first use
+        const size_t W = (size_t)V + 2;
+        AE_ALLOC(a.lk_hist, (size_t)a.QM * W);
+        AE_ALLOC(a.lk_base, (size_t)a.QM * W);
+        AE_ALLOC(a.lk_tot, W);
+        AE_ALLOC(a.lk_chb, W);
+        AE_ALLOC(a.lk_cnt, 2);
+    }
+    const size_t bytes = (size_t)n_rows * D * 4;
+    int32_t *dev = nullptr;
+    hipError_t e = hipMalloc((void **)&dev, bytes);
+    if (e != hipSuccess) {
+        set_error("nvqa_ae_corpus_load: hipMalloc of %zu bytes for %lld rows failed: %s", bytes, (long long)n_rows, hipGetErrorString(e));
+        return -1;
+    }
+    e = hipMemcpy(dev, tokens, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->s); // steps in flight still gather from the old corpus
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        set_error("nvqa_ae_corpus_load: copying %zu bytes to the device failed: %s", bytes, hipGetErrorString(e));
+        return -1;
+    }
+    if (a.corpus) (void)hipFree(a.corpus);
+    a.corpus = dev;
+    a.corpus_rows = n_rows;
+    a.row_last.swap(last);
+    a.row_cnt.swap(cnt);
+    return 0;
+}
+
+extern "C" int nvqa_ae_step_rows(nvqa_ctx *c, const int64_t *rows, const nvqa_dropout *dropout, float *loss_out)
+{
+    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_step_rows"));
+    const Drop dr = ae_drop(dropout, true);
+    int ncount = 0;
+    NVQA_TRY(ae_rows_plan(c, "nvqa_ae_step_rows", c->d.B, rows, &ncount));
+    if (c->comm) NVQA_TRY(ae_dp_count(c, ncount, true));
+    NVQA_TRY(ae_rows_launch(c, c->d.B, rows, true));
+    NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
+    NVQA_TRY(ae_backward(c, dr));
+    NVQA_TRY(ae_comm_join(c));
+    c->have_grads = true;
+    c->ae->routes[1] += 1;
+    if (loss_out) {
+        NVQA_HIP(hipStreamSynchronize(c->s));
+        *loss_out = ae_last_loss(c);
+    }
+    return 0;
+}
+
+extern "C" int nvqa_ae_evaluate_rows(nvqa_ctx *c, int32_t n, const int64_t *rows, float *loss_out, int32_t *samples_out)
+{
+    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_evaluate_rows"));
+    if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
+    int ncount = 0;
+    NVQA_TRY(ae_rows_plan(c, "nvqa_ae_evaluate_rows", n, rows, &ncount));
+    NVQA_TRY(ae_rows_launch(c, n, rows, false));
+    return ae_evaluate_run(c, n, ncount, loss_out, samples_out);
+}
+
+extern "C" int nvqa_ae_step_routes(const nvqa_ctx *c, int64_t out[2])
+{
+    if (!c || !out) { set_error("NULL argument"); return -1; }
+    if (!c->ae || (c->d.arch != NVQA_ARCH_AE1 && c->d.arch != NVQA_ARCH_AE2)) {
+        set_error("nvqa_ae_step_routes: an NVQA_ARCH_AE1 / NVQA_ARCH_AE2 context expected (arch %d)", c->d.arch);
+        return -1;
+    }
+    out[0] = c->ae->routes[0];
+    out[1] = c->ae->routes[1];
+    return 0;
+}
 
 // The bf16 operand mode of the AE1 / AE2 step.  A switch of its own: nvqa_set_precision(ctx, 1) stays
 // refused on every auto-encoder context.

@@ -32,6 +32,7 @@ class DataLoader:
         self.ix_to_word = ix_to_word or {}
         self.seq_length = next(iter(self.labels.values())).shape[1]
         self.iterators = {k: 1 for k in self.labels}
+        self._corpus = None
 
     @staticmethod
     def _has(f, split):
@@ -61,22 +62,49 @@ class DataLoader:
         return self._global_batch(split, batch_size)
 
     def _global_batch(self, split, batch_size):
-        data = self.labels[split]
-        max_index = data.shape[0]
+        rows, bounds = self._global_rows(split, batch_size)
+        return self.labels[split][rows], bounds
+
+    def _global_rows(self, split, batch_size):
+        """the 0-based rows of the split that getBatch draws next (and the iterator's move)"""
+        max_index = self.labels[split].shape[0]
         it = self.iterators[split]
         wrapped = False
         if it + batch_size - 1 > max_index:
             wrapped = True
             if it < max_index:
                 num_left = max_index - it + 1
-                batch = np.concatenate([data[it - 1:max_index], data[0:batch_size - num_left]])
+                rows = np.concatenate([np.arange(it - 1, max_index), np.arange(0, min(batch_size - num_left, max_index))])
             else:
-                batch = data[0:batch_size].copy()
+                rows = np.arange(0, min(batch_size, max_index))
             self.iterators[split] = 1
         else:
-            batch = data[it - 1:it - 1 + batch_size].copy()
+            rows = np.arange(it - 1, it - 1 + batch_size)
             self.iterators[split] = it + batch_size
-        return batch, {"it_pos_now": self.iterators[split], "it_max": max_index, "wrapped": wrapped}
+        return rows.astype(np.int64), {"it_pos_now": self.iterators[split], "it_max": max_index, "wrapped": wrapped}
+
+    def corpus(self):
+        """(tokens [N x D] int32, {split: first_row}): the splits one after the other -- train, val, test, then any other by
+        name -- as one array for Context.ae_corpus_load; row i of a split is row first_row + i of it."""
+        if self._corpus is None:
+            order = [s for s in ("train", "val", "test") if s in self.labels] + sorted(set(self.labels) - {"train", "val", "test"})
+            first, at = {}, 0
+            for s in order:
+                first[s] = at
+                at += self.labels[s].shape[0]
+            self._corpus = (np.ascontiguousarray(np.concatenate([self.labels[s] for s in order]), np.int32), first)
+        return self._corpus
+
+    def get_rows(self, split, batch_size, rank_stride=True):
+        """get_batch by name: (rows int64 of corpus()[0], bounds), with corpus()[0][rows] equal to what get_batch returns for
+        the same call.  Moves the same iterator in the same way (wrap, rank stride, back to 1 after a wrap)."""
+        first = self.corpus()[1][split]
+        if self.world > 1 and rank_stride:
+            rows, bounds = self._global_rows(split, batch_size * self.world)
+            rows = rows[self.rank * batch_size:(self.rank + 1) * batch_size]
+        else:
+            rows, bounds = self._global_rows(split, batch_size)
+        return rows + first, bounds
 
 
 def decode_sequence(ix_to_word, seq, end_token):
@@ -130,6 +158,7 @@ class AETrainer:
         self.dropout_seed = seed + 1000 * self.rank  # ranks hold different sentences: identical masks would correlate them
         self.iter = 1
         self.bf16 = bool(bf16)
+        self._resident = None  # the loader whose corpus is resident (load_corpus)
         self.ctx.init_params(seed, -0.08, 0.08)
         if self.bf16:  # bf16 operands for every dense product of the step and of eval_split (nvqa_ae_set_precision)
             self.ctx.ae_set_precision(1)
@@ -148,31 +177,67 @@ class AETrainer:
             lr *= 0.5 ** ((self.iter - self.decay_start) / self.decay_every)
         return lr
 
-    def train_step(self, tokens):
-        """lossFun + log line + update of one iteration; returns (loss, # updates, paramsNorm, the log line)."""
+    def load_corpus(self, loader):
+        """Make the loader's corpus resident in HBM (Context.ae_corpus_load of DataLoader.corpus()).  From here on train and
+        eval_split name their batches by row ids (get_rows, ae_step_rows / ae_evaluate_rows): the same batches, the same bits."""
+        self.ctx.ae_corpus_load(loader.corpus()[0])
+        self._resident = loader
+
+    def train_step(self, tokens, stats=True):
+        """lossFun + log line + update of one iteration; returns (loss, # updates, paramsNorm, the log line).
+        stats=False: the same step and update without the log line's figures (None in their place), so nothing is read back."""
+        return self._step(lambda dr: self.ctx.ae_step(tokens, dr) if stats else self.ctx.ae_step(tokens, dr, want_loss=False), stats)
+
+    def train_step_rows(self, rows, stats=True):
+        """train_step on rows of the resident corpus (load_corpus); with stats=False the iteration only enqueues work."""
+        if getattr(self, "_resident", None) is None:
+            raise ValueError("train_step_rows before load_corpus")
+        return self._step(lambda dr: self.ctx.ae_step_rows(rows, dr) if stats else self.ctx.ae_step_rows(rows, dr, want_loss=False), stats)
+
+    def _step(self, step, stats):
         dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.dropout_seed, self.iter)
-        loss = self.ctx.ae_step(tokens, dr)
+        loss = step(dr)
         lr = self.current_lr()
+        norm = count = None
         if self.optim == "adam":
-            norm, count = self.ctx.adam_update(lr, self.alpha, self.beta, self.eps, self.weight_decay, self.grad_clip, stats=True)
+            out = self.ctx.adam_update(lr, self.alpha, self.beta, self.eps, self.weight_decay, self.grad_clip, stats=stats)
+            if stats:
+                norm, count = out
         else:  # the statistics of the log line, then the same clamp / wd in nvqa_rmsprop_update
-            x = self.ctx.get_params()
-            g = np.clip(self.ctx.get_grads(), -self.grad_clip, self.grad_clip) + np.float32(self.weight_decay) * x
-            norm = float(np.sqrt((x.astype(np.float64) ** 2).sum()))
-            count = int((np.abs(g * np.float32(lr)) >= np.abs(x) * np.float32(0.01)).sum())
+            if stats:
+                x = self.ctx.get_params()
+                g = np.clip(self.ctx.get_grads(), -self.grad_clip, self.grad_clip) + np.float32(self.weight_decay) * x
+                norm = float(np.sqrt((x.astype(np.float64) ** 2).sum()))
+                count = int((np.abs(g * np.float32(lr)) >= np.abs(x) * np.float32(0.01)).sum())
             self.ctx.rmsprop_update(lr, self.alpha, self.eps, self.weight_decay, self.grad_clip)
-        line = "iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f" % (self.iter, loss, count, norm)
+        line = "iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f" % (self.iter, loss, count, norm) if stats else None
         self.iter += 1
         return loss, count, norm, line
 
-    def train(self, loader, iters, log=print):
+    def _check_resident(self, loader):
+        mine = getattr(self, "_resident", None)
+        if mine is not None and loader is not mine:
+            raise ValueError("the resident corpus is another loader's (load_corpus): its row ids mean nothing here")
+        return mine is not None
+
+    def train(self, loader, iters, log=print, log_every=1):
+        """iters iterations.  log_every > 1: only the iterations whose number is a multiple of it are logged; the others run
+        without the loss and the log line's statistics, so the host waits for nothing, and the returned losses are those of
+        the logged iterations."""
+        resident = self._check_resident(loader)
         losses = []
         for _ in range(iters):
-            batch, _ = loader.get_batch("train", self.dims.B)
-            loss, _, _, line = self.train_step(batch)
-            losses.append(loss)
-            if log:
-                log(line)
+            stats = self.iter % log_every == 0
+            if resident:
+                rows, _ = loader.get_rows("train", self.dims.B)
+                loss, _, _, line = self.train_step_rows(rows, stats)
+            else:
+                batch, _ = loader.get_batch("train", self.dims.B)
+                loss, _, _, line = self.train_step(batch, stats)
+            if stats:
+                losses.append(loss)
+                if log:
+                    log(line)
         return losses
 
     def eval_split(self, loader, split="val", val_sentences_use=-1):
@@ -183,16 +248,22 @@ class AETrainer:
         ends once n >= val_sentences_use, so a non-positive val_sentences_use evaluates one batch, as there.
         Data parallel: evaluation is rank-local (no collective) and walks the split without the rank stride, so with a
         DataLoader(rank=r, world=n) every rank evaluates the same rows and reports the same loss, as the Lua twins do."""
+        resident = self._check_resident(loader)
         loader.reset_iterator(split)
         losses, preds, used, n = [], [], 0, 0
         end = self.dims.V + 1
         ae2 = self.dims.arch == binding.ARCH_AE2
         while True:
-            if getattr(loader, "world", 1) > 1:
-                batch, bounds = loader.get_batch(split, self.dims.B, rank_stride=False)
+            if resident:
+                rows, bounds = loader.get_rows(split, self.dims.B, rank_stride=False)
+                batch = loader.corpus()[0][rows]
+                loss, samples = self.ctx.ae_evaluate_rows(rows, samples=True)
             else:
-                batch, bounds = loader.get_batch(split, self.dims.B)
-            loss, samples = self.ctx.ae_evaluate(batch, samples=True)
+                if getattr(loader, "world", 1) > 1:
+                    batch, bounds = loader.get_batch(split, self.dims.B, rank_stride=False)
+                else:
+                    batch, bounds = loader.get_batch(split, self.dims.B)
+                loss, samples = self.ctx.ae_evaluate(batch, samples=True)
             losses.append(loss)
             for p, a in zip(decode_sequence(loader.ix_to_word, samples, end), decode_sequence(loader.ix_to_word, batch, end)):
                 used += 1

@@ -83,6 +83,10 @@ SYMBOLS = {
     "nvqa_ae_evaluate_images": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _f32p, _i32p]),
     "nvqa_ae_set_precision": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_ae_comm_init": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "nvqa_ae_corpus_load": (ctypes.c_int, [_vp, ctypes.c_int64, _i32p]),
+    "nvqa_ae_step_rows": (ctypes.c_int, [_vp, _i64p, ctypes.POINTER(Dropout), _f32p]),
+    "nvqa_ae_evaluate_rows": (ctypes.c_int, [_vp, ctypes.c_int32, _i64p, _f32p, _i32p]),
+    "nvqa_ae_step_routes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     "nvqa_adam_update": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_ae_wp_step": (ctypes.c_int, [_vp, _f32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_wp_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _i32p, _f32p, _i32p]),
@@ -312,6 +316,37 @@ class Context:
         counts (comm_init stays refused on an auto-encoder context; this one is refused on the weak-paired and VQA contexts)."""
         buf = ctypes.create_string_buffer(bytes(comm_id), COMM_ID_BYTES)
         self._check(self.lib.nvqa_ae_comm_init(self._h, rank, world, ctypes.cast(buf, _vp)))
+
+    def ae_corpus_load(self, tokens):
+        """nvqa_ae_corpus_load: tokens [N x D] (0..V, 0 = null, left-aligned) become the context's resident corpus in HBM
+        (ARCH_AE1 / ARCH_AE2).  A failed load leaves the previous corpus in place."""
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(-1, self.dims.T)
+        self._check(self.lib.nvqa_ae_corpus_load(self._h, tok.shape[0], _i32(tok)))
+
+    def ae_step_rows(self, rows, dropout=None, want_loss=True):
+        """nvqa_ae_step_rows: ae_step on rows [B] (0-based, any order, repeats allowed) of the resident corpus, bit for bit.
+        With want_loss=False (and no communicator) the call only enqueues."""
+        r = np.ascontiguousarray(rows, np.int64).reshape(-1)
+        assert r.size == self.dims.B
+        loss = ctypes.c_float(0)
+        dr = ctypes.byref(dropout) if dropout is not None else None
+        self._check(self.lib.nvqa_ae_step_rows(self._h, r.ctypes.data_as(_i64p), dr, ctypes.byref(loss) if want_loss else None))
+        return float(loss.value) if want_loss else None
+
+    def ae_evaluate_rows(self, rows, samples=False):
+        """nvqa_ae_evaluate_rows: ae_evaluate on n = len(rows) <= B rows of the resident corpus."""
+        r = np.ascontiguousarray(rows, np.int64).reshape(-1)
+        n = r.size
+        out = np.empty((n, self.dims.T), np.int32) if samples else None
+        loss = ctypes.c_float(0)
+        self._check(self.lib.nvqa_ae_evaluate_rows(self._h, n, r.ctypes.data_as(_i64p), ctypes.byref(loss), _i32(out)))
+        return float(loss.value), out
+
+    def ae_step_routes(self):
+        """Training steps so far by where their batch came from: {'host': ae_step*, 'resident': ae_step_rows}."""
+        out = (ctypes.c_int64 * 2)()
+        self._check(self.lib.nvqa_ae_step_routes(self._h, out))
+        return {"host": int(out[0]), "resident": int(out[1])}
 
     def adam_update(self, lr, beta1=0.8, beta2=0.999, eps=1e-8, wd=0.0, clamp=0.0, stats=False):
         """clamp -> + wd x -> adam in one pass; stats=True returns (paramsNorm, # updates) of the log line."""

@@ -65,6 +65,10 @@ int nvqa_ae_evaluate_images(nvqa_ctx *ctx, int32_t n, const float *images, const
                             int32_t *samples_out);
 int nvqa_ae_set_precision(nvqa_ctx *ctx, int bf16);
 int nvqa_ae_comm_init(nvqa_ctx *ctx, int rank, int world, const void *id);
+int nvqa_ae_corpus_load(nvqa_ctx *ctx, int64_t n_rows, const int32_t *tokens);
+int nvqa_ae_step_rows(nvqa_ctx *ctx, const int64_t *rows, const nvqa_dropout *dropout, float *loss_out);
+int nvqa_ae_evaluate_rows(nvqa_ctx *ctx, int32_t n, const int64_t *rows, float *loss_out, int32_t *samples_out);
+int nvqa_ae_step_routes(const nvqa_ctx *ctx, int64_t out[2]);
 int nvqa_adam_update(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                      float stats_out[2]);
 int nvqa_ae_wp_step(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,

@@ -17,6 +17,10 @@ Validation is rank-local over the same rows on every rank; rank 0 alone writes t
 creates no communicator.  F must not exist when the job starts: a rank above 0 reads it as soon as it is there, and an id left by
 an earlier run would make ncclCommInitRank wait for ranks that never come.  Rank 0 removes a stale F first thing, before it
 loads the data, and removes its own F again when the communicator stands; start rank 0 first, or use a fresh name per job.
+
+-resident 1 (absent in the reference): [train | val] is copied to HBM once (nvqa_ae_corpus_load) and every training and
+validation batch is named by its row ids (nvqa_ae_step_rows / nvqa_ae_evaluate_rows): the same rows from the same iterator,
+rank stride included, and the same bits (DESIGN.md section 9.7).
 ]]--
 require 'torch'
 require 'hdf5'
@@ -49,6 +53,7 @@ cmd:option('-id', '', 'an id identifying this run/job')
 cmd:option('-seed', 123, 'random number generator seed to use')
 cmd:option('-gpuid', 0, 'which MI355X to use')
 cmd:option('-bf16', 0, '1 = bf16 operands for every dense product of the step, f32 accumulate (nvqa_ae_set_precision)')
+cmd:option('-resident', 0, '1 = the label sets stay in HBM (nvqa_ae_corpus_load) and every batch is named by its row ids')
 cmd:option('-rank', 0, 'data parallel: this process\'s rank, 0 .. world - 1')
 cmd:option('-world', 1, 'data parallel: number of processes (1 = no communicator)')
 cmd:option('-comm_id_file', '', 'data parallel: file through which rank 0 hands the communicator id to the other ranks')
@@ -111,6 +116,28 @@ if opt.world > 1 then                               -- the parameters above came
   nvqa.check(nvqa.lib.nvqa_ae_comm_init(ctx, opt.rank, opt.world, id))
   if opt.rank == 0 then os.remove(opt.comm_id_file) end  -- every rank has read it: ncclCommInitRank returns when all have joined
 end
+-- -resident 1: [train | val] in HBM once; a batch is then getBatch's rows by number (0-based, same iterator, same wrap)
+local first_row = {train = 0, val = labels.train:size(1)}
+if opt.resident == 1 then
+  local corpus = torch.cat(labels.train, labels.val, 1):contiguous()
+  nvqa.check(nvqa.lib.nvqa_ae_corpus_load(ctx, corpus:size(1), nvqa.iptr(corpus)))
+end
+local function getRows(split, batch_size)
+  local max_index, it = labels[split]:size(1), iterators[split]
+  local rows, wrapped, num_left = torch.LongTensor(batch_size), false, 0
+  if it + batch_size - 1 > max_index then
+    wrapped = true
+    if it < max_index then num_left = max_index - it + 1 end
+    for i = 1, batch_size do
+      rows[i] = first_row[split] + (i <= num_left and it + i - 2 or i - num_left - 1)
+    end
+    iterators[split] = 1
+  else
+    for i = 1, batch_size do rows[i] = first_row[split] + it + i - 2 end
+    iterators[split] = it + batch_size
+  end
+  return rows, wrapped
+end
 local dropout_seed = opt.seed + 1000 * opt.rank     -- ranks hold different sentences: identical masks would correlate them
 
 local function eval_split(split)                    -- eval_split (:148-194): mean of the per-batch losses
@@ -118,8 +145,16 @@ local function eval_split(split)                    -- eval_split (:148-194): me
   local loss_sum, evals, used = 0, 0, 0
   local loss = ffi.new('float[1]')
   while true do
-    local batch, wrapped = getBatch(split, opt.batch_size)
-    nvqa.check(nvqa.lib.nvqa_ae_evaluate(ctx, opt.batch_size, nvqa.iptr(batch), loss, nil))
+    local wrapped
+    if opt.resident == 1 then
+      local rows
+      rows, wrapped = getRows(split, opt.batch_size)
+      nvqa.check(nvqa.lib.nvqa_ae_evaluate_rows(ctx, opt.batch_size, nvqa.lptr(rows), loss, nil))
+    else
+      local batch
+      batch, wrapped = getBatch(split, opt.batch_size)
+      nvqa.check(nvqa.lib.nvqa_ae_evaluate(ctx, opt.batch_size, nvqa.iptr(batch), loss, nil))
+    end
     loss_sum = loss_sum + loss[0]; evals = evals + 1; used = used + opt.batch_size
     if wrapped or used >= opt.val_sentences_use then break end
   end
@@ -140,9 +175,15 @@ end
 local iter, loss0 = 1, nil
 local loss, stats = ffi.new('float[1]'), ffi.new('float[2]')
 while true do
-  local batch = getBatch('train', opt.batch_size * opt.world)
-  if opt.world > 1 then batch = batch:narrow(1, opt.rank * opt.batch_size + 1, opt.batch_size):contiguous() end
-  nvqa.check(nvqa.lib.nvqa_ae_step(ctx, nvqa.iptr(batch), nvqa.dropout(1, opt.drop_prob_ae, dropout_seed, iter), loss))
+  if opt.resident == 1 then
+    local rows = getRows('train', opt.batch_size * opt.world)
+    if opt.world > 1 then rows = rows:narrow(1, opt.rank * opt.batch_size + 1, opt.batch_size):contiguous() end
+    nvqa.check(nvqa.lib.nvqa_ae_step_rows(ctx, nvqa.lptr(rows), nvqa.dropout(1, opt.drop_prob_ae, dropout_seed, iter), loss))
+  else
+    local batch = getBatch('train', opt.batch_size * opt.world)
+    if opt.world > 1 then batch = batch:narrow(1, opt.rank * opt.batch_size + 1, opt.batch_size):contiguous() end
+    nvqa.check(nvqa.lib.nvqa_ae_step(ctx, nvqa.iptr(batch), nvqa.dropout(1, opt.drop_prob_ae, dropout_seed, iter), loss))
+  end
   local learning_rate = opt.learning_rate
   if iter > opt.learning_rate_decay_start and opt.learning_rate_decay_start >= 0 then
     local frac = (iter - opt.learning_rate_decay_start) / opt.learning_rate_decay_every

@@ -22,8 +22,10 @@ NVQA_RCCL_LIB names -- on a one-GPU machine the stand-in tests/shim/libnccl_shim
 refused, since a real one would wait for the N - 1 ranks this tool never starts.  A second context of the same
 shape without a communicator is timed in the same job, the two alternating block by block; the line carries both
 ("ms_per_step" without, "ms_per_step_world" with the communicator), their difference and the communicator context's profile.
+--resident (--arch 1 | 2, no --world): the same batches as one corpus in HBM (nvqa_ae_corpus_load), every step named by its row
+ids (nvqa_ae_step_rows); the line then carries "resident": 1.  Without the flag the tool runs as ever.
 
-    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--bf16] [--I 4096 --null-share 0.5] [--world N]
+    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--bf16] [--I 4096 --null-share 0.5] [--world N] [--resident]
                                            [--blocks 5 --steps 10 --warmup 5] [--out FILE]
 """
 import argparse
@@ -73,10 +75,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--world", type=int, default=1)
+    ap.add_argument("--resident", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.world < 1 or (a.world > 1 and a.arch not in (1, 2)):
         ap.error("--world: data parallel is for --arch 1 | 2 (the weak-paired contexts refuse a communicator)")
+    if a.resident and (a.arch not in (1, 2) or a.world > 1):
+        ap.error("--resident: the resident corpus is for --arch 1 | 2, timed without --world")
     if a.bf16 and a.arch not in (1, 2):
         ap.error("--bf16: the weak-paired auto-encoders have no bf16 operand mode")
     pkg = ge.load_package()
@@ -119,6 +124,10 @@ def main():
         for i, n in enumerate(lens):
             tok[i, :n] = rng.integers(1, a.V + 1, n)
         batches.append(tok)
+    rows = []
+    if a.resident:  # batch k = rows [k B, (k + 1) B) of the corpus
+        ctx.ae_corpus_load(np.concatenate(batches))
+        rows = [np.arange(k * a.B, (k + 1) * a.B, dtype=np.int64) for k in range(len(batches))]
     feats = []
     if a.arch in (5, 6):
         for _ in batches:
@@ -141,6 +150,8 @@ def main():
                 ctx.ae1_wp_step(feats[k], batches[k], enc_state=enc_state, dropout=dr, want_loss=False)
             else:
                 ctx.ae1_wp_step(feats[k], batches[k], enc_tokens=batches[k], dropout=dr, want_loss=False)
+        elif a.resident:
+            ctx.ae_step_rows(rows[k], dr, want_loss=False)
         else:
             ctx.ae_step(batches[k], dr, want_loss=False)
         ctx.adam_update(lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
@@ -167,6 +178,8 @@ def main():
         loss = ctx.ae_wp_step(feats[0], batches[0], enc_tokens=batches[0], dropout=b.Dropout(1, 0.5, 123, 0))
     elif a.arch == 6:
         loss = ctx.ae1_wp_step(feats[0], batches[0], enc_tokens=batches[0], dropout=b.Dropout(1, 0.5, 123, 0))
+    elif a.resident:
+        loss = ctx.ae_step_rows(rows[0], b.Dropout(1, 0.5, 123, 0))
     else:
         loss = ctx.ae_step(batches[0], b.Dropout(1, 0.5, 123, 0))
     # profiled pass (events around every launch group: slower, reported per group only)
@@ -218,6 +231,8 @@ def main():
     line.update(world_part)
     if a.bf16:
         line.update(bf16=1, fraction_of_bf16_mfma_peak=round(fl / (ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4))
+    if a.resident:
+        line.update(resident=1)
     if a.arch in (5, 6):
         line.update(I=I, null_share=a.null_share, null_steps_timed=int(sum(null[i % null.size] for i in timed)))
     s = json.dumps(line)
