@@ -19,6 +19,7 @@
  *   nvqa_rmsprop_update            optim.rmsprop(JdJ, x, config, state) :408,
  *                                  formula misc/rmsprop_lrscale.lua:13-34
  *   nvqa_forward                   eval-mode forward + argmax      004_eval_model.lua:202-233
+ *   nvqa_optim_update              sgd / sgdm / sgdmom / adagrad / rmsprop / adam of 001_train_autoencoder/misc/optim_updates.lua
  *   nvqa_dataset_load /            dataset[...] tensors + dataset:next_batch() gather
  *   nvqa_step_indices              002_train_baseline.lua:93-121,195-222
  *   nvqa_ae_corpus_load /          the label tensors of misc/DataLoader.lua + its linear walk (getBatch): the text
@@ -348,6 +349,12 @@ int nvqa_ae_wp_get_projection_grads(nvqa_ctx *ctx, float *w_out, float *b_out);
  * of x before the update. */
 int nvqa_ae_wp_projection_adam(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                                float stats_out[2]);
+/* The same update with the three rules of the scripts' -cnn_optim: rule = NVQA_OPT_SGD | NVQA_OPT_SGDM | NVQA_OPT_ADAM (further
+ * down; any other rule is an error).  The order (wd, then clamp), stats_out and the contexts are those of
+ * nvqa_ae_wp_projection_adam.  ADAM shares that call's state and step counter and gives the same bits; SGDM owns a velocity
+ * buffer (allocated and zeroed on first use, zeroed again by nvqa_init_params); cnnFinalLearningScales is 1 on this Linear. */
+int nvqa_ae_wp_projection_update(nvqa_ctx *ctx, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
+                                 float stats_out[2]);
 /* ---- arch1 weak-paired auto-encoder (NVQA_ARCH_AE1_WP contexts) ---- */
 /* 004_train_arch1_weakpaired_autoencoder_{vgg,inc}.lua with misc/AutoEncoder_vqa_arch.lua.  The flat vector is
  * [encoder | decoder | multimodal] with multimodal = W_q [2R x 2R], b_q [2R], W_v [2R x I], b_v [2R] (netdef.AxB(2R, I, 2R));
@@ -379,6 +386,28 @@ int nvqa_ae1_wp_get_lookup(nvqa_ctx *ctx, float *w_out);
  * (the log line of 001_train_arch1_text_autoencoder.lua:266-268). */
 int nvqa_adam_update(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                      float stats_out[2]);
+/* The six update rules of misc/optim_updates.lua (-optim rmsprop|adagrad|sgd|sgdm|sgdmom|adam of the seven scripts of
+ * 001_train_autoencoder), each one fused pass over the flat vector.  Valid on every context, with nvqa_adam_update's contract
+ * for every rule: per-segment gradient scale (nvqa_set_grad_scales x 1/world), then g = clamp(g, -clamp, clamp) (clamp > 0), then
+ * g += wd * x (wd != 0), then the rule; stats_out (may be NULL; synchronises) = {||x||_2, count(|lr g| >= 0.01 |x|)} of x before
+ * the update, g after clamp + wd; NVQA_ARCH_AE2_WP: [encoder | decoder] only, the frozen lookup table keeps its bits and the
+ * statistics leave it out; the step-skip words and the data-parallel status word are handled as there, and with a communicator
+ * the global batch's gradient is applied.  Arguments a rule does not use are ignored.  An error for an unknown rule and before
+ * any step.
+ * State: SGD has none.  SGDM, SGDMOM and ADAGRAD own one buffer each, allocated and zeroed on first use and zeroed again by
+ * nvqa_init_params.  RMSPROP uses the buffer of nvqa_rmsprop_update, ADAM the buffers and the step counter of nvqa_adam_update:
+ * with equal arguments the old and the new entry point give the same bits and may be interleaved on one context.  Through this
+ * call RMSPROP runs on the weak-paired contexts and with per-segment scales on an auto-encoder context too
+ * (nvqa_rmsprop_update itself keeps both refusals).
+ * HBM traffic per parameter: 12 B (SGD), 20 B (the four one-buffer rules), 28 B (ADAM). */
+#define NVQA_OPT_SGD     0  /* sgd()     optim_updates.lua:4-10            x -= lr g                   */
+#define NVQA_OPT_SGDM    1  /* sgdm()    :12-24  v = a v + lr g;            x -= v                      */
+#define NVQA_OPT_SGDMOM  2  /* sgdmom()  :26-40  m' = a m - lr g;           x += -a m + (1 + a) m'      */
+#define NVQA_OPT_ADAGRAD 3  /* adagrad() :42-57  m += g g;                  x -= lr g / (sqrt(m) + eps) */
+#define NVQA_OPT_RMSPROP 4  /* rmsprop() :60-76  m = a m + (1 - a) g g;     x -= lr g / (sqrt(m) + eps) */
+#define NVQA_OPT_ADAM    5  /* adam()    :78-111 as nvqa_adam_update (alpha = beta1, beta = beta2)      */
+int nvqa_optim_update(nvqa_ctx *ctx, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
+                      float stats_out[2]);
 
 /* ---- measurement ------------------------------------------------------ */
 /* HIP-event timing of kernel groups on the stream they are launched on.

@@ -101,7 +101,8 @@ struct AeState {
     float *feat = nullptr;      // AE2_WP: [B x I] features, L2-normalised in place (f^, kept for dW_p)
     float *h_feat = nullptr;    // AE2_WP: pinned staging
     float *wp_x = nullptr, *wp_g = nullptr, *wp_m = nullptr, *wp_v = nullptr; // AE2_WP: [W_p (E x I) | b_p (E)], its gradient, Adam
-    double *wp_part = nullptr;  // AE2_WP: per-workgroup statistics of nvqa_ae_wp_projection_adam
+    float *wp_vel = nullptr;    // AE2_WP: the projection's velocity of nvqa_ae_wp_projection_update(NVQA_OPT_SGDM), allocated on first use
+    double *wp_part = nullptr;  // AE2_WP: per-workgroup statistics of nvqa_ae_wp_projection_adam / _update
     int64_t wp_t = 0;           // AE2_WP: the projection's Adam step counter
     hipEvent_t staged = nullptr; // AE2_WP: the last batch's host-to-device copies are done (the staging buffers are free)
     bool staged_rec = false;
@@ -718,33 +719,85 @@ __global__ __launch_bounds__(256) void k_ae_lk_rank(const int32_t *tok, int B, i
     if (p % NVQA_AE_LK_CHUNK == 0) lk_start[chb[v] + p / NVQA_AE_LK_CHUNK] = slot;
 }
 
-// clamp -> + wd x -> adam (misc/optim_updates.lua:78-111) in one pass, with the log line's statistics of x before the update:
+// The six update rules of misc/optim_updates.lua, one element each; RULE = NVQA_OPT_*.  alpha / beta are b1 / b2, step is Adam's
+// bias-corrected rate (formed on the host), m is the rule's one state buffer (Adam: m and v).  RMSPROP keeps k_rmsprop's
+// expressions (kernels.h) term for term: nvqa_rmsprop_update and nvqa_optim_update share the buffer and must give the same bits.
+struct RuleArgs {
+    float lr, b1, b2, eps, step;
+};
+template <int RULE>
+__device__ __forceinline__ void rule_apply(const RuleArgs &r, float &x, float &m, float &v, float g)
+{
+    if constexpr (RULE == NVQA_OPT_SGD) {           // :4-10
+        x += -r.lr * g;
+    } else if constexpr (RULE == NVQA_OPT_SGDM) {   // :12-24
+        m = r.b1 * m + r.lr * g;
+        x -= m;
+    } else if constexpr (RULE == NVQA_OPT_SGDMOM) { // :26-40
+        const float m0 = m;
+        m = r.b1 * m0 - r.lr * g;
+        x += -r.b1 * m0;
+        x += (1.f + r.b1) * m;
+    } else if constexpr (RULE == NVQA_OPT_ADAGRAD) { // :42-57
+        m += g * g;
+        x += -r.lr * g / (sqrtf(m) + r.eps);
+    } else if constexpr (RULE == NVQA_OPT_RMSPROP) { // :60-76
+        const float om = 1.0f - r.b1;
+        const float mi = r.b1 * m + om * g * g;
+        m = mi;
+        x += -r.lr * g / (sqrtf(mi) + r.eps);
+    } else {                                         // :78-111
+        m = r.b1 * m + (1.f - r.b1) * g;
+        v = r.b2 * v + (1.f - r.b2) * g * g;
+        x -= r.step * (m / (sqrtf(v) + r.eps));
+    }
+}
+template <int RULE> struct RuleState { // how many state buffers the rule reads and writes
+    static constexpr int n = RULE == NVQA_OPT_SGD ? 0 : (RULE == NVQA_OPT_ADAM ? 2 : 1);
+};
+
+// clamp -> + wd x -> the rule in one pass, with the log line's statistics of x before the update:
 // part[2 blk] = sum x^2, part[2 blk + 1] = count(|lr g| >= 0.01 |x|).  Per-segment gradient scales (data-parallel mean,
 // -lr_scale) are applied before the clamp as k_rmsprop does; the step-skip words are honoured like there.
-struct AdamArgs {
+// HBM traffic per parameter: 12 B (SGD: read x, g; write x), 20 B (one state buffer), 28 B (Adam).
+struct OptimArgs {
     float *x, *m, *v;
     const float *g;
     size_t n, seg0, seg1; // segment ends: [0, seg0) scale gs[0], [seg0, seg1) gs[1], rest gs[2]
     float gs[3];
-    float lr, b1, b2, eps, wd, clamp, step;
+    RuleArgs r;
+    float wd, clamp;
     const unsigned *skip;
     const float *dp_skip;
     float *h_dp, *dp_next;
     double *part;
 };
-__device__ __forceinline__ void adam_one(const AdamArgs &a, size_t i, float &x, float &m, float &v, float g, double &sq, double &cnt)
+template <int RULE>
+__device__ __forceinline__ void optim_one(const OptimArgs &a, size_t i, float &x, float &m, float &v, float g, double &sq, double &cnt)
 {
     g *= i < a.seg0 ? a.gs[0] : (i < a.seg1 ? a.gs[1] : a.gs[2]);
     if (a.clamp > 0.f) g = fminf(fmaxf(g, -a.clamp), a.clamp);
     if (a.wd != 0.f) g += a.wd * x;
     sq += (double)x * (double)x;
-    cnt += fabsf(g * a.lr) >= fabsf(x) * 0.01f ? 1.0 : 0.0;
-    m = a.b1 * m + (1.f - a.b1) * g;
-    v = a.b2 * v + (1.f - a.b2) * g * g;
-    x -= a.step * (m / (sqrtf(v) + a.eps));
+    cnt += fabsf(g * a.r.lr) >= fabsf(x) * 0.01f ? 1.0 : 0.0;
+    rule_apply<RULE>(a.r, x, m, v, g);
 }
-__global__ __launch_bounds__(256) void k_adam(AdamArgs a)
+// the block's two partial sums -> part[2 blk], part[2 blk + 1]
+__device__ __forceinline__ void optim_stats_out(double (*sh)[256], double sq, double cnt, double *part)
 {
+    sh[0][threadIdx.x] = sq;
+    sh[1][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = sh[0][0]; part[2 * blockIdx.x + 1] = sh[1][0]; }
+}
+template <int RULE>
+__global__ __launch_bounds__(256) void k_optim(OptimArgs a)
+{
+    constexpr int NS = RuleState<RULE>::n;
     __shared__ double sh[2][256];
     if (a.dp_next && blockIdx.x == 0 && threadIdx.x == 0) *a.dp_next = 0.f;
     bool skip = a.skip && (a.skip[0] | a.skip[4]) != 0u;
@@ -758,35 +811,40 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a)
         float4 *x4 = reinterpret_cast<float4 *>(a.x), *m4 = reinterpret_cast<float4 *>(a.m), *v4 = reinterpret_cast<float4 *>(a.v);
         const float4 *g4 = reinterpret_cast<const float4 *>(a.g);
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-            float4 xv = x4[i], mv = m4[i], vv = v4[i];
+            float4 xv = x4[i], mv = {}, vv = {};
+            if constexpr (NS >= 1) mv = m4[i];
+            if constexpr (NS >= 2) vv = v4[i];
             const float4 gv = g4[i];
-            adam_one(a, 4 * i + 0, xv.x, mv.x, vv.x, gv.x, sq, cnt);
-            adam_one(a, 4 * i + 1, xv.y, mv.y, vv.y, gv.y, sq, cnt);
-            adam_one(a, 4 * i + 2, xv.z, mv.z, vv.z, gv.z, sq, cnt);
-            adam_one(a, 4 * i + 3, xv.w, mv.w, vv.w, gv.w, sq, cnt);
-            x4[i] = xv; m4[i] = mv; v4[i] = vv;
+            optim_one<RULE>(a, 4 * i + 0, xv.x, mv.x, vv.x, gv.x, sq, cnt);
+            optim_one<RULE>(a, 4 * i + 1, xv.y, mv.y, vv.y, gv.y, sq, cnt);
+            optim_one<RULE>(a, 4 * i + 2, xv.z, mv.z, vv.z, gv.z, sq, cnt);
+            optim_one<RULE>(a, 4 * i + 3, xv.w, mv.w, vv.w, gv.w, sq, cnt);
+            x4[i] = xv;
+            if constexpr (NS >= 1) m4[i] = mv;
+            if constexpr (NS >= 2) v4[i] = vv;
         }
         const size_t t = 4 * n4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; // the < 4 trailing elements
-        if (t < a.n) adam_one(a, t, a.x[t], a.m[t], a.v[t], a.g[t], sq, cnt);
+        if (t < a.n) {
+            float m = 0.f, v = 0.f;
+            if constexpr (NS >= 1) m = a.m[t];
+            if constexpr (NS >= 2) v = a.v[t];
+            optim_one<RULE>(a, t, a.x[t], m, v, a.g[t], sq, cnt);
+            if constexpr (NS >= 1) a.m[t] = m;
+            if constexpr (NS >= 2) a.v[t] = v;
+        }
     }
-    if (!a.part) return;
-    sh[0][threadIdx.x] = sq;
-    sh[1][threadIdx.x] = cnt;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { a.part[2 * blockIdx.x] = sh[0][0]; a.part[2 * blockIdx.x + 1] = sh[1][0]; }
+    if (a.part) optim_stats_out(sh, sq, cnt, a.part);
 }
 
 // the weak-paired AE's projection update (the cnn branch of 004_train_arch2_weakpaired_autoencoder_vgg.lua: g += wd x, then
-// clamp (:318-322), then adam of misc/optim_updates.lua:78-111 with lrs = 1, cnnFinalLearningScales of the final Linear), over
-// x = [W_p | b_p], n values; part[2 blk] = sum x^2 of the weight (i < nw: cnn:get(40).weight), part[2 blk + 1] =
+// clamp (:318-322), then sgd / sgdm / adam of misc/optim_updates.lua with lrs = 1, cnnFinalLearningScales of the final Linear),
+// over x = [W_p | b_p], n values; part[2 blk] = sum x^2 of the weight (i < nw: cnn:get(40).weight), part[2 blk + 1] =
 // count(|lr g| >= 0.01 |x|) over all n (:302-305), both of x before the update
-__global__ __launch_bounds__(256) void k_ae_wp_adam(float *x, float *m, float *v, const float *g, size_t n, size_t nw, float lr,
-                                                    float b1, float b2, float eps, float wd, float clamp, float step, double *part)
+template <int RULE>
+__global__ __launch_bounds__(256) void k_ae_wp_optim(float *x, float *m, float *v, const float *g, size_t n, size_t nw, RuleArgs r,
+                                                     float wd, float clamp, double *part)
 {
+    constexpr int NS = RuleState<RULE>::n;
     __shared__ double sh[2][256];
     double sq = 0, cnt = 0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -795,21 +853,16 @@ __global__ __launch_bounds__(256) void k_ae_wp_adam(float *x, float *m, float *v
         if (wd != 0.f) gi += wd * xi;
         if (clamp > 0.f) gi = fminf(fmaxf(gi, -clamp), clamp);
         if (i < nw) sq += (double)xi * (double)xi;
-        cnt += fabsf(gi * lr) >= fabsf(xi) * 0.01f ? 1.0 : 0.0;
-        const float mi = b1 * m[i] + (1.f - b1) * gi, vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        x[i] = xi - step * (mi / (sqrtf(vi) + eps));
+        cnt += fabsf(gi * r.lr) >= fabsf(xi) * 0.01f ? 1.0 : 0.0;
+        float xo = xi, mi = 0.f, vi = 0.f;
+        if constexpr (NS >= 1) mi = m[i];
+        if constexpr (NS >= 2) vi = v[i];
+        rule_apply<RULE>(r, xo, mi, vi, gi);
+        if constexpr (NS >= 1) m[i] = mi;
+        if constexpr (NS >= 2) v[i] = vi;
+        x[i] = xo;
     }
-    if (!part) return;
-    sh[0][threadIdx.x] = sq;
-    sh[1][threadIdx.x] = cnt;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { part[2 * blockIdx.x] = sh[0][0]; part[2 * blockIdx.x + 1] = sh[1][0]; }
+    if (part) optim_stats_out(sh, sq, cnt, part);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1005,7 +1058,7 @@ void ae_destroy(nvqa_ctx *c)
     AeState &a = *c->ae;
     void *ptrs[] = {a.corpus, a.lk_hist, a.lk_base, a.lk_tot, a.lk_chb, a.lk_cnt, a.Htd16, a.G16, a.Wp16, a.WpT16, a.rowlse, a.rowtgt, a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
                     a.logits, a.rowloss, a.loss, a.dpw, a.slabs, a.colpart, a.img, a.etok, a.feat, a.wp_x, a.wp_g, a.wp_m, a.wp_v,
-                    a.wp_part, a.jbuf, a.qd, a.vd, a.qc, a.ic, a.dqp, a.dvp, a.dh0, a.dfeat, a.br_slabs};
+                    a.wp_vel, a.wp_part, a.jbuf, a.qd, a.vd, a.qc, a.ic, a.dqp, a.dvp, a.dh0, a.dfeat, a.br_slabs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (a.staged) (void)hipEventDestroy(a.staged);
@@ -1528,6 +1581,7 @@ int ae_wp_init(nvqa_ctx *c, uint64_t seed, float lo, float hi)
     NVQA_HIP(hipMemcpy(a.wp_x, w.data(), np * 4, hipMemcpyHostToDevice));
     NVQA_HIP(hipMemset(a.wp_m, 0, np * 4));
     NVQA_HIP(hipMemset(a.wp_v, 0, np * 4));
+    if (a.wp_vel) NVQA_HIP(hipMemset(a.wp_vel, 0, np * 4));
     a.wp_t = 0;
     return 0;
 }
@@ -2018,77 +2072,146 @@ extern "C" int nvqa_ae_wp_get_projection_grads(nvqa_ctx *c, float *w_out, float 
     return ae_wp_copy_out(c, c->ae->wp_g, w_out, b_out);
 }
 
-extern "C" int nvqa_ae_wp_projection_adam(nvqa_ctx *c, float lr, float beta1, float beta2, float eps, float wd, float clamp,
-                                          float stats_out[2])
+// the per-workgroup partial sums of an update's statistics -> {sqrt(sum x^2), count}
+static int optim_read_stats(nvqa_ctx *c, const double *part, int NB, float stats_out[2])
 {
-    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_projection_adam"));
-    if (!c->have_grads) { set_error("nvqa_ae_wp_projection_adam before any nvqa_ae_wp_step"); return -1; }
-    AeState &a = *c->ae;
-    const size_t nw = (size_t)c->d.E * c->d.I, n = nw + c->d.E;
-    const int NB = 1024;
-    a.wp_t += 1;
-    const double t = (double)a.wp_t;
-    const float step = (float)(lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
-    ProfScope ps(c, PF_ADAM, 0, 28.0 * n);
-    hipLaunchKernelGGL(k_ae_wp_adam, dim3(NB), dim3(256), 0, c->s, a.wp_x, a.wp_m, a.wp_v, (const float *)a.wp_g, n, nw, lr, beta1,
-                       beta2, eps, wd, clamp, step, stats_out ? a.wp_part : (double *)nullptr);
-    NVQA_HIP(hipGetLastError());
-    if (stats_out) {
-        std::vector<double> h(2 * NB);
-        NVQA_HIP(hipMemcpyAsync(h.data(), a.wp_part, 2 * NB * sizeof(double), hipMemcpyDeviceToHost, c->s));
-        NVQA_HIP(hipStreamSynchronize(c->s));
-        double sq = 0, cnt = 0;
-        for (int b = 0; b < NB; ++b) { sq += h[2 * b]; cnt += h[2 * b + 1]; }
-        stats_out[0] = (float)sqrt(sq);
-        stats_out[1] = (float)cnt;
-    }
+    std::vector<double> h(2 * NB);
+    NVQA_HIP(hipMemcpyAsync(h.data(), part, 2 * NB * sizeof(double), hipMemcpyDeviceToHost, c->s));
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    double sq = 0, cnt = 0;
+    for (int b = 0; b < NB; ++b) { sq += h[2 * b]; cnt += h[2 * b + 1]; }
+    stats_out[0] = (float)sqrt(sq);
+    stats_out[1] = (float)cnt;
     return 0;
 }
 
-// AE2_WP: [encoder | decoder] only (the reference's params; the frozen lookup is left out of parameters())
-extern "C" int nvqa_adam_update(nvqa_ctx *c, float lr, float beta1, float beta2, float eps, float wd, float clamp,
-                                float stats_out[2])
+// Adam's bias-corrected rate at step t (optim_updates.lua:99-102)
+static float adam_step_size(float lr, float beta1, float beta2, int64_t t)
+{
+    return (float)(lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
+}
+
+static int ae_wp_projection_rule(nvqa_ctx *c, const char *fn, int rule, float lr, float alpha, float beta, float eps, float wd,
+                                 float clamp, float stats_out[2])
+{
+    NVQA_TRY(ae_check_wp(c, fn));
+    if (rule != NVQA_OPT_SGD && rule != NVQA_OPT_SGDM && rule != NVQA_OPT_ADAM) {
+        set_error("%s: rule %d is not one of -cnn_optim's (NVQA_OPT_SGD, NVQA_OPT_SGDM, NVQA_OPT_ADAM)", fn, rule);
+        return -1;
+    }
+    if (!c->have_grads) { set_error("%s before any nvqa_ae_wp_step", fn); return -1; }
+    AeState &a = *c->ae;
+    const size_t nw = (size_t)c->d.E * c->d.I, n = nw + c->d.E;
+    const int NB = 1024;
+    if (rule == NVQA_OPT_SGDM && !a.wp_vel) {
+        NVQA_HIP(hipMalloc((void **)&a.wp_vel, n * 4));
+        NVQA_HIP(hipMemsetAsync(a.wp_vel, 0, n * 4, c->s));
+    }
+    RuleArgs r = {lr, alpha, beta, eps, 0.f};
+    if (rule == NVQA_OPT_ADAM) r.step = adam_step_size(lr, alpha, beta, ++a.wp_t);
+    double *part = stats_out ? a.wp_part : (double *)nullptr;
+    const float *g = a.wp_g;
+    if (rule == NVQA_OPT_ADAM) {
+        ProfScope ps(c, PF_ADAM, 0, 28.0 * n);
+        hipLaunchKernelGGL(k_ae_wp_optim<NVQA_OPT_ADAM>, dim3(NB), dim3(256), 0, c->s, a.wp_x, a.wp_m, a.wp_v, g, n, nw, r, wd, clamp, part);
+    } else if (rule == NVQA_OPT_SGDM) {
+        ProfScope ps(c, PF_RMSPROP, 0, 20.0 * n);
+        hipLaunchKernelGGL(k_ae_wp_optim<NVQA_OPT_SGDM>, dim3(NB), dim3(256), 0, c->s, a.wp_x, a.wp_vel, (float *)nullptr, g, n, nw, r, wd, clamp, part);
+    } else {
+        ProfScope ps(c, PF_RMSPROP, 0, 12.0 * n);
+        hipLaunchKernelGGL(k_ae_wp_optim<NVQA_OPT_SGD>, dim3(NB), dim3(256), 0, c->s, a.wp_x, (float *)nullptr, (float *)nullptr, g, n, nw, r, wd, clamp, part);
+    }
+    NVQA_HIP(hipGetLastError());
+    return stats_out ? optim_read_stats(c, a.wp_part, NB, stats_out) : 0;
+}
+
+extern "C" int nvqa_ae_wp_projection_adam(nvqa_ctx *c, float lr, float beta1, float beta2, float eps, float wd, float clamp,
+                                          float stats_out[2])
+{
+    return ae_wp_projection_rule(c, "nvqa_ae_wp_projection_adam", NVQA_OPT_ADAM, lr, beta1, beta2, eps, wd, clamp, stats_out);
+}
+
+extern "C" int nvqa_ae_wp_projection_update(nvqa_ctx *c, int rule, float lr, float alpha, float beta, float eps, float wd,
+                                            float clamp, float stats_out[2])
+{
+    return ae_wp_projection_rule(c, "nvqa_ae_wp_projection_update", rule, lr, alpha, beta, eps, wd, clamp, stats_out);
+}
+
+template <int RULE>
+static void optim_launch(nvqa_ctx *c, const OptimArgs &a, int NB, int group)
+{
+    ProfScope ps(c, group, 0, (12.0 + 8.0 * RuleState<RULE>::n) * a.n);
+    hipLaunchKernelGGL(k_optim<RULE>, dim3(NB), dim3(256), 0, c->s, a);
+}
+
+// Every rule of misc/optim_updates.lua over the flat vector; AE2_WP: [encoder | decoder] only (the reference's params; the frozen
+// lookup is left out of parameters()).  State: SGD none; SGDM, SGDMOM, ADAGRAD one buffer each (c->opt_state, allocated and zeroed
+// on first use); RMSPROP the buffer of nvqa_rmsprop_update (c->M2); ADAM adam_m / adam_v / adam_t.
+static int optim_update(nvqa_ctx *c, const char *fn, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
+                        float stats_out[2])
 {
     if (!c) { set_error("ctx is NULL"); return -1; }
-    if (!c->have_grads) { set_error("nvqa_adam_update before any step"); return -1; }
+    if (rule < NVQA_OPT_SGD || rule > NVQA_OPT_ADAM) { set_error("%s: unknown rule %d (NVQA_OPT_SGD = 0 .. NVQA_OPT_ADAM = 5)", fn, rule); return -1; }
+    if (!c->have_grads) { set_error("%s before any step", fn); return -1; }
     NVQA_HIP(hipSetDevice(c->device));
     const size_t n = c->lo.total;
     const int NB = 1024;
-    if (!c->adam_m) {
-        NVQA_HIP(hipMalloc((void **)&c->adam_m, n * 4 + 16));
-        NVQA_HIP(hipMalloc((void **)&c->adam_v, n * 4 + 16));
-        NVQA_HIP(hipMemsetAsync(c->adam_m, 0, n * 4, c->s));
-        NVQA_HIP(hipMemsetAsync(c->adam_v, 0, n * 4, c->s));
-        NVQA_HIP(hipMalloc((void **)&c->adam_part, 2 * NB * sizeof(double)));
-        c->adam_t = 0;
+    OptimArgs a = {};
+    if (rule == NVQA_OPT_ADAM) {
+        if (!c->adam_v) { // adam_v is set last: after a failed allocation the next call starts here again, and nothing leaks
+            if (!c->adam_m) NVQA_HIP(hipMalloc((void **)&c->adam_m, n * 4 + 16));
+            NVQA_HIP(hipMalloc((void **)&c->adam_v, n * 4 + 16));
+            NVQA_HIP(hipMemsetAsync(c->adam_m, 0, n * 4, c->s));
+            NVQA_HIP(hipMemsetAsync(c->adam_v, 0, n * 4, c->s));
+            c->adam_t = 0;
+        }
+        c->adam_t += 1;
+        a.m = c->adam_m; a.v = c->adam_v;
+    } else if (rule == NVQA_OPT_RMSPROP) {
+        a.m = c->M2;
+    } else if (rule != NVQA_OPT_SGD) {
+        float *&st = c->opt_state[rule - NVQA_OPT_SGDM];
+        if (!st) {
+            NVQA_HIP(hipMalloc((void **)&st, n * 4 + 16));
+            NVQA_HIP(hipMemsetAsync(st, 0, n * 4, c->s));
+        }
+        a.m = st;
     }
-    c->adam_t += 1;
-    ProfScope ps(c, PF_ADAM, 0, 28.0 * (c->d.arch == NVQA_ARCH_AE2_WP ? c->lo.seg[0] + c->lo.seg[1] : n));
-    AdamArgs a = {};
-    a.x = c->P; a.m = c->adam_m; a.v = c->adam_v; a.g = c->G;
+    // (adam_part: the statistics' partial sums of every rule, not Adam's alone, so allocated apart from adam_m / adam_v)
+    if (stats_out && !c->adam_part) NVQA_HIP(hipMalloc((void **)&c->adam_part, 2 * NB * sizeof(double)));
+    a.x = c->P; a.g = c->G;
     a.n = c->d.arch == NVQA_ARCH_AE2_WP ? c->lo.seg[0] + c->lo.seg[1] : n;
     a.seg0 = c->lo.seg[0]; a.seg1 = c->lo.seg[0] + c->lo.seg[1];
     const float inv_world = 1.0f / (float)c->world;
     for (int i = 0; i < 3; ++i) a.gs[i] = c->gscale[i] * inv_world;
-    const double t = (double)c->adam_t;
-    a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = wd; a.clamp = clamp;
-    a.step = (float)(lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
+    a.r.lr = lr; a.r.b1 = alpha; a.r.b2 = beta; a.r.eps = eps; a.wd = wd; a.clamp = clamp;
+    if (rule == NVQA_OPT_ADAM) a.r.step = adam_step_size(lr, alpha, beta, c->adam_t);
     a.skip = c->comm ? nullptr : c->pf_sticky;
     a.dp_skip = c->comm ? c->dp_status + c->dp_slot : nullptr;
     a.h_dp = c->comm ? c->h_dp_status : nullptr;
     a.dp_next = c->comm ? c->dp_status + (c->dp_slot ^ 1) : nullptr;
     a.part = stats_out ? c->adam_part : nullptr;
-    hipLaunchKernelGGL(k_adam, dim3(NB), dim3(256), 0, c->s, a);
+    switch (rule) {
+    case NVQA_OPT_SGD: optim_launch<NVQA_OPT_SGD>(c, a, NB, PF_RMSPROP); break;
+    case NVQA_OPT_SGDM: optim_launch<NVQA_OPT_SGDM>(c, a, NB, PF_RMSPROP); break;
+    case NVQA_OPT_SGDMOM: optim_launch<NVQA_OPT_SGDMOM>(c, a, NB, PF_RMSPROP); break;
+    case NVQA_OPT_ADAGRAD: optim_launch<NVQA_OPT_ADAGRAD>(c, a, NB, PF_RMSPROP); break;
+    case NVQA_OPT_RMSPROP: optim_launch<NVQA_OPT_RMSPROP>(c, a, NB, PF_RMSPROP); break;
+    default: optim_launch<NVQA_OPT_ADAM>(c, a, NB, PF_ADAM); break;
+    }
     NVQA_HIP(hipGetLastError());
     if (c->comm) c->dp_clean[c->dp_slot ^ 1] = true;
-    if (stats_out) {
-        std::vector<double> h(2 * NB);
-        NVQA_HIP(hipMemcpyAsync(h.data(), c->adam_part, 2 * NB * sizeof(double), hipMemcpyDeviceToHost, c->s));
-        NVQA_HIP(hipStreamSynchronize(c->s));
-        double sq = 0, cnt = 0;
-        for (int b = 0; b < NB; ++b) { sq += h[2 * b]; cnt += h[2 * b + 1]; }
-        stats_out[0] = (float)sqrt(sq);
-        stats_out[1] = (float)cnt;
-    }
-    return 0;
+    return stats_out ? optim_read_stats(c, c->adam_part, NB, stats_out) : 0;
+}
+
+extern "C" int nvqa_adam_update(nvqa_ctx *c, float lr, float beta1, float beta2, float eps, float wd, float clamp,
+                                float stats_out[2])
+{
+    return optim_update(c, "nvqa_adam_update", NVQA_OPT_ADAM, lr, beta1, beta2, eps, wd, clamp, stats_out);
+}
+
+extern "C" int nvqa_optim_update(nvqa_ctx *c, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
+                                 float stats_out[2])
+{
+    return optim_update(c, "nvqa_optim_update", rule, lr, alpha, beta, eps, wd, clamp, stats_out);
 }

@@ -399,7 +399,7 @@ extern "C" int nvqa_destroy(nvqa_ctx *c)
     c->prof_pool.clear();
     comm_destroy(c);
     ae_destroy(c);
-    for (void *q : {(void *)c->adam_m, (void *)c->adam_v, (void *)c->adam_part})
+    for (void *q : {(void *)c->adam_m, (void *)c->adam_v, (void *)c->adam_part, (void *)c->opt_state[0], (void *)c->opt_state[1], (void *)c->opt_state[2]})
         if (q) (void)hipFree(q);
     if (c->hset[0].tok) { // two device sets + pinned staging of the host-batch entries
         for (int p = 0; p < 2; ++p) {
@@ -695,11 +695,13 @@ extern "C" int nvqa_init_params(nvqa_ctx *c, uint64_t seed, float lo, float hi)
     NVQA_TRY(nvqa_set_params(c, p.data()));
     if (c->d.arch == NVQA_ARCH_AE2_WP) NVQA_TRY(ae_wp_init(c, seed, lo, hi));
     NVQA_HIP(hipMemset(c->M2, 0, c->lo.total * 4));
-    if (c->adam_m) { // a fresh start of nvqa_adam_update too
+    if (c->adam_v) { // a fresh start of nvqa_adam_update too (adam_v is allocated after adam_m)
         NVQA_HIP(hipMemset(c->adam_m, 0, c->lo.total * 4));
         NVQA_HIP(hipMemset(c->adam_v, 0, c->lo.total * 4));
         c->adam_t = 0;
     }
+    for (float *st : c->opt_state) // and of the one-buffer rules of nvqa_optim_update
+        if (st) NVQA_HIP(hipMemset(st, 0, c->lo.total * 4));
     return 0;
 }
 
@@ -2214,7 +2216,7 @@ int nvqa::ae_comm_count(nvqa_ctx *c, float *cnt)
 }
 
 // reduce_join for the auto-encoder step: the closing all-reduce carries two floats, the status word (dp_status[1], always zero
-// here, read by k_adam / k_rmsprop as ever) and the rank's loss partial loss_r w_r (dp_status[2]); their sums go to the host copy's
+// here, read by k_optim / k_rmsprop as ever) and the rank's loss partial loss_r w_r (dp_status[2]); their sums go to the host copy's
 // words 0 and 2 (word 1 is the update kernels' sticky count).
 int nvqa::ae_comm_join(nvqa_ctx *c)
 {

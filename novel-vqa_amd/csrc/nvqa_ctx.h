@@ -77,7 +77,7 @@ enum ProfId {
     PF_AE_DGRAD,     // time-batched d(input) products
     PF_AE_WGRAD,     // time-batched weight gradients + bias sums
     PF_AE_EMB_BWD,   // lookup-table gradient
-    PF_ADAM,         // nvqa_adam_update
+    PF_ADAM,         // nvqa_adam_update, nvqa_optim_update(NVQA_OPT_ADAM) (its other rules: PF_RMSPROP)
     PF_AE_WP_PROJ_FWD, // weak-paired AE: feature L2 norm + x0 = f^ W_p^T + b_p
     PF_AE_WP_PROJ_BWD, // weak-paired AE: dW_p, db_p
     PF_AE1WP_BRIDGE_FWD, // arch1 weak-paired AE: D_Q / D_V, the two split-K projections, the finisher into the decoder's state slot
@@ -230,6 +230,7 @@ struct nvqa_ctx {
     float *adam_m = nullptr, *adam_v = nullptr;
     double *adam_part = nullptr; // per-workgroup {sum x^2, update count} of the log-line statistics
     int64_t adam_t = 0;
+    float *opt_state[3] = {nullptr, nullptr, nullptr}; // nvqa_optim_update: the one buffer of SGDM, SGDMOM, ADAGRAD (allocated on first use)
 
     // data parallel
     void *comm = nullptr;

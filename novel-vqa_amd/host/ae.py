@@ -121,6 +121,15 @@ def decode_sequence(ix_to_word, seq, end_token):
     return out
 
 
+def _optim_update(ctx, optim, lr, lr0, alpha, beta, eps, wd, clamp, stats=True):
+    """the scripts' `perform a parameter update` block: Context.optim_update of the named rule with the decayed rate lr --
+    except sgd, which every script applies with the undecayed opt.learning_rate (lr0).  adam keeps its own entry point,
+    nvqa_adam_update: the same kernel, state and bits as optim_update(OPT_ADAM)."""
+    if optim == "adam":
+        return ctx.adam_update(lr, alpha, beta, eps, wd, clamp, stats=stats)
+    return ctx.optim_update(binding.OPT_RULES[optim], lr0 if optim == "sgd" else lr, alpha, beta, eps, wd, clamp, stats=stats)
+
+
 # the training scripts' defaults that differ between the two auto-encoders (001_train_arch{1,2}_text_autoencoder.lua:32-50)
 ARCH_DEFAULTS = {
     binding.ARCH_AE1: {"learning_rate": 1e-5, "max_iters": 75001, "save_model_every": 75000},
@@ -130,8 +139,12 @@ ARCH_DEFAULTS = {
 
 class AETrainer:
     """The training script's loop on the library: ae_step (lossFun), the log line, the learning-rate decay and the
-    Adam (or RMSprop) update.  dims: binding.Dims with arch = ARCH_AE1 or ARCH_AE2, T = seq_length, I = C = A = 0
-    (the arch2 script forces 1 layer, :104; the library takes any L).  learning_rate None: the script's default.
+    update.  optim: the script's -optim, one of rmsprop | adagrad | sgd | sgdm | sgdmom | adam (misc/optim_updates.lua), each
+    one fused pass of nvqa_optim_update's kernel with the log line's statistics reduced on the device.  sgd is applied with the
+    undecayed learning_rate -- every reference script calls sgd(params, grad_params, opt.learning_rate) -- so it ignores
+    learning_rate_decay_start; the other rules take the decayed rate.
+    dims: binding.Dims with arch = ARCH_AE1 or ARCH_AE2, T = seq_length, I = C = A = 0 (the arch2 script forces 1 layer,
+    :104; the library takes any L).  learning_rate None: the script's default.
     bf16: the step's bf16 operand mode (Context.ae_set_precision), for either arch.
     rank (data parallel, comm_init): the parameters come from `seed` on every rank (identical replicas), the dropout masks
     from seed + 1000 * rank, as in VQATrainer; dims.B is the batch per rank.  With a communicator the log line's loss,
@@ -144,8 +157,8 @@ class AETrainer:
             raise ValueError("AETrainer needs dims.arch = ARCH_AE1 (3) or ARCH_AE2 (4)")
         if learning_rate is None:
             learning_rate = ARCH_DEFAULTS[dims.arch]["learning_rate"]
-        if optim not in ("adam", "rmsprop"):
-            raise ValueError("optim: adam or rmsprop (the other optimisers of misc/optim_updates.lua are not provided)")
+        if optim not in binding.OPT_RULES:
+            raise ValueError("optim: rmsprop | adagrad | sgd | sgdm | sgdmom | adam (misc/optim_updates.lua)")
         self.dims = dims
         self.ctx = binding.Context(dims, device)
         self.learning_rate = learning_rate
@@ -197,19 +210,11 @@ class AETrainer:
     def _step(self, step, stats):
         dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.dropout_seed, self.iter)
         loss = step(dr)
-        lr = self.current_lr()
         norm = count = None
-        if self.optim == "adam":
-            out = self.ctx.adam_update(lr, self.alpha, self.beta, self.eps, self.weight_decay, self.grad_clip, stats=stats)
-            if stats:
-                norm, count = out
-        else:  # the statistics of the log line, then the same clamp / wd in nvqa_rmsprop_update
-            if stats:
-                x = self.ctx.get_params()
-                g = np.clip(self.ctx.get_grads(), -self.grad_clip, self.grad_clip) + np.float32(self.weight_decay) * x
-                norm = float(np.sqrt((x.astype(np.float64) ** 2).sum()))
-                count = int((np.abs(g * np.float32(lr)) >= np.abs(x) * np.float32(0.01)).sum())
-            self.ctx.rmsprop_update(lr, self.alpha, self.eps, self.weight_decay, self.grad_clip)
+        out = _optim_update(self.ctx, self.optim, self.current_lr(), self.learning_rate, self.alpha, self.beta, self.eps,
+                            self.weight_decay, self.grad_clip, stats)
+        if stats:
+            norm, count = out
         line = "iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f" % (self.iter, loss, count, norm) if stats else None
         self.iter += 1
         return loss, count, norm, line
@@ -330,8 +335,10 @@ WEAKPAIRED_DEFAULTS = {"vgg": {"learning_rate": 1e-5, "I": 4096}, "inc": {"learn
 
 class WeakPairedAETrainer:
     """The weak-paired script's loop on an NVQA_ARCH_AE2_WP context: the null-sentence draw, ae_wp_step (lossFun), the log line
-    with both update counts, the learning-rate decay, Adam on [encoder | decoder] (the lookup table is frozen) and, once
-    fine-tuning has started (finetune_cnn_after >= 0 and iter >= it), Adam on the projection with its own state.
+    with both update counts, the learning-rate decay, the -optim rule (default adam; AETrainer's six names, sgd undecayed as
+    there) on [encoder | decoder] (the lookup table is frozen) and, once fine-tuning has started (finetune_cnn_after >= 0 and
+    iter >= it), the -cnn_optim rule (sgd | sgdm | adam, default adam, all three at the decayed cnn rate) on the projection with
+    its own state.
     dims: binding.Dims with arch = ARCH_AE2_WP, T = seq_length, I = the CNN feature width, C = A = 0.
     variant: 'vgg' or 'inc' (the default learning rate); learning_rate None: the variant's.
 
@@ -341,7 +348,12 @@ class WeakPairedAETrainer:
     def __init__(self, dims, device=0, variant="vgg", learning_rate=None, learning_rate_decay_start=-1,
                  learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
                  grad_clip=0.1, drop_prob=0.5, rand_val=0.5, finetune_cnn_after=-1, cnn_optim_alpha=0.8, cnn_optim_beta=0.999,
-                 cnn_learning_rate=1e-5, cnn_weight_decay=0.0, seed=123, bf16=False):
+                 cnn_learning_rate=1e-5, cnn_weight_decay=0.0, seed=123, bf16=False, optim="adam", cnn_optim="adam"):
+        if optim not in binding.OPT_RULES:
+            raise ValueError("optim: rmsprop | adagrad | sgd | sgdm | sgdmom | adam (misc/optim_updates.lua)")
+        if cnn_optim not in binding.CNN_OPT_RULES:
+            raise ValueError("cnn_optim: sgd | sgdm | adam")
+        self.optim, self.cnn_optim = optim, cnn_optim
         if bf16:
             raise ValueError("bf16: the weak-paired auto-encoders have no bf16 operand mode (their step is launch-bound)")
         if dims.arch != binding.ARCH_AE2_WP:
@@ -407,12 +419,18 @@ class WeakPairedAETrainer:
         dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.seed, self.iter)
         loss = self.ctx.ae_wp_step(feats, tokens, enc_tokens=None if null else tokens, dropout=dr)
         lr, cnn_lr = self.current_lr()
-        norm, count = self.ctx.adam_update(lr, self.alpha, self.beta, self.eps, self.weight_decay, self.grad_clip, stats=True)
+        norm, count = _optim_update(self.ctx, self.optim, lr, self.learning_rate, self.alpha, self.beta, self.eps,
+                                    self.weight_decay, self.grad_clip)
         if self.finetuning():
             # wd then clamp, and only when cnn_weight_decay > 0, as the script's lossFun does (:318-322)
             clamp = self.grad_clip if self.cnn_weight_decay > 0 else 0.0
-            cnn_norm, cnn_count = self.ctx.ae_wp_projection_adam(cnn_lr, self.cnn_alpha, self.cnn_beta, self.eps,
-                                                                 self.cnn_weight_decay, clamp, stats=True)
+            if self.cnn_optim == "adam":  # its own entry point: the same kernel, state and bits as the rule OPT_ADAM
+                cnn_norm, cnn_count = self.ctx.ae_wp_projection_adam(cnn_lr, self.cnn_alpha, self.cnn_beta, self.eps,
+                                                                     self.cnn_weight_decay, clamp, stats=True)
+            else:
+                cnn_norm, cnn_count = self.ctx.ae_wp_projection_update(binding.CNN_OPT_RULES[self.cnn_optim], cnn_lr,
+                                                                       self.cnn_alpha, self.cnn_beta, self.eps,
+                                                                       self.cnn_weight_decay, clamp, stats=True)
             self._frozen_cnn_stats = None
         else:
             cnn_norm, cnn_count = self._cnn_stats_frozen()
@@ -467,8 +485,8 @@ WEAKPAIRED1_DEFAULTS = {"vgg": {"batch_size": 16, "I": 4096}, "inc": {"batch_siz
 
 class WeakPairedAE1Trainer:
     """The arch1 weak-paired script's loop on an NVQA_ARCH_AE1_WP context: the encoder-skip draw (:296-304), ae1_wp_step
-    (lossFun), the log line, the learning-rate decay and Adam over [encoder | decoder | multimodal] (clamp, then weight decay,
-    :335-341).  The lookup table is frozen and lives outside the flat vector.
+    (lossFun), the log line, the learning-rate decay and the -optim rule (default adam; AETrainer's six names, sgd undecayed as
+    there) over [encoder | decoder | multimodal] (clamp, then weight decay, :335-341).  The lookup table is frozen and lives outside the flat vector.
     dims: binding.Dims with arch = ARCH_AE1_WP, T = seq_length, L = 1, I = the CNN feature width, C = 2R, A = 0.
 
     The skip draw replaces Lua's `math.random() <= 0.5`, whose stream cannot be reproduced: a numpy generator seeded by
@@ -479,7 +497,10 @@ class WeakPairedAE1Trainer:
 
     def __init__(self, dims, device=0, variant="vgg", learning_rate=3e-5, learning_rate_decay_start=-1,
                  learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
-                 grad_clip=0.1, drop_prob=0.5, skip_prob=0.5, seed=123, bf16=False):
+                 grad_clip=0.1, drop_prob=0.5, skip_prob=0.5, seed=123, bf16=False, optim="adam"):
+        if optim not in binding.OPT_RULES:
+            raise ValueError("optim: rmsprop | adagrad | sgd | sgdm | sgdmom | adam (misc/optim_updates.lua)")
+        self.optim = optim
         if bf16:
             raise ValueError("bf16: the weak-paired auto-encoders have no bf16 operand mode (their step is launch-bound)")
         if dims.arch != binding.ARCH_AE1_WP:
@@ -586,8 +607,8 @@ class WeakPairedAE1Trainer:
             loss = self.ctx.ae1_wp_step(feats, tokens, enc_state=np.tile(self.mean_vector, (self.dims.B, 1)), dropout=dr)
         else:
             loss = self.ctx.ae1_wp_step(feats, tokens, enc_tokens=tokens, dropout=dr)
-        norm, count = self.ctx.adam_update(self.current_lr(), self.alpha, self.beta, self.eps, self.weight_decay, self.grad_clip,
-                                           stats=True)
+        norm, count = _optim_update(self.ctx, self.optim, self.current_lr(), self.learning_rate, self.alpha, self.beta, self.eps,
+                                    self.weight_decay, self.grad_clip)
         line = "iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f" % (self.iter, loss, count, norm)
         self.iter += 1
         return loss, count, norm, skip, line

@@ -16,6 +16,12 @@ COMM_ID_BYTES = 128
 
 
 ARCH1, ARCH2, ARCH_AE1, ARCH_AE2, ARCH_AE2_WP, ARCH_AE1_WP = 1, 2, 3, 4, 5, 6
+# NVQA_OPT_*: the update rules of misc/optim_updates.lua (Context.optim_update, Context.ae_wp_projection_update)
+OPT_SGD, OPT_SGDM, OPT_SGDMOM, OPT_ADAGRAD, OPT_RMSPROP, OPT_ADAM = 0, 1, 2, 3, 4, 5
+# the scripts' -optim / -cnn_optim names
+OPT_RULES = {"sgd": OPT_SGD, "sgdm": OPT_SGDM, "sgdmom": OPT_SGDMOM, "adagrad": OPT_ADAGRAD, "rmsprop": OPT_RMSPROP,
+             "adam": OPT_ADAM}
+CNN_OPT_RULES = {k: OPT_RULES[k] for k in ("sgd", "sgdm", "adam")}
 
 
 class NvqaError(RuntimeError):
@@ -88,12 +94,14 @@ SYMBOLS = {
     "nvqa_ae_evaluate_rows": (ctypes.c_int, [_vp, ctypes.c_int32, _i64p, _f32p, _i32p]),
     "nvqa_ae_step_routes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     "nvqa_adam_update": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
+    "nvqa_optim_update": (ctypes.c_int, [_vp, ctypes.c_int] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_ae_wp_step": (ctypes.c_int, [_vp, _f32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_wp_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _i32p, _f32p, _i32p]),
     "nvqa_ae_wp_set_projection": (ctypes.c_int, [_vp, _f32p, _f32p]),
     "nvqa_ae_wp_get_projection": (ctypes.c_int, [_vp, _f32p, _f32p]),
     "nvqa_ae_wp_get_projection_grads": (ctypes.c_int, [_vp, _f32p, _f32p]),
     "nvqa_ae_wp_projection_adam": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
+    "nvqa_ae_wp_projection_update": (ctypes.c_int, [_vp, ctypes.c_int] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_ae1_wp_step": (ctypes.c_int, [_vp, _f32p, _i32p, _f32p, _i32p, ctypes.POINTER(Dropout), _f32p, _f32p]),
     "nvqa_ae1_wp_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _i32p, _f32p, _i32p]),
     "nvqa_ae1_wp_encode": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p]),
@@ -354,6 +362,14 @@ class Context:
         self._check(self.lib.nvqa_adam_update(self._h, lr, beta1, beta2, eps, wd, clamp, _f32(out)))
         return (float(out[0]), int(out[1])) if stats else None
 
+    def optim_update(self, rule, lr, alpha=0.8, beta=0.999, eps=1e-8, wd=0.0, clamp=0.0, stats=False):
+        """nvqa_optim_update: clamp -> + wd x -> the rule (OPT_SGD .. OPT_ADAM, misc/optim_updates.lua) in one pass, on any
+        context; stats=True returns (paramsNorm, # updates) of the log line.  OPT_RMSPROP shares rmsprop_update's state and
+        bits, OPT_ADAM adam_update's."""
+        out = np.zeros(2, np.float32) if stats else None
+        self._check(self.lib.nvqa_optim_update(self._h, int(rule), lr, alpha, beta, eps, wd, clamp, _f32(out)))
+        return (float(out[0]), int(out[1])) if stats else None
+
     # ---- weak-paired auto-encoder (arch ARCH_AE2_WP) --------------------------------
     def ae_wp_step(self, feats, tokens, enc_tokens=None, dropout=None, want_loss=True):
         """nvqa_ae_wp_step: feats [B x I] (the frozen CNN body's output; the library L2-normalises its copy), tokens [B x D]
@@ -403,6 +419,13 @@ class Context:
         """+ wd x -> clamp -> adam on [W_p | b_p]; stats=True returns (||W_p||, # cnn updates) of the log line."""
         out = np.zeros(2, np.float32) if stats else None
         self._check(self.lib.nvqa_ae_wp_projection_adam(self._h, lr, beta1, beta2, eps, wd, clamp, _f32(out)))
+        return (float(out[0]), int(out[1])) if stats else None
+
+    def ae_wp_projection_update(self, rule, lr, alpha=0.8, beta=0.999, eps=1e-8, wd=0.0, clamp=0.0, stats=False):
+        """nvqa_ae_wp_projection_update: + wd x -> clamp -> OPT_SGD | OPT_SGDM | OPT_ADAM on [W_p | b_p] (-cnn_optim);
+        stats as ae_wp_projection_adam, whose state and bits OPT_ADAM shares."""
+        out = np.zeros(2, np.float32) if stats else None
+        self._check(self.lib.nvqa_ae_wp_projection_update(self._h, int(rule), lr, alpha, beta, eps, wd, clamp, _f32(out)))
         return (float(out[0]), int(out[1])) if stats else None
 
     # ---- arch1 weak-paired auto-encoder (arch ARCH_AE1_WP) --------------------------

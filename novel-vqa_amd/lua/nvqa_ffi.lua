@@ -71,6 +71,8 @@ int nvqa_ae_evaluate_rows(nvqa_ctx *ctx, int32_t n, const int64_t *rows, float *
 int nvqa_ae_step_routes(const nvqa_ctx *ctx, int64_t out[2]);
 int nvqa_adam_update(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                      float stats_out[2]);
+int nvqa_optim_update(nvqa_ctx *ctx, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
+                      float stats_out[2]);
 int nvqa_ae_wp_step(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
                     const nvqa_dropout *dropout, float *loss_out);
 int nvqa_ae_wp_evaluate(nvqa_ctx *ctx, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
@@ -80,6 +82,8 @@ int nvqa_ae_wp_get_projection(nvqa_ctx *ctx, float *w_out, float *b_out);
 int nvqa_ae_wp_get_projection_grads(nvqa_ctx *ctx, float *w_out, float *b_out);
 int nvqa_ae_wp_projection_adam(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                                float stats_out[2]);
+int nvqa_ae_wp_projection_update(nvqa_ctx *ctx, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
+                                 float stats_out[2]);
 int nvqa_ae1_wp_step(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const float *enc_state,
                      const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out);
 int nvqa_ae1_wp_evaluate(nvqa_ctx *ctx, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
@@ -122,6 +126,21 @@ function M.lptr(t) return ffi.cast('const int64_t*', t:data()) end
 function M.dropout(mode, p, seed, step)
   local d = ffi.new('nvqa_dropout'); d.mode = mode; d.p = p; d.seed = seed; d.step = step
   return d
+end
+
+-- -optim / -cnn_optim of the scripts of 001_train_autoencoder -> NVQA_OPT_* (misc/optim_updates.lua)
+M.OPT = {sgd = 0, sgdm = 1, sgdmom = 2, adagrad = 3, rmsprop = 4, adam = 5}
+M.CNN_OPT = {sgd = 0, sgdm = 1, adam = 5}
+
+-- The scripts' `perform a parameter update` block as one call: clamp, weight decay and the -optim rule in one pass, with the
+-- log line's statistics in stats = {paramsNorm, # updates}.  learning_rate is the decayed rate; sgd takes the undecayed
+-- opt.learning_rate, as every reference script passes it (sgd(params, grad_params, opt.learning_rate)).
+function M.optim_update(ctx, opt, learning_rate, stats)
+  local rule = M.OPT[opt.optim]
+  if rule == nil then error('bad option opt.optim (rmsprop | adagrad | sgd | sgdm | sgdmom | adam)') end
+  local lr = (opt.optim == 'sgd') and opt.learning_rate or learning_rate
+  check(M.lib.nvqa_optim_update(ctx, rule, lr, opt.optim_alpha, opt.optim_beta, opt.optim_epsilon, opt.weight_decay,
+                                opt.grad_clip, stats))
 end
 
 return M

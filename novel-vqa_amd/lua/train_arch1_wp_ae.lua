@@ -4,7 +4,7 @@ train_arch1_wp_ae.lua -- 001_train_autoencoder/004_train_arch1_weakpaired_autoen
 
 Same command-line options (:27-78, minus -backend / -language_eval / -cnn_proto / -cnn_model and the cnn optimiser's, whose
 body is frozen here; -img_average_path is dropped: the script loads that vector and never uses it), same learning-rate decay,
-update (clamp, then weight decay, :335-341) and stopping rules.  What changed:
+update (clamp, then weight decay, :335-341, then the -optim rule) and stopping rules.  What changed:
   * The CNN body is frozen and runs outside: -input_feats_h5 holds its output per caption, /feats/train and /feats/val
     [N x I], row i belonging to /labels/<split> row i.  DataLoaderWeakPaired's lockstep walk and wrap rule are kept.
   * AutoEncoder_vqa (misc/AutoEncoder_vqa_arch.lua), L2Normalize and LanguageModelCriterion are one library context of arch
@@ -40,10 +40,11 @@ cmd:option('-max_iters', -1, 'max number of iterations to run for (-1 = run fore
 cmd:option('-batch_size',16,'what is the batch size in number of sentences per batch?')
 cmd:option('-grad_clip',0.1,'clip gradients at this value')
 cmd:option('-drop_prob_ae', 0.5, 'strength of dropout in the AutoEncoder RNN')
+cmd:option('-optim','adam','what update to use? rmsprop|adagrad|sgd|sgdm|sgdmom|adam')
 cmd:option('-learning_rate',3e-5,'learning rate')
 cmd:option('-learning_rate_decay_start', -1, 'at what iteration to start decaying learning rate? (-1 = dont)')
 cmd:option('-learning_rate_decay_every', 50000, 'every how many iterations thereafter to drop LR by half?')
-cmd:option('-optim_alpha',0.8,'alpha for adam')
+cmd:option('-optim_alpha',0.8,'alpha for adagrad/rmsprop/momentum/adam')
 cmd:option('-optim_beta',0.999,'beta used for adam')
 cmd:option('-optim_epsilon',1e-8,'epsilon that goes into denominator for smoothing')
 cmd:option('-weight_decay', 1e-6, 'L2 regularization parameter')
@@ -184,8 +185,12 @@ while true do
   if iter > opt.learning_rate_decay_start and opt.learning_rate_decay_start >= 0 then
     learning_rate = learning_rate * math.pow(0.5, (iter - opt.learning_rate_decay_start) / opt.learning_rate_decay_every)
   end
-  nvqa.check(nvqa.lib.nvqa_adam_update(ctx, learning_rate, opt.optim_alpha, opt.optim_beta, opt.optim_epsilon,
-                                       opt.weight_decay, opt.grad_clip, stats))
+  if opt.optim == 'adam' then  -- the script's default keeps its own entry point: the same kernel, state and bits as the rule
+    nvqa.check(nvqa.lib.nvqa_adam_update(ctx, learning_rate, opt.optim_alpha, opt.optim_beta, opt.optim_epsilon,
+                                         opt.weight_decay, opt.grad_clip, stats))
+  else
+    nvqa.optim_update(ctx, opt, learning_rate, stats)
+  end
   print(string.format('iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f', iter, loss[0], stats[1], stats[0]))
   if iter % opt.save_checkpoint_every == 0 or iter == opt.max_iters then
     local val_loss = eval_split('val')

@@ -2,7 +2,7 @@
 train_arch2_wp_ae.lua -- 001_train_autoencoder/004_train_arch2_weakpaired_autoencoder_vgg.lua (and _inc.lua: -nhimage 2048,
 -learning_rate 3e-5) with the hot path on libnvqa.
 
-Same command-line options (:27-74, minus -backend / -language_eval / -cnn_proto / -cnn_model / -cnn_optim), same log line
+Same command-line options (:27-74, minus -backend / -language_eval / -cnn_proto / -cnn_model), same log line
 (:302-306), learning-rate decay (:443-451), updates (:453-467) and stopping rules (:470-478).  What changed:
   * The CNN body is frozen (-finetune_cnn_after only starts the update of its final Linear, the projection) and runs outside:
     -input_feats_h5 holds its output per caption, /feats/train and /feats/val [N x I] (vgg: post-ReLU fc7 as nvqa_vgg16_fc7
@@ -35,16 +35,18 @@ cmd:option('-max_iters', 22501, 'max number of iterations to run for (-1 = run f
 cmd:option('-batch_size',20,'what is the batch size in number of sentences per batch?')
 cmd:option('-grad_clip',0.1,'clip gradients at this value')
 cmd:option('-drop_prob_ae', 0.5, 'strength of dropout in the AutoEncoder RNN')
+cmd:option('-optim','adam','what update to use? rmsprop|adagrad|sgd|sgdm|sgdmom|adam')
 cmd:option('-learning_rate',1e-5,'learning rate')
 cmd:option('-learning_rate_decay_start', -1, 'at what iteration to start decaying learning rate? (-1 = dont)')
 cmd:option('-learning_rate_decay_every', 50000, 'every how many iterations thereafter to drop LR by half?')
-cmd:option('-optim_alpha',0.8,'alpha for adam')
+cmd:option('-optim_alpha',0.8,'alpha for adagrad/rmsprop/momentum/adam')
 cmd:option('-optim_beta',0.999,'beta used for adam')
 cmd:option('-optim_epsilon',1e-8,'epsilon that goes into denominator for smoothing')
 cmd:option('-weight_decay', 1e-6, 'L2 regularization parameter')
 cmd:option('-finetune_cnn_after', -1, 'After what iteration do we start updating the projection? (-1 = never)')
 cmd:option('-rand_val', 0.5, 'probability of feeding the null sentence to the encoder')
-cmd:option('-cnn_optim_alpha',0.8,'alpha for adam of the projection')
+cmd:option('-cnn_optim','adam','optimization to use for the projection: sgd|sgdm|adam')
+cmd:option('-cnn_optim_alpha',0.8,'alpha for momentum / adam of the projection')
 cmd:option('-cnn_optim_beta',0.999,'beta for adam of the projection')
 cmd:option('-cnn_learning_rate',1e-5,'learning rate for the projection')
 cmd:option('-cnn_weight_decay', 0, 'L2 weight decay just for the projection')
@@ -154,13 +156,24 @@ while true do
     learning_rate = learning_rate * decay_factor
     cnn_learning_rate = cnn_learning_rate * decay_factor
   end
-  nvqa.check(nvqa.lib.nvqa_adam_update(ctx, learning_rate, opt.optim_alpha, opt.optim_beta, opt.optim_epsilon,
-                                       opt.weight_decay, opt.grad_clip, stats))
+  if opt.optim == 'adam' then  -- the script's default keeps its own entry point: the same kernel, state and bits as the rule
+    nvqa.check(nvqa.lib.nvqa_adam_update(ctx, learning_rate, opt.optim_alpha, opt.optim_beta, opt.optim_epsilon,
+                                         opt.weight_decay, opt.grad_clip, stats))
+  else
+    nvqa.optim_update(ctx, opt, learning_rate, stats)
+  end
   if opt.finetune_cnn_after >= 0 and iter >= opt.finetune_cnn_after then
     local clamp = 0
     if opt.cnn_weight_decay > 0 then clamp = opt.grad_clip end                   -- wd, then clamp, as lossFun (:318-322)
-    nvqa.check(nvqa.lib.nvqa_ae_wp_projection_adam(ctx, cnn_learning_rate, opt.cnn_optim_alpha, opt.cnn_optim_beta,
-                                                   opt.optim_epsilon, opt.cnn_weight_decay, clamp, cnn_stats))
+    local cnn_rule = nvqa.CNN_OPT[opt.cnn_optim]
+    if cnn_rule == nil then error('bad option for opt.cnn_optim (sgd | sgdm | adam)') end
+    if opt.cnn_optim == 'adam' then  -- as for -optim: the default keeps its own entry point
+      nvqa.check(nvqa.lib.nvqa_ae_wp_projection_adam(ctx, cnn_learning_rate, opt.cnn_optim_alpha, opt.cnn_optim_beta,
+                                                     opt.optim_epsilon, opt.cnn_weight_decay, clamp, cnn_stats))
+    else
+      nvqa.check(nvqa.lib.nvqa_ae_wp_projection_update(ctx, cnn_rule, cnn_learning_rate, opt.cnn_optim_alpha, opt.cnn_optim_beta,
+                                                       opt.optim_epsilon, opt.cnn_weight_decay, clamp, cnn_stats))
+    end
     frozen_stats = nil
   else
     if frozen_stats == nil then                                                  -- a zero gradient: the zero entries count

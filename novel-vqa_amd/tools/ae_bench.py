@@ -22,10 +22,13 @@ NVQA_RCCL_LIB names -- on a one-GPU machine the stand-in tests/shim/libnccl_shim
 refused, since a real one would wait for the N - 1 ranks this tool never starts.  A second context of the same
 shape without a communicator is timed in the same job, the two alternating block by block; the line carries both
 ("ms_per_step" without, "ms_per_step_world" with the communicator), their difference and the communicator context's profile.
+--optim RULE: the update of every step is nvqa_optim_update of that rule of misc/optim_updates.lua (rmsprop | adagrad | sgd |
+sgdm | sgdmom | adam) with the scripts' alpha 0.8 / beta 0.999; the line then carries "optim".  The default, adam, runs
+nvqa_adam_update as ever.
 --resident (--arch 1 | 2, no --world): the same batches as one corpus in HBM (nvqa_ae_corpus_load), every step named by its row
 ids (nvqa_ae_step_rows); the line then carries "resident": 1.  Without the flag the tool runs as ever.
 
-    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--bf16] [--I 4096 --null-share 0.5] [--world N] [--resident]
+    python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--bf16] [--I 4096 --null-share 0.5] [--world N] [--resident] [--optim RULE]
                                            [--blocks 5 --steps 10 --warmup 5] [--out FILE]
 """
 import argparse
@@ -76,6 +79,7 @@ def main():
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--world", type=int, default=1)
     ap.add_argument("--resident", action="store_true")
+    ap.add_argument("--optim", default="adam", choices=("rmsprop", "adagrad", "sgd", "sgdm", "sgdmom", "adam"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.world < 1 or (a.world > 1 and a.arch not in (1, 2)):
@@ -154,7 +158,10 @@ def main():
             ctx.ae_step_rows(rows[k], dr, want_loss=False)
         else:
             ctx.ae_step(batches[k], dr, want_loss=False)
-        ctx.adam_update(lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
+        if a.optim == "adam":
+            ctx.adam_update(lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
+        else:
+            ctx.optim_update(b.OPT_RULES[a.optim], lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
 
     def timed_block(c):
         t0 = time.perf_counter()
@@ -233,6 +240,8 @@ def main():
         line.update(bf16=1, fraction_of_bf16_mfma_peak=round(fl / (ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4))
     if a.resident:
         line.update(resident=1)
+    if a.optim != "adam":
+        line.update(optim=a.optim)
     if a.arch in (5, 6):
         line.update(I=I, null_share=a.null_share, null_steps_timed=int(sum(null[i % null.size] for i in timed)))
     s = json.dumps(line)
