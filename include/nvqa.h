@@ -84,6 +84,16 @@ typedef struct nvqa_dropout {
     uint64_t step; /* iteration counter, mixed into every mask */
 } nvqa_dropout;
 
+/* Decoding options of nvqa_ae_sample / nvqa_ae_sample_rows: the opt table of sample(sents, opt)
+ * (001_train_autoencoder/misc/AutoEncoder_text_nostart.lua:134-139).  32 bytes. */
+typedef struct nvqa_sample_opts {
+    int32_t mode;        /* 0 = argmax (sample_max = 1), 1 = multinomial (sample_max = 0), 2 = beam (beam_size > 1) */
+    int32_t beam_size;   /* mode 2: 1..8; ignored otherwise */
+    float temperature;   /* mode 1: > 0; ignored otherwise */
+    int32_t pad_;        /* 0 */
+    uint64_t seed, step; /* mode 1: keys of the counter-based generator (nvqa_rng.h, NVQA_SITE_AE_SAMPLE) */
+} nvqa_sample_opts;
+
 typedef struct nvqa_ctx nvqa_ctx;
 
 /* ---- lifetime ------------------------------------------------------- */
@@ -320,6 +330,34 @@ int nvqa_ae_step_rows(nvqa_ctx *ctx, const int64_t *rows, const nvqa_dropout *dr
 int nvqa_ae_evaluate_rows(nvqa_ctx *ctx, int32_t n, const int64_t *rows, float *loss_out, int32_t *samples_out);
 /* out[0] = training steps fed from host tokens so far (nvqa_ae_step*), out[1] = training steps fed from the resident corpus */
 int nvqa_ae_step_routes(const nvqa_ctx *ctx, int64_t out[2]);
+/* Decoding of NVQA_ARCH_AE1 / NVQA_ARCH_AE2 contexts: sample(sents, opt) of
+ * misc/AutoEncoder_text_nostart.lua:134-210 (and the same block of misc/AutoEncoder.lua) with its second result, seqLogprobs.
+ * Evaluate mode; the encoder is fed as nvqa_ae_evaluate feeds it (0 -> 1, up to the batch's last non-null column), the decoder
+ * START and then its own picks.  n in 1..B rows; tokens [n x D]; images [n x E] or NULL (NVQA_ARCH_AE2; must be NULL on
+ * NVQA_ARCH_AE1); seq_out [n x D] 1-based tokens, V+1 = END; logprobs_out [n x D] (may be NULL); opts = NULL is mode 0.  f32 and
+ * the bf16 operand mode (the products are nvqa_ae_evaluate's; the selection always reads the f32 logits).  No collective is
+ * issued: rank-local on a data-parallel context.  Every bad argument -- mode outside 0..2, temperature <= 0 or not finite in
+ * mode 1, beam_size outside 1..8 or above V+1 or n beam_size > B in mode 2, n outside 1..B, images on NVQA_ARCH_AE1, V+1 > 16384
+ * or R not a multiple of 4 -- is an error before anything is launched, as is a weak-paired context (their *_evaluate decodes
+ * greedily).  No other entry point changes: nvqa_ae_evaluate* keeps its own argmax.
+ * With z the f32 logits row of a decoder step and l = z - logsumexp(z):
+ *   mode 0: the pick is the first maximum of z (the tokens equal nvqa_ae_evaluate's samples_out); logprobs_out = l[pick].
+ *   mode 1: w_c = exp((z_c - max z) / temperature); u = (h >> 8) 2^-24, h = nvqa_hash32 of (seed, step, NVQA_SITE_AE_SAMPLE, b D + s), b
+ *     the row in the caller's order and s = 0..D-1 the position; the pick is the smallest c with sum_{j<=c} w_j > u sum_j w_j
+ *     (the last c with w_c > 0 if rounding leaves none); logprobs_out = l[pick], untempered (logprobs:gather, :195).  The sums
+ *     run in a fixed order of the kernel's own: same input, same bits.
+ *   mode 2: a plain beam search, the library's own definition (the reference names sample_beam at :138 and does not ship it).
+ *     Each sentence keeps K = beam_size hypotheses on n K <= B decoder rows; a hypothesis' score is the sum of its tokens' l, no
+ *     length normalisation.  At position 0 only hypothesis 0 is expanded; from then on a live hypothesis k offers (k, c) with
+ *     score S_k + l_kc and a finished one (last token END) offers itself once, score unchanged, ranked as (k, END).  The K best
+ *     survive, ties to the smaller k (V+1) + c, ordered best first; a survivor takes its parent's state, tokens and log-probs.
+ *     After D positions seq_out / logprobs_out are hypothesis 0's tokens and their l, END included, zeros behind it.  With
+ *     K = 1 the tokens equal mode 0's up to and including the first END (mode 0, like the reference, decodes on behind it). */
+int nvqa_ae_sample(nvqa_ctx *ctx, int32_t n, const float *images, const int32_t *tokens, const nvqa_sample_opts *opts,
+                   int32_t *seq_out, float *logprobs_out);
+/* nvqa_ae_sample on rows[0..n) of the resident corpus (nvqa_ae_corpus_load; AE2: zero image rows) */
+int nvqa_ae_sample_rows(nvqa_ctx *ctx, int32_t n, const int64_t *rows, const nvqa_sample_opts *opts, int32_t *seq_out,
+                        float *logprobs_out);
 /* ---- weak-paired auto-encoder (NVQA_ARCH_AE2_WP contexts) ---- */
 /* 004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua with misc/AutoEncoderNull.lua.  The CNN body is frozen and runs
  * outside: feats [B x I] are its output (vgg: post-ReLU fc7 as nvqa_vgg16_fc7 returns it, I = 4096; inc: I = 2048).  The

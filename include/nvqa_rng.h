@@ -26,6 +26,9 @@
  *   NVQA_SITE_AE_TOP      decoder top h         idx = (b*(D+2) + s)*R + j
  *   NVQA_SITE_AE_LSTM     input of layer l >= 1 idx = (((k*L + l)*B + b)*(D+2) + t)*R + j   (encoder t = 0..D+1)
  * The weak-paired auto-encoder (NVQA_ARCH_AE2_WP) draws the NVQA_ARCH_AE2 masks with the same indices.
+ * Decoding (nvqa_ae_sample / nvqa_ae_sample_rows, mode 1; seed and step are nvqa_sample_opts'): no mask but the uniform of the
+ * multinomial draw, u = (hash32 >> 8) * 2^-24, one per emitted token (b = row in the caller's order, s = 0..D-1):
+ *   NVQA_SITE_AE_SAMPLE   sample position        idx = b*D + s
  */
 #ifndef NVQA_RNG_H
 #define NVQA_RNG_H
@@ -47,6 +50,7 @@
 #define NVQA_SITE_AE_DEC_LK 6u
 #define NVQA_SITE_AE_TOP 7u
 #define NVQA_SITE_AE_LSTM 8u
+#define NVQA_SITE_AE_SAMPLE 9u
 
 NVQA_HD uint32_t nvqa_hash32(uint64_t seed, uint64_t step, uint32_t site, uint64_t idx)
 {

@@ -1,5 +1,6 @@
 // ae.hip -- the text auto-encoder of the reference's first stage (NVQA_ARCH_AE1): training forward, LanguageModelCriterion,
-// backward, evaluate-mode loss and greedy decoding, and the fused clamp / weight-decay / Adam update (any context); the
+// backward, evaluate-mode loss and greedy decoding, sampling / beam decoding with log-probabilities (nvqa_ae_sample*, kernels
+// in ae_decode.h), and the fused clamp / weight-decay / Adam update (any context); the
 // arch2 text and weak-paired auto-encoders (NVQA_ARCH_AE2, NVQA_ARCH_AE2_WP) run the same code, below.
 //
 // Reference: 001_train_autoencoder/001_train_arch1_text_autoencoder.lua (lossFun :212-245, update :349-362, log line
@@ -47,6 +48,7 @@
 #include <vector>
 
 #include "ae_bridge.h"
+#include "ae_decode.h"
 #include "gemm_f32.h"
 #include "nvqa_ctx.h"
 #include "prof.h"
@@ -144,6 +146,16 @@ struct AeState {
     bool lk_dev = false;               // the current step's index was built on the device: nu / nch are lk_cnt's, not h_lk's
     hipEvent_t step_ev = nullptr;      // data parallel: the compute stream's position at the start of a resident step
     int64_t routes[2] = {0, 0};        // training steps fed from host tokens / from the resident corpus (nvqa_ae_step_routes)
+    // decoding (nvqa_ae_sample*; ae_decode.h), allocated on first use
+    float *slp = nullptr;              // [B x D] log-probabilities of the emitted tokens
+    float *bm_h[NVQA_MAX_LAYERS] = {}; // beam: [B][R] the state the next decoder step reads (the last step's, re-ordered)
+    float *bm_c[NVQA_MAX_LAYERS] = {};
+    int32_t *bm_bp = nullptr, *bm_tk = nullptr; // beam: [D][B] back-pointers (decoder rows) and tokens (0 behind END) per position
+    float *bm_lp = nullptr;            // beam: [D][B] their log-probabilities
+    float *bm_score = nullptr;         // beam: [B] the hypotheses' scores
+    int32_t *bm_fin = nullptr;         // beam: [B] 1 = the hypothesis has emitted END
+    float *bm_csc = nullptr, *bm_clp = nullptr; // beam: [B][NVQA_AE_BEAM_MAX] a row's best (score, log-prob, column)
+    int32_t *bm_cc = nullptr;
 };
 
 static int ae_alloc(void **p, size_t bytes)
@@ -1058,13 +1070,14 @@ void ae_destroy(nvqa_ctx *c)
     AeState &a = *c->ae;
     void *ptrs[] = {a.corpus, a.lk_hist, a.lk_base, a.lk_tot, a.lk_chb, a.lk_cnt, a.Htd16, a.G16, a.Wp16, a.WpT16, a.rowlse, a.rowtgt, a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
                     a.logits, a.rowloss, a.loss, a.dpw, a.slabs, a.colpart, a.img, a.etok, a.feat, a.wp_x, a.wp_g, a.wp_m, a.wp_v,
-                    a.wp_vel, a.wp_part, a.jbuf, a.qd, a.vd, a.qc, a.ic, a.dqp, a.dvp, a.dh0, a.dfeat, a.br_slabs};
+                    a.wp_vel, a.wp_part, a.jbuf, a.qd, a.vd, a.qc, a.ic, a.dqp, a.dvp, a.dh0, a.dfeat, a.br_slabs,
+                    a.slp, a.bm_bp, a.bm_tk, a.bm_lp, a.bm_score, a.bm_fin, a.bm_csc, a.bm_clp, a.bm_cc};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (a.staged) (void)hipEventDestroy(a.staged);
     if (a.step_ev) (void)hipEventDestroy(a.step_ev);
     for (int l = 0; l < NVQA_MAX_LAYERS; ++l)
-        for (void *p : {(void *)a.Gt[l], (void *)a.Hs[l], (void *)a.Cs[l], (void *)a.U[l]})
+        for (void *p : {(void *)a.Gt[l], (void *)a.Hs[l], (void *)a.Cs[l], (void *)a.U[l], (void *)a.bm_h[l], (void *)a.bm_c[l]})
             if (p) (void)hipFree(p);
     for (void *p : {(void *)a.h_lk, (void *)a.h_tok, (void *)a.h_loss, (void *)a.h_img, (void *)a.h_etok, (void *)a.h_feat, (void *)a.h_j})
         if (p) (void)hipHostFree(p);
@@ -1095,8 +1108,9 @@ static int ae_i2h(nvqa_ctx *c, int l, int q0, int q1, bool dec)
     return 0;
 }
 
-// recurrent step q of layer l: gates = (projection in Gt) + h_{q-1} W_h2h^T, fused cell (epilogues.h EpiLstmFwd)
-static int ae_fwd_step(nvqa_ctx *c, int l, int q, const Drop &dr)
+// recurrent step q of layer l: gates = (projection in Gt) + h_{q-1} W_h2h^T, fused cell (epilogues.h EpiLstmFwd).
+// h_from / c_from (beam search): the state the step reads, in place of slot q
+static int ae_fwd_step(nvqa_ctx *c, int l, int q, const Drop &dr, const float *h_from = nullptr, const float *c_from = nullptr)
 {
     AeState &a = *c->ae;
     const int B = c->d.B, R = c->d.R;
@@ -1106,13 +1120,13 @@ static int ae_fwd_step(nvqa_ctx *c, int l, int q, const Drop &dr)
     ProfScope ps(c, PF_AE_LSTM_FWD, h_in ? 2.0 * B * 4 * R * R : 0.0);
     EpiLstmFwd e = {};
     e.gx = a.Gt[l] + (size_t)q * B * 4 * R;
-    e.c_prev = a.Cs[l] + (size_t)sl * B * R;
+    e.c_prev = c_from ? c_from : a.Cs[l] + (size_t)sl * B * R;
     e.c = a.Cs[l] + (size_t)(sl + 1) * B * R;
     e.h = a.Hs[l] + (size_t)(sl + 1) * B * R;
     e.nrows = a.nrows;
     e.R = R; e.B = B; e.T = a.QM; e.t = q; e.lnext_m1 = l;
     e.dr = dr;
-    const float *hprev = a.Hs[l] + (size_t)sl * B * R;
+    const float *hprev = h_from ? h_from : a.Hs[l] + (size_t)sl * B * R;
     GemmArgs g = ae_args(hprev, R, c->P + w_h2h_of(c, l, dec), R, B, R, 0);
     g.R = R;
     g.A2 = hprev; g.lda2 = R; g.B2 = c->P + w_h2h_of(c, l, dec); g.ldb2 = R; g.K2 = h_in ? R : 0;
@@ -1788,7 +1802,166 @@ static int ae_rows_launch(nvqa_ctx *c, int n, const int64_t *rows, bool index)
     return 0;
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------
+// decoding: nvqa_ae_sample / nvqa_ae_sample_rows (ae_decode.h)
+// ------------------------------------------------------------------------------------------------------------------
+struct AeSample { int mode = 0, K = 1; float T = 1.f; uint64_t seed = 0, step = 0; };
+
+// every refusal of the two calls but those of the batch itself (tokens, rows), before anything is launched
+static int ae_sample_check(nvqa_ctx *c, const char *fn, int n, const nvqa_sample_opts *opts, bool images, const int32_t *seq_out,
+                           AeSample *o)
+{
+    NVQA_TRY(ae_check(c));
+    if (c->ae->feats) {
+        set_error("%s: not available on a weak-paired auto-encoder context (arch %d): nvqa_ae_wp_evaluate / nvqa_ae1_wp_evaluate decode "
+                  "greedily", fn, c->d.arch);
+        return -1;
+    }
+    const nvqa_dims &d = c->d;
+    if (!seq_out) { set_error("%s: seq_out is NULL", fn); return -1; }
+    if (n < 1 || n > d.B) { set_error("%s: n = %d outside 1..B (%d)", fn, n, d.B); return -1; }
+    if (images && d.arch != NVQA_ARCH_AE2) { set_error("%s: images on an NVQA_ARCH_AE1 context (the text auto-encoder takes none)", fn); return -1; }
+    if (opts) {
+        o->mode = opts->mode; o->K = opts->beam_size; o->T = opts->temperature; o->seed = opts->seed; o->step = opts->step;
+    }
+    if (o->mode < 0 || o->mode > 2) { set_error("%s: mode %d outside 0..2 (argmax, multinomial, beam)", fn, o->mode); return -1; }
+    if (o->mode == 1 && !(o->T > 0.f && std::isfinite(o->T))) { set_error("%s: temperature %g must be finite and > 0", fn, (double)o->T); return -1; }
+    if (o->mode == 2) {
+        if (o->K < 1 || o->K > NVQA_AE_BEAM_MAX) { set_error("%s: beam_size %d outside 1..%d", fn, o->K, NVQA_AE_BEAM_MAX); return -1; }
+        if (o->K > d.V + 1) { set_error("%s: beam_size %d above the V + 1 = %d classes", fn, o->K, d.V + 1); return -1; }
+        if ((int64_t)n * o->K > d.B) { set_error("%s: n beam_size = %d x %d decoder rows exceed B (%d)", fn, n, o->K, d.B); return -1; }
+    } else o->K = 1;
+    if (d.V + 1 > NVQA_AE_SEL_NT * 4 * NVQA_AE_SEL_MAXV4) {
+        set_error("%s: V + 1 = %d exceeds the %d columns the selection kernels hold in registers", fn, d.V + 1, NVQA_AE_SEL_NT * 4 * NVQA_AE_SEL_MAXV4);
+        return -1;
+    }
+    if (d.R % 4) { set_error("%s: R = %d is not a multiple of 4 (the state gather moves 16 bytes a thread)", fn, d.R); return -1; }
+    return 0;
+}
+
+static int ae_sample_alloc(nvqa_ctx *c, bool beam)
+{
+    AeState &a = *c->ae;
+    const size_t B = c->d.B, D = a.D, R = c->d.R;
+    if (a.slp && (!beam || a.bm_bp)) return 0;
+    if (!a.slp) AE_ALLOC(a.slp, B * D);
+    if (beam && !a.bm_bp) {
+        for (int l = 0; l < c->d.L; ++l) {
+            AE_ALLOC(a.bm_h[l], B * R);
+            AE_ALLOC(a.bm_c[l], B * R);
+        }
+        AE_ALLOC(a.bm_tk, D * B);
+        AE_ALLOC(a.bm_lp, D * B);
+        AE_ALLOC(a.bm_score, B);
+        AE_ALLOC(a.bm_fin, B);
+        AE_ALLOC(a.bm_csc, B * NVQA_AE_BEAM_MAX);
+        AE_ALLOC(a.bm_clp, B * NVQA_AE_BEAM_MAX);
+        AE_ALLOC(a.bm_cc, B * NVQA_AE_BEAM_MAX);
+        AE_ALLOC(a.bm_bp, D * B);
+    }
+    NVQA_HIP(hipDeviceSynchronize()); // (the zero fills ran on the null stream)
+    return 0;
+}
+
+// the selection kernels by the float4s a thread holds: 1 (V + 1 <= 1024), 4 (<= 4096), 16 (<= 16384)
+#define AE_SEL_DISPATCH(KERNEL, grid, ...)                                                                                    \
+    do {                                                                                                                      \
+        if (Vp1 <= NVQA_AE_SEL_NT * 4) hipLaunchKernelGGL(KERNEL<1>, grid, dim3(NVQA_AE_SEL_NT), 0, c->s, __VA_ARGS__);       \
+        else if (Vp1 <= NVQA_AE_SEL_NT * 16) hipLaunchKernelGGL(KERNEL<4>, grid, dim3(NVQA_AE_SEL_NT), 0, c->s, __VA_ARGS__); \
+        else hipLaunchKernelGGL(KERNEL<NVQA_AE_SEL_MAXV4>, grid, dim3(NVQA_AE_SEL_NT), 0, c->s, __VA_ARGS__);                 \
+    } while (0)
+
+// the batch in place (n rows; tmax / te set): the encoder exactly as ae_forward runs it -- the same launches on the same row
+// counts, so the state the decoder starts from has nvqa_ae_evaluate's bits -- then D decoder steps fed START and their own picks.
+// Nothing synchronises inside the loop; one copy per output at the end.
+static int ae_sample_run(nvqa_ctx *c, int32_t n, const AeSample &o, int32_t *seq_out, float *logprobs_out)
+{
+    AeState &a = *c->ae;
+    const nvqa_dims &d = c->d;
+    const int B = d.B, R = d.R, L = d.L, D = a.D, TE = a.te, Vp1 = d.V + 1, K = o.K, nK = n * K;
+    const bool beam = o.mode == 2;
+    const Drop dr = ae_drop(nullptr, false);
+    if (a.p16) { // this call's bf16 images of W_proj (ae_forward)
+        hipLaunchKernelGGL(k_ae_wproj_images, dim3((a.ld16 + 63) / 64, (R + 63) / 64), dim3(256), 0, c->s, c->P + c->lo.w_proj, Vp1, R,
+                           a.ld16, a.Wp16, a.WpT16);
+        NVQA_HIP(hipGetLastError());
+    }
+    NVQA_TRY(ae_embed(c, 0, TE, nullptr, dr));
+    for (int l = 0; l < L; ++l) {
+        if (l > 0) NVQA_TRY(ae_layer_input(c, l, 0, TE, dr));
+        NVQA_TRY(ae_i2h(c, l, 0, TE, false));
+        for (int q = 0; q < TE; ++q) NVQA_TRY(ae_fwd_step(c, l, q, dr));
+    }
+    const dim3 ggrid((unsigned)std::min<size_t>(((size_t)nK * (R / 4) + 255) / 256, 1024));
+    if (beam) { // sentence i's final encoder state (slot te, row i) to its K decoder rows
+        for (int l = 0; l < L; ++l)
+            hipLaunchKernelGGL(k_ae_beam_gather, ggrid, dim3(256), 0, c->s, (const float *)(a.Hs[l] + (size_t)TE * B * R),
+                               (const float *)(a.Cs[l] + (size_t)TE * B * R), a.bm_h[l], a.bm_c[l], (const int32_t *)nullptr, K, nK, R / 4);
+        NVQA_HIP(hipGetLastError());
+    }
+    for (int s = 0; s < D; ++s) {
+        const int q = TE + s;
+        const float *lg = a.logits + (size_t)s * B * a.ldl;
+        NVQA_TRY(ae_embed(c, q, q + 1, s == 0 ? nullptr : a.cur, dr));
+        for (int l = 0; l < L; ++l) {
+            if (l > 0) NVQA_TRY(ae_layer_input(c, l, q, q + 1, dr));
+            NVQA_TRY(ae_i2h(c, l, q, q + 1, true));
+            NVQA_TRY(ae_fwd_step(c, l, q, dr, beam ? a.bm_h[l] : nullptr, beam ? a.bm_c[l] : nullptr));
+        }
+        NVQA_TRY(ae_project(c, s, s + 1, dr));
+        if (!beam) {
+            AE_SEL_DISPATCH(k_ae_select, dim3(n), lg, a.ldl, Vp1, D, s, o.mode, o.T, o.seed, o.step, a.cur, a.samples, a.slp);
+            NVQA_HIP(hipGetLastError());
+            continue;
+        }
+        AE_SEL_DISPATCH(k_ae_beam_rows, dim3(nK), lg, a.ldl, Vp1, s, K, (const float *)a.bm_score, (const int32_t *)a.bm_fin, a.bm_csc,
+                        a.bm_clp, a.bm_cc);
+        hipLaunchKernelGGL(k_ae_beam_merge, dim3(n), dim3(64), 0, c->s, K, s, B, Vp1, (const float *)a.bm_csc, (const float *)a.bm_clp,
+                           (const int32_t *)a.bm_cc, a.bm_score, a.bm_fin, a.cur, a.bm_bp, a.bm_tk, a.bm_lp);
+        if (s + 1 < D) // the survivors' states: slot q + 1 (just written) through the back-pointers into the buffers step q + 1 reads
+            for (int l = 0; l < L; ++l)
+                hipLaunchKernelGGL(k_ae_beam_gather, ggrid, dim3(256), 0, c->s, (const float *)(a.Hs[l] + (size_t)(q + 1) * B * R),
+                                   (const float *)(a.Cs[l] + (size_t)(q + 1) * B * R), a.bm_h[l], a.bm_c[l],
+                                   (const int32_t *)(a.bm_bp + (size_t)s * B), K, nK, R / 4);
+        NVQA_HIP(hipGetLastError());
+    }
+    if (beam) {
+        hipLaunchKernelGGL(k_ae_beam_out, dim3((n + 63) / 64), dim3(64), 0, c->s, n, K, D, B, (const int32_t *)a.bm_bp,
+                           (const int32_t *)a.bm_tk, (const float *)a.bm_lp, a.samples, a.slp);
+        NVQA_HIP(hipGetLastError());
+    }
+    NVQA_HIP(hipMemcpyAsync(seq_out, a.samples, (size_t)n * D * 4, hipMemcpyDeviceToHost, c->s));
+    if (logprobs_out) NVQA_HIP(hipMemcpyAsync(logprobs_out, a.slp, (size_t)n * D * 4, hipMemcpyDeviceToHost, c->s));
+    NVQA_HIP(hipStreamSynchronize(c->s));
+    return 0;
+}
+
 } // namespace nvqa
+
+extern "C" int nvqa_ae_sample(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, const nvqa_sample_opts *opts,
+                              int32_t *seq_out, float *logprobs_out)
+{
+    AeSample o;
+    NVQA_TRY(ae_sample_check(c, "nvqa_ae_sample", n, opts, images != nullptr, seq_out, &o));
+    if (!tokens) { set_error("nvqa_ae_sample: tokens is NULL"); return -1; }
+    NVQA_TRY(ae_sample_alloc(c, o.mode == 2));
+    int ncount = 0;
+    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount));
+    return ae_sample_run(c, n, o, seq_out, logprobs_out);
+}
+
+extern "C" int nvqa_ae_sample_rows(nvqa_ctx *c, int32_t n, const int64_t *rows, const nvqa_sample_opts *opts, int32_t *seq_out,
+                                   float *logprobs_out)
+{
+    AeSample o;
+    NVQA_TRY(ae_sample_check(c, "nvqa_ae_sample_rows", n, opts, false, seq_out, &o));
+    int ncount = 0;
+    NVQA_TRY(ae_rows_plan(c, "nvqa_ae_sample_rows", n, rows, &ncount));
+    NVQA_TRY(ae_sample_alloc(c, o.mode == 2));
+    NVQA_TRY(ae_rows_launch(c, n, rows, false));
+    return ae_sample_run(c, n, o, seq_out, logprobs_out);
+}
 
 extern "C" int nvqa_ae_corpus_load(nvqa_ctx *c, int64_t n_rows, const int32_t *tokens)
 {

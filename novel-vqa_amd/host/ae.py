@@ -245,9 +245,35 @@ class AETrainer:
                     log(line)
         return losses
 
-    def eval_split(self, loader, split="val", val_sentences_use=-1):
+    def sample(self, batch_or_rows, sample_max=1, temperature=1.0, beam_size=1, seed=0, logprobs=False, step=0, images=None):
+        """sample(sents, opt) of misc/AutoEncoder_text_nostart.lua:134-210 under its option names: sample_max = 1 is the argmax,
+        or -- with beam_size > 1 -- the beam search (:138); sample_max = 0 draws from exp(logprobs / temperature), keyed by
+        (seed, step).  batch_or_rows: tokens [n x D], or a 1-d array of row ids of the resident corpus (load_corpus).  A beam
+        needs beam_size decoder rows per sentence, so more than B // beam_size sentences are decoded in several calls (the
+        multinomial draws are keyed by the row within a call: one call per B rows there).  Returns seq [n x D], or
+        (seq, seqLogprobs) with logprobs=True."""
+        x = np.asarray(batch_or_rows)
+        beam = sample_max == 1 and beam_size > 1
+        mode = binding.SAMPLE_BEAM if beam else (binding.SAMPLE_ARGMAX if sample_max == 1 else binding.SAMPLE_MULTINOMIAL)
+        opts = binding.SampleOpts(mode, int(beam_size), float(temperature), 0, int(seed), int(step))
+        per = max(1, self.dims.B // (int(beam_size) if beam else 1))
+        out = []
+        for i in range(0, x.shape[0], per):
+            if x.ndim == 1:
+                if getattr(self, "_resident", None) is None:
+                    raise ValueError("sample(rows) before load_corpus")
+                out.append(self.ctx.ae_sample_rows(x[i:i + per], opts, logprobs=True))
+            else:
+                img = None if images is None else np.asarray(images)[i:i + per]
+                out.append(self.ctx.ae_sample(x[i:i + per], opts, images=img, logprobs=True))
+        seq, lp = np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out])
+        return (seq, lp) if logprobs else seq
+
+    def eval_split(self, loader, split="val", val_sentences_use=-1, sample_opts=None):
         """eval_split (:148-194): mean of the per-batch evaluate-mode losses, stopping when the split wraps or (when
         val_sentences_use > 0) once that many sentences were used; predictions are the greedy decodes through ix_to_word.
+        sample_opts (a dict of sample()'s keywords; default None = the greedy path above, untouched): the predictions come from
+        sample(batch, **sample_opts) instead, the loss as ever.
         (The arch1 reference's counter `n` is never incremented there, so only the wrap ends its loop.)
         ARCH_AE2 (001_train_arch2_text_autoencoder.lua:192-195): n grows by batch_size after every batch and the loop
         ends once n >= val_sentences_use, so a non-positive val_sentences_use evaluates one batch, as there.
@@ -262,13 +288,15 @@ class AETrainer:
             if resident:
                 rows, bounds = loader.get_rows(split, self.dims.B, rank_stride=False)
                 batch = loader.corpus()[0][rows]
-                loss, samples = self.ctx.ae_evaluate_rows(rows, samples=True)
+                loss, samples = self.ctx.ae_evaluate_rows(rows, samples=sample_opts is None)
             else:
                 if getattr(loader, "world", 1) > 1:
                     batch, bounds = loader.get_batch(split, self.dims.B, rank_stride=False)
                 else:
                     batch, bounds = loader.get_batch(split, self.dims.B)
-                loss, samples = self.ctx.ae_evaluate(batch, samples=True)
+                loss, samples = self.ctx.ae_evaluate(batch, samples=sample_opts is None)
+            if sample_opts is not None:
+                samples = self.sample(rows if resident else batch, **{**sample_opts, "logprobs": False})
             losses.append(loss)
             for p, a in zip(decode_sequence(loader.ix_to_word, samples, end), decode_sequence(loader.ix_to_word, batch, end)):
                 used += 1

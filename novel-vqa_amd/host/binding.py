@@ -41,6 +41,17 @@ class Dropout(ctypes.Structure):
                 ("step", ctypes.c_uint64)]
 
 
+class SampleOpts(ctypes.Structure):
+    """nvqa_sample_opts: mode SAMPLE_ARGMAX | SAMPLE_MULTINOMIAL | SAMPLE_BEAM; beam_size (beam: 1..8), temperature (multinomial:
+    > 0), seed / step (multinomial: keys of the counter-based generator, site NVQA_SITE_AE_SAMPLE)."""
+
+    _fields_ = [("mode", ctypes.c_int32), ("beam_size", ctypes.c_int32), ("temperature", ctypes.c_float),
+                ("pad_", ctypes.c_int32), ("seed", ctypes.c_uint64), ("step", ctypes.c_uint64)]
+
+
+SAMPLE_ARGMAX, SAMPLE_MULTINOMIAL, SAMPLE_BEAM = 0, 1, 2
+
+
 # every symbol include/nvqa.h declares: name -> (restype, argtypes)
 _vp, _i32p, _f32p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -93,6 +104,8 @@ SYMBOLS = {
     "nvqa_ae_step_rows": (ctypes.c_int, [_vp, _i64p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_evaluate_rows": (ctypes.c_int, [_vp, ctypes.c_int32, _i64p, _f32p, _i32p]),
     "nvqa_ae_step_routes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "nvqa_ae_sample": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, ctypes.POINTER(SampleOpts), _i32p, _f32p]),
+    "nvqa_ae_sample_rows": (ctypes.c_int, [_vp, ctypes.c_int32, _i64p, ctypes.POINTER(SampleOpts), _i32p, _f32p]),
     "nvqa_adam_update": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_optim_update": (ctypes.c_int, [_vp, ctypes.c_int] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_ae_wp_step": (ctypes.c_int, [_vp, _f32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
@@ -349,6 +362,30 @@ class Context:
         loss = ctypes.c_float(0)
         self._check(self.lib.nvqa_ae_evaluate_rows(self._h, n, r.ctypes.data_as(_i64p), ctypes.byref(loss), _i32(out)))
         return float(loss.value), out
+
+    def ae_sample(self, tokens, opts=None, images=None, logprobs=False):
+        """nvqa_ae_sample: decode n = len(tokens) <= B rows by opts (SampleOpts; None = argmax).  Returns seq [n x D] (1-based,
+        V+1 = END; beam: zeros behind END), or (seq, log-probabilities [n x D] of the emitted tokens) with logprobs=True.
+        ARCH_AE2 only: images [n x E] (None = zeros)."""
+        d = self.dims
+        tokens = np.ascontiguousarray(tokens, np.int32).reshape(-1, d.T)
+        n = tokens.shape[0]
+        img = None if images is None else np.ascontiguousarray(images, np.float32).reshape(n, d.E)
+        seq = np.empty((n, d.T), np.int32)
+        lp = np.empty((n, d.T), np.float32) if logprobs else None
+        self._check(self.lib.nvqa_ae_sample(self._h, n, _f32(img), _i32(tokens), ctypes.byref(opts) if opts is not None else None,
+                                            _i32(seq), _f32(lp)))
+        return (seq, lp) if logprobs else seq
+
+    def ae_sample_rows(self, rows, opts=None, logprobs=False):
+        """nvqa_ae_sample_rows: ae_sample on n = len(rows) <= B rows of the resident corpus."""
+        r = np.ascontiguousarray(rows, np.int64).reshape(-1)
+        n = r.size
+        seq = np.empty((n, self.dims.T), np.int32)
+        lp = np.empty((n, self.dims.T), np.float32) if logprobs else None
+        self._check(self.lib.nvqa_ae_sample_rows(self._h, n, r.ctypes.data_as(_i64p), ctypes.byref(opts) if opts is not None else None,
+                                                 _i32(seq), _f32(lp)))
+        return (seq, lp) if logprobs else seq
 
     def ae_step_routes(self):
         """Training steps so far by where their batch came from: {'host': ae_step*, 'resident': ae_step_rows}."""

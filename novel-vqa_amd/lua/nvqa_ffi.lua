@@ -12,6 +12,7 @@ local ffi = require 'ffi'
 ffi.cdef[[
 typedef struct nvqa_dims { int32_t arch, B, T, V, E, R, L, I, C, A; } nvqa_dims;
 typedef struct nvqa_dropout { int32_t mode; float p; uint64_t seed; uint64_t step; } nvqa_dropout;
+typedef struct nvqa_sample_opts { int32_t mode; int32_t beam_size; float temperature; int32_t pad_; uint64_t seed, step; } nvqa_sample_opts;
 typedef struct nvqa_ctx nvqa_ctx;
 int nvqa_create(const nvqa_dims *dims, int device, nvqa_ctx **out);
 int nvqa_destroy(nvqa_ctx *ctx);
@@ -69,6 +70,10 @@ int nvqa_ae_corpus_load(nvqa_ctx *ctx, int64_t n_rows, const int32_t *tokens);
 int nvqa_ae_step_rows(nvqa_ctx *ctx, const int64_t *rows, const nvqa_dropout *dropout, float *loss_out);
 int nvqa_ae_evaluate_rows(nvqa_ctx *ctx, int32_t n, const int64_t *rows, float *loss_out, int32_t *samples_out);
 int nvqa_ae_step_routes(const nvqa_ctx *ctx, int64_t out[2]);
+int nvqa_ae_sample(nvqa_ctx *ctx, int32_t n, const float *images, const int32_t *tokens, const nvqa_sample_opts *opts,
+                   int32_t *seq_out, float *logprobs_out);
+int nvqa_ae_sample_rows(nvqa_ctx *ctx, int32_t n, const int64_t *rows, const nvqa_sample_opts *opts, int32_t *seq_out,
+                        float *logprobs_out);
 int nvqa_adam_update(nvqa_ctx *ctx, float lr, float beta1, float beta2, float eps, float wd, float clamp,
                      float stats_out[2]);
 int nvqa_optim_update(nvqa_ctx *ctx, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
@@ -126,6 +131,35 @@ function M.lptr(t) return ffi.cast('const int64_t*', t:data()) end
 function M.dropout(mode, p, seed, step)
   local d = ffi.new('nvqa_dropout'); d.mode = mode; d.p = p; d.seed = seed; d.step = step
   return d
+end
+
+-- sample(sents, opt) of misc/AutoEncoder_text_nostart.lua:134-210 on the library: opt.sample_max (default 1), opt.beam_size
+-- (default 1), opt.temperature (default 1.0) as there; opt.seed / opt.step key the multinomial draws.  sample_max = 1 with
+-- beam_size > 1 is the beam (:138).  sents: IntTensor [n x D]; imgs: FloatTensor [n x E] or nil (arch2 only).  Returns
+-- seq IntTensor [n x D] and seqLogprobs FloatTensor [n x D].
+function M.sample_opts(opt)
+  opt = opt or {}
+  local o = ffi.new('nvqa_sample_opts')
+  local sample_max, beam_size = opt.sample_max or 1, opt.beam_size or 1
+  o.mode = (sample_max == 1) and ((beam_size > 1) and 2 or 0) or 1
+  o.beam_size = beam_size; o.temperature = opt.temperature or 1.0; o.pad_ = 0
+  o.seed = opt.seed or 0; o.step = opt.step or 0
+  return o
+end
+
+function M.ae_sample(ctx, sents, opt, imgs)
+  local n, D = sents:size(1), sents:size(2)
+  local seq, lp = torch.IntTensor(n, D), torch.FloatTensor(n, D)
+  check(M.lib.nvqa_ae_sample(ctx, n, imgs and M.fptr(imgs) or nil, M.iptr(sents), M.sample_opts(opt), ffi.cast('int32_t*', seq:data()),
+                             M.fptr(lp)))
+  return seq, lp
+end
+
+function M.ae_sample_rows(ctx, rows, D, opt)
+  local n = rows:size(1)
+  local seq, lp = torch.IntTensor(n, D), torch.FloatTensor(n, D)
+  check(M.lib.nvqa_ae_sample_rows(ctx, n, M.lptr(rows), M.sample_opts(opt), ffi.cast('int32_t*', seq:data()), M.fptr(lp)))
+  return seq, lp
 end
 
 -- -optim / -cnn_optim of the scripts of 001_train_autoencoder -> NVQA_OPT_* (misc/optim_updates.lua)
