@@ -253,6 +253,17 @@ int nvqa_vgg16_set_precision(nvqa_vgg *vgg, int bf16);
 /* loadim's arithmetic (:50,65-69): bilinear scale of RGB [0,1] planes n x 3 x H x W to hw x hw,
  * x255, RGB->BGR, mean subtraction.  out: n x 3 x hw x hw. */
 int nvqa_vgg16_preprocess(nvqa_vgg *vgg, const float *rgb, int n, int H, int W, float *out);
+/* The raw-image route of the weak-paired scripts (004_train_arch{1,2}_weakpaired_autoencoder_vgg.lua with net_utils.prepro):
+ * images = n x 3 x S x S uint8 planar RGB as /images/<split> stores them.  One fused kernel cuts the hw x hw window whose
+ * 0-based origin is (xoff, yoff), 0 <= off <= S - hw (one origin for the batch; S == hw: no crop), converts to float, subtracts
+ * the RGB mean {123.68, 116.779, 103.939} and writes the network's input; the bytes the convolutions read are those
+ * nvqa_vgg16_fc7 reads from the same crop prepared on the host (BGR planes, mean-subtracted, float32).  body_dropout NULL or
+ * mode 0: evaluate mode, the bits of nvqa_vgg16_fc7.  mode 1: drop6 and drop7 (modules 35 and 38) are live, masks of
+ * nvqa_rng.h's NVQA_SITE_VGG_FC6 / NVQA_SITE_VGG_FC7 applied to the f32 value.  feats_out: n x F = module 38's output.
+ * An error, before anything is launched: S < hw, an origin outside 0..S-hw, n outside 1..max_batch or above the extractor's
+ * chunk size (NVQA_VGG_CHUNK, 256), no weights loaded, p outside [0, 1). */
+int nvqa_vgg16_fc7_raw(nvqa_vgg *vgg, const uint8_t *images, int n, int S, int xoff, int yoff,
+                       const nvqa_dropout *body_dropout, float *feats_out);
 
 /* The extractor run on the fly in front of the training step (BASELINE config "end-to-end"):
  * images [B x 3 x hw x hw] as loadim returns them -> fc7 -> row L2 norm (002_train_baseline.lua:117-121)
@@ -418,6 +429,27 @@ int nvqa_ae1_wp_encode(nvqa_ctx *ctx, int32_t n, const int32_t *enc_tokens, floa
 /* The frozen lookup table W_lk [(V+1) x E] (row V = START); no update ever touches it. */
 int nvqa_ae1_wp_set_lookup(nvqa_ctx *ctx, const float *w);
 int nvqa_ae1_wp_get_lookup(nvqa_ctx *ctx, float *w_out);
+/* ---- the weak-paired steps with the VGG-16 body in the loop ---- */
+/* The `cnn` forward of the weak-paired scripts in front of the step: images_u8 [B x 3 x S x S] (evaluate: [n x ...]), window
+ * origin and body_dropout as nvqa_vgg16_fc7_raw takes them.  The body runs on the extractor's stream; the context's stream
+ * waits for it and L2-normalises the features into the slot the host-fed call fills, and from there on the call IS
+ * nvqa_ae_wp_step / nvqa_ae_wp_evaluate / nvqa_ae1_wp_step / nvqa_ae1_wp_evaluate: the results are bit-equal to those calls
+ * given nvqa_vgg16_fc7_raw's features.  The features never visit the host; with loss_out = NULL (and dfeats_out = NULL) a step
+ * waits for nothing but the previous batch's host-to-device copies.  The body is frozen: dfeats_out stays d(loss)/d(f^).
+ * An error before anything is launched: what the host-fed call refuses, what nvqa_vgg16_fc7_raw refuses, a context of the
+ * other arch, an extractor whose feature width is not dims.I or that lives on another device. */
+int nvqa_ae_wp_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                           const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                           const nvqa_dropout *dropout, float *loss_out);
+int nvqa_ae_wp_evaluate_images(nvqa_ctx *ctx, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
+                               const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                               float *loss_out, int32_t *samples_out);
+int nvqa_ae1_wp_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                            const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const float *enc_state,
+                            const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out);
+int nvqa_ae1_wp_evaluate_images(nvqa_ctx *ctx, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                                float *loss_out, int32_t *samples_out);
 /* Valid on every context.  One pass over the flat vector: g = clamp(g, -clamp, clamp) (clamp > 0), g += wd * x, then
  * adam() of misc/optim_updates.lua:78-111 (step counter held by the context, reset by nvqa_init_params).
  * stats_out (may be NULL; synchronises) = {||x||_2, count(|lr g| >= 0.01 |x|)} of x before the update, g after clamp + wd

@@ -29,6 +29,10 @@
  * Decoding (nvqa_ae_sample / nvqa_ae_sample_rows, mode 1; seed and step are nvqa_sample_opts'): no mask but the uniform of the
  * multinomial draw, u = (hash32 >> 8) * 2^-24, one per emitted token (b = row in the caller's order, s = 0..D-1):
  *   NVQA_SITE_AE_SAMPLE   sample position        idx = b*D + s
+ * The VGG-16 body in training mode (nvqa_vgg16_fc7_raw and the weak-paired *_images steps with a body dropout; F = the fc width,
+ * b = image row in the caller's order; seed and step are the body dropout's own):
+ *   NVQA_SITE_VGG_FC6     drop6 (module 35)      idx = b*F + j
+ *   NVQA_SITE_VGG_FC7     drop7 (module 38)      idx = b*F + j
  */
 #ifndef NVQA_RNG_H
 #define NVQA_RNG_H
@@ -51,6 +55,8 @@
 #define NVQA_SITE_AE_TOP 7u
 #define NVQA_SITE_AE_LSTM 8u
 #define NVQA_SITE_AE_SAMPLE 9u
+#define NVQA_SITE_VGG_FC6 10u
+#define NVQA_SITE_VGG_FC7 11u
 
 NVQA_HD uint32_t nvqa_hash32(uint64_t seed, uint64_t step, uint32_t site, uint64_t idx)
 {

@@ -56,7 +56,25 @@
 
 using namespace nvqa;
 
+// vgg.hip: the raw-image route of the extractor with the features left on the device (the weak-paired *_images steps)
+struct nvqa_vgg;
+int nvqa_vgg_check_raw(const nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff,
+                       const nvqa_dropout *dr);
+int nvqa_vgg_forward_raw_device(nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff,
+                                const nvqa_dropout *dr, const float **feats_dev, hipStream_t *stream);
+int nvqa_vgg_features_taken(nvqa_vgg *v, hipStream_t consumer);
+void nvqa_vgg_where(const nvqa_vgg *v, int *device, int *F);
+
 namespace nvqa {
+
+// the body in front of a weak-paired step: where ae_upload takes the features from instead of the host
+struct AeBody {
+    nvqa_vgg *vgg;
+    const char *fn;
+    const uint8_t *images;
+    int S, xoff, yoff;
+    const nvqa_dropout *dr;
+};
 
 struct AeState {
     bool ae2 = false;    // NVQA_ARCH_AE2 (and AE2_WP): image row and START in front of the encoder's tokens
@@ -1467,9 +1485,12 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
 // host side of a batch: tokens -> device, tmax, the criterion's n, and (training) the token -> rows index of the lookup
 // gradient (a counting sort: deterministic row order per token).  AE2: images [n x E] (NULL: zeros) -> the device rows.
 // AE2_WP: enc_tokens [n x D] (NULL: the null sentence) -> etok and te = 2 + their tmax; feats [n x I] -> feat, L2-normalised
-// over the n rows (the padding rows stay zero).
+// over the n rows (the padding rows stay zero).  With `body` (feats is then NULL) the features come from the extractor, which
+// runs here, behind every check of the batch: its stream hands fc7o over by an event, the normalisation reads it straight into
+// feat, and the extractor's next pass waits for that read.
 static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *images, bool index, int *ncount,
-                     const float *feats = nullptr, const int32_t *enc_tokens = nullptr, const float *enc_state = nullptr)
+                     const float *feats = nullptr, const int32_t *enc_tokens = nullptr, const float *enc_state = nullptr,
+                     const AeBody *body = nullptr)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
@@ -1520,13 +1541,30 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *ima
             NVQA_HIP(hipMemcpyAsync(a.jbuf, a.h_j, (size_t)B * N * 4, hipMemcpyHostToDevice, c->s));
         }
         NVQA_HIP(hipMemcpyAsync(a.etok, a.h_etok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
-        memcpy(a.h_feat, feats, (size_t)n * I * 4);
-        if (n < B) memset(a.h_feat + (size_t)n * I, 0, (size_t)(B - n) * I * 4);
-        NVQA_HIP(hipMemcpyAsync(a.feat, a.h_feat, (size_t)B * I * 4, hipMemcpyHostToDevice, c->s));
-        NVQA_HIP(hipEventRecord(a.staged, c->s));
-        a.staged_rec = true;
-        ProfScope ps(c, a.bridge ? PF_AE1WP_BRIDGE_FWD : PF_AE_WP_PROJ_FWD, 0, (double)n * I * 12);
-        NVQA_TRY(l2norm_rows_launch(c->s, a.feat, n, (int)I));
+        if (body) {
+            NVQA_HIP(hipEventRecord(a.staged, c->s));
+            a.staged_rec = true;
+            const float *fdev = nullptr;
+            hipStream_t vs = nullptr;
+            NVQA_TRY(nvqa_vgg_forward_raw_device(body->vgg, body->fn, body->images, n, body->S, body->xoff, body->yoff, body->dr, &fdev, &vs));
+            if (!c->evStart) NVQA_HIP(hipEventCreateWithFlags(&c->evStart, hipEventDisableTiming)); // (nvqa_destroy releases it)
+            NVQA_HIP(hipEventRecord(c->evStart, vs));
+            NVQA_HIP(hipStreamWaitEvent(c->s, c->evStart, 0));
+            if (n < B) NVQA_HIP(hipMemsetAsync(a.feat + (size_t)n * I, 0, (size_t)(B - n) * I * 4, c->s));
+            {
+                ProfScope ps(c, a.bridge ? PF_AE1WP_BRIDGE_FWD : PF_AE_WP_PROJ_FWD, 0, (double)n * I * 12);
+                NVQA_TRY(l2norm_copy_launch(c->s, fdev, n, (int)I, a.feat));
+            }
+            NVQA_TRY(nvqa_vgg_features_taken(body->vgg, c->s));
+        } else {
+            memcpy(a.h_feat, feats, (size_t)n * I * 4);
+            if (n < B) memset(a.h_feat + (size_t)n * I, 0, (size_t)(B - n) * I * 4);
+            NVQA_HIP(hipMemcpyAsync(a.feat, a.h_feat, (size_t)B * I * 4, hipMemcpyHostToDevice, c->s));
+            NVQA_HIP(hipEventRecord(a.staged, c->s));
+            a.staged_rec = true;
+            ProfScope ps(c, a.bridge ? PF_AE1WP_BRIDGE_FWD : PF_AE_WP_PROJ_FWD, 0, (double)n * I * 12);
+            NVQA_TRY(l2norm_rows_launch(c->s, a.feat, n, (int)I));
+        }
     }
     a.img_live = a.ae2 && images;
     if (a.img_live) {
@@ -1672,12 +1710,12 @@ static int ae_dp_count(nvqa_ctx *c, int ncount, bool edge)
 
 static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out,
                         float *dimages_out, const float *feats = nullptr, const int32_t *enc_tokens = nullptr,
-                        const float *enc_state = nullptr, float *dfeats_out = nullptr)
+                        const float *enc_state = nullptr, float *dfeats_out = nullptr, const AeBody *body = nullptr)
 {
     if (!tokens) { set_error("tokens is NULL"); return -1; }
     const Drop dr = ae_drop(dropout, true);
     int ncount = 0;
-    NVQA_TRY(ae_upload(c, c->d.B, tokens, images, !c->ae->feats, &ncount, feats, enc_tokens, enc_state));
+    NVQA_TRY(ae_upload(c, c->d.B, tokens, images, !c->ae->feats, &ncount, feats, enc_tokens, enc_state, body));
     if (c->comm) NVQA_TRY(ae_dp_count(c, ncount, false));
     NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
     NVQA_TRY(ae_backward(c, dr, dfeats_out != nullptr));
@@ -1728,12 +1766,12 @@ static int ae_evaluate_run(nvqa_ctx *c, int32_t n, int ncount, float *loss_out, 
 }
 
 static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, float *loss_out, int32_t *samples_out,
-                            const float *feats = nullptr, const int32_t *enc_tokens = nullptr)
+                            const float *feats = nullptr, const int32_t *enc_tokens = nullptr, const AeBody *body = nullptr)
 {
     if (!tokens) { set_error("tokens is NULL"); return -1; }
     if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
     int ncount = 0;
-    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount, feats, enc_tokens));
+    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount, feats, enc_tokens, nullptr, body));
     return ae_evaluate_run(c, n, ncount, loss_out, samples_out);
 }
 
@@ -2155,6 +2193,64 @@ extern "C" int nvqa_ae1_wp_evaluate(nvqa_ctx *c, int32_t n, const float *feats, 
     NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_evaluate"));
     if (!feats || !enc_tokens) { set_error("nvqa_ae1_wp_evaluate: feats or enc_tokens is NULL"); return -1; }
     return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, feats, enc_tokens);
+}
+
+// ---- the weak-paired steps with the VGG-16 body in the loop ----
+// every refusal that concerns the extractor, before anything is launched (the batch's own are ae_upload's, which run first there)
+static int ae_check_body(nvqa_ctx *c, const AeBody &b, int n)
+{
+    if (!b.vgg) { set_error("%s: vgg is NULL", b.fn); return -1; }
+    if (n < 1 || n > c->d.B) { set_error("%s: n = %d outside 1..B (%d)", b.fn, n, c->d.B); return -1; }
+    int dev = 0, F = 0;
+    nvqa_vgg_where(b.vgg, &dev, &F);
+    if (F != c->d.I) { set_error("%s: extractor feature width %d != dims.I %d", b.fn, F, c->d.I); return -1; }
+    if (dev != c->device) { set_error("%s: the extractor lives on device %d, the context on device %d", b.fn, dev, c->device); return -1; }
+    return nvqa_vgg_check_raw(b.vgg, b.fn, b.images, n, b.S, b.xoff, b.yoff, b.dr);
+}
+
+extern "C" int nvqa_ae_wp_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                      const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                                      const nvqa_dropout *dropout, float *loss_out)
+{
+    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_step_images"));
+    const AeBody body{vgg, "nvqa_ae_wp_step_images", images_u8, S, xoff, yoff, body_dropout};
+    NVQA_TRY(ae_check_body(c, body, c->d.B));
+    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr, nullptr, enc_tokens, nullptr, nullptr, &body);
+}
+
+extern "C" int nvqa_ae_wp_evaluate_images(nvqa_ctx *c, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                          const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                                          float *loss_out, int32_t *samples_out)
+{
+    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_evaluate_images"));
+    const AeBody body{vgg, "nvqa_ae_wp_evaluate_images", images_u8, S, xoff, yoff, body_dropout};
+    NVQA_TRY(ae_check_body(c, body, n));
+    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, nullptr, enc_tokens, &body);
+}
+
+extern "C" int nvqa_ae1_wp_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                       const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const float *enc_state,
+                                       const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out)
+{
+    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_step_images"));
+    if ((enc_tokens != nullptr) == (enc_state != nullptr)) {
+        set_error("nvqa_ae1_wp_step_images: exactly one of enc_tokens and enc_state must be given");
+        return -1;
+    }
+    const AeBody body{vgg, "nvqa_ae1_wp_step_images", images_u8, S, xoff, yoff, body_dropout};
+    NVQA_TRY(ae_check_body(c, body, c->d.B));
+    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr, nullptr, enc_tokens, enc_state, dfeats_out, &body);
+}
+
+extern "C" int nvqa_ae1_wp_evaluate_images(nvqa_ctx *c, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                           const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                                           float *loss_out, int32_t *samples_out)
+{
+    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_evaluate_images"));
+    if (!enc_tokens) { set_error("nvqa_ae1_wp_evaluate_images: enc_tokens is NULL"); return -1; }
+    const AeBody body{vgg, "nvqa_ae1_wp_evaluate_images", images_u8, S, xoff, yoff, body_dropout};
+    NVQA_TRY(ae_check_body(c, body, n));
+    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, nullptr, enc_tokens, &body);
 }
 
 // the evaluate-mode encoder alone: [c_T | h_T] of the state slot te, joined by the bridge's prep kernel

@@ -739,6 +739,13 @@ int nvqa::l2norm_rows_launch(hipStream_t s, float *F, int n, int I)
     return 0;
 }
 
+int nvqa::l2norm_copy_launch(hipStream_t s, const float *src, int n, int I, float *dst)
+{
+    hipLaunchKernelGGL(k_l2norm_copy, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, src, n, I, dst);
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------
 // helpers: bias gradient = column sum, split-K wgrad
 // ------------------------------------------------------------------------------------
@@ -1659,6 +1666,7 @@ extern "C" int nvqa_step(nvqa_ctx *c, const int32_t *tokens, const int32_t *leng
 // returns them; the extractor's feature width must equal dims.I.
 struct nvqa_vgg;
 int nvqa_vgg_forward_device(nvqa_vgg *v, const float *images, int n, const float **feats_dev, int *F, hipStream_t *stream);
+int nvqa_vgg_features_taken(nvqa_vgg *v, hipStream_t consumer);
 
 extern "C" int nvqa_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const float *images, const int32_t *tokens,
                                 const int32_t *lengths, const int32_t *labels, const nvqa_dropout *dropout,
@@ -1679,6 +1687,8 @@ extern "C" int nvqa_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const float *images,
     NVQA_HIP(hipStreamWaitEvent(c->s, c->evStart, 0));
     hipLaunchKernelGGL(k_l2norm_copy, dim3((c->d.B + 3) / 4), dim3(256), 0, c->s, feats, c->d.B, c->d.I, c->img);
     NVQA_HIP(hipGetLastError());
+    // the extractor's next pass overwrites the features: it waits for this read (with loss_out = NULL nothing else orders them)
+    NVQA_TRY(nvqa_vgg_features_taken(vgg, c->s));
     return run_step(c, dropout, loss_out);
 }
 

@@ -25,6 +25,8 @@ int ae_comm_count(nvqa_ctx *c, float *cnt); // cnt[1] = sum over the ranks of cn
 int ae_comm_join(nvqa_ctx *c);              // closing exchange {status word, loss partial}; the compute stream waits for it
 // nvqa_api.hip: k_l2norm_rows (kernels.h) over rows [0, n) of F [n x I] in place (the weak-paired auto-encoder's features)
 int l2norm_rows_launch(hipStream_t s, float *F, int n, int I);
+// nvqa_api.hip: k_l2norm_copy (kernels.h), the same arithmetic from src [n x I] into dst (features handed over on the device)
+int l2norm_copy_launch(hipStream_t s, const float *src, int n, int I, float *dst);
 
 #define NVQA_HIP(expr)                                                                           \
     do {                                                                                         \

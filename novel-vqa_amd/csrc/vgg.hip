@@ -65,6 +65,21 @@ __global__ void k_nchw_to_nhwc4(const float *in, int n, int H, int W, float4 *ou
     out[i] = make_float4(src[0], src[hw], src[2 * hw], 0.f);
 }
 
+// The raw-image front end (net_utils.prepro of the weak-paired scripts): uint8 planar RGB [n][3][S][S], the hw x hw window at
+// (xoff, yoff) of every image, float, minus the RGB mean {123.68, 116.779, 103.939} (one rounded subtraction), written as the
+// network's NHWC4 input in its channel order (B, G, R, 0): the bits k_nchw_to_nhwc4 makes of the same crop prepared on the host.
+__global__ void k_prepro_u8_nhwc4(const uint8_t *in, int n, int S, int hw, int xoff, int yoff, float4 *out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t win = (size_t)hw * hw, plane = (size_t)S * S;
+    if (i >= n * win) return;
+    const size_t img = i / win, p = i % win;
+    const int y = (int)(p / hw), x = (int)(p % hw);
+    const uint8_t *src = in + img * 3 * plane + (size_t)(yoff + y) * S + (xoff + x);
+    out[i] = make_float4(__fsub_rn((float)src[2 * plane], 103.939f), __fsub_rn((float)src[plane], 116.779f),
+                         __fsub_rn((float)src[0], 123.68f), 0.f);
+}
+
 // 2x2 max pool, stride 2, NHWC, C % 4 == 0
 __global__ void k_maxpool2_nhwc(const float4 *in, int n, int H, int W, int C4, float4 *out)
 {
@@ -127,6 +142,18 @@ __global__ void k_fc_finish(const float *slabs, int S, int M, int N, const float
     float s = 0.f;
     for (int z = 0; z < S; ++z) s += slabs[(size_t)z * M * N + i];
     out[i] = fmaxf(s + bias[i % N], 0.0f);
+}
+
+// the training-mode form (drop6 / drop7 live): the same sum, bias and ReLU, times the mask of element b * N + j of `site`
+// (nvqa_rng.h), applied to the f32 value before anything rounds it
+__global__ void k_fc_finish_drop(const float *slabs, int S, int M, int N, const float *bias, float *out, uint64_t seed,
+                                 uint64_t step, uint32_t site, float p, float inv_keep)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)M * N) return;
+    float s = 0.f;
+    for (int z = 0; z < S; ++z) s += slabs[(size_t)z * M * N + i];
+    out[i] = nvqa_dropout_scale(seed, step, site, i, p, inv_keep) * fmaxf(s + bias[i % N], 0.0f);
 }
 
 // One output sample of Torch's image.scale 1-D pass (torch/image generic/image.c: image_(Main_scaleLinear_rowcol); the
@@ -234,6 +261,16 @@ struct nvqa_vgg {
     hipStream_t sc = nullptr;
     hipEvent_t evCopy[2] = {}, evDone = nullptr; // chunk on the device / last forward finished with v->img
     bool done_rec = false;
+    // the raw-image route (nvqa_vgg16_fc7_raw and the weak-paired steps): the uint8 batch on the device, grown on demand
+    // and its pinned staging, so that the copy is asynchronous: a call waits only for the previous batch's copy (evRaw)
+    uint8_t *raw = nullptr, *h_raw = nullptr;
+    size_t raw_bytes = 0;
+    hipEvent_t evRaw = nullptr;
+    bool raw_rec = false;
+    // a consumer on another stream (nvqa_ae_wp_step_images) has taken its copy of fc7o: the next pass, which overwrites fc7o
+    // and the activation buffers, waits for it
+    hipEvent_t evTaken = nullptr;
+    bool taken_rec = false;
     int chunk = 256; // measured at B = 512 (configs[4]): one shot 142.0 ms, chunks of 256 140.1, of 128 143.2 (smaller launches fill the chip worse)
 };
 
@@ -284,6 +321,8 @@ extern "C" int nvqa_vgg16_create(int device, int width_div, int input_hw, int ma
         NVQA_HIP(hipEventCreateWithFlags(&v->evCopy[p], hipEventDisableTiming));
     }
     NVQA_HIP(hipEventCreateWithFlags(&v->evDone, hipEventDisableTiming));
+    NVQA_HIP(hipEventCreateWithFlags(&v->evTaken, hipEventDisableTiming));
+    NVQA_HIP(hipEventCreateWithFlags(&v->evRaw, hipEventDisableTiming));
     { const int n = env_int("NVQA_VGG_CHUNK", 0); if (n > 0) v->chunk = n; }
     for (int i = 0; i < 13; ++i) {
         NVQA_HIP(hipMalloc((void **)&v->Wc[i], (size_t)v->cout[i] * 9 * v->cinp[i] * 4));
@@ -320,6 +359,10 @@ extern "C" int nvqa_vgg16_destroy(nvqa_vgg *v)
         if (v->evCopy[p]) (void)hipEventDestroy(v->evCopy[p]);
     }
     if (v->evDone) (void)hipEventDestroy(v->evDone);
+    if (v->evTaken) (void)hipEventDestroy(v->evTaken);
+    if (v->evRaw) (void)hipEventDestroy(v->evRaw);
+    if (v->raw) (void)hipFree(v->raw);
+    if (v->h_raw) (void)hipHostFree(v->h_raw);
     if (v->sc) (void)hipStreamDestroy(v->sc);
     (void)hipStreamDestroy(v->s);
     delete v;
@@ -380,7 +423,9 @@ extern "C" int nvqa_vgg16_set_weights(nvqa_vgg *v, const float *flat)
 }
 
 // b16: x and W are bf16 arrays (the gfx950 form of fc6); K counts their elements
-static int fc_layer(nvqa_vgg *v, const float *x, int M, int K, const float *W, const float *b, float *out, bool b16 = false)
+// dr (mode 1): the output goes through the Dropout behind the layer's ReLU, masks of `site`
+static int fc_layer(nvqa_vgg *v, const float *x, int M, int K, const float *W, const float *b, float *out, bool b16 = false,
+                    const Drop *dr = nullptr, uint32_t site = 0)
 {
     const int N = v->F;
     if (b16) K /= 2; // storage floats
@@ -394,17 +439,30 @@ static int fc_layer(nvqa_vgg *v, const float *x, int M, int K, const float *W, c
     if (b16) NVQA_HIP((launch_gemm<CfgFcB, A_KC, B_KC, false, EpiSlab>(v->s, g, EpiSlab{v->slabs, N, (size_t)M * N})));
     else if (v->bf16) NVQA_HIP((launch_gemm<WithBF<CfgFc>::type, A_KC, B_KC, false, EpiSlab>(v->s, g, EpiSlab{v->slabs, N, (size_t)M * N})));
     else NVQA_HIP((launch_gemm<CfgFc, A_KC, B_KC, false, EpiSlab>(v->s, g, EpiSlab{v->slabs, N, (size_t)M * N})));
-    hipLaunchKernelGGL(k_fc_finish, dim3(((size_t)M * N + 255) / 256), dim3(256), 0, v->s, v->slabs, ks, M, N, b, out);
+    if (dr && dr->mode)
+        hipLaunchKernelGGL(k_fc_finish_drop, dim3(((size_t)M * N + 255) / 256), dim3(256), 0, v->s, v->slabs, ks, M, N, b, out, dr->seed,
+                           dr->step, site, dr->p, dr->inv_keep);
+    else hipLaunchKernelGGL(k_fc_finish, dim3(((size_t)M * N + 255) / 256), dim3(256), 0, v->s, v->slabs, ks, M, N, b, out);
     NVQA_HIP(hipGetLastError());
     return 0;
 }
 
-// the network on n images that are already on the device (img [n][3][hw][hw]); post-ReLU fc7 features -> out [n x F]
-static int vgg_network(nvqa_vgg *v, const float *img, int n, float *out)
+// where the raw-image route takes its input from: uint8 planar RGB [n][3][S][S] on the device and the window's origin
+struct RawSrc {
+    const uint8_t *u8;
+    int S, xoff, yoff;
+};
+
+// the network on n images that are already on the device (img [n][3][hw][hw], or raw); post-ReLU fc7 features -> out [n x F],
+// with dr (mode 1) module 38's training-mode output: drop6 and drop7 live
+static int vgg_network(nvqa_vgg *v, const float *img, int n, float *out, const RawSrc *raw = nullptr, const Drop *dr = nullptr)
 {
     int H = v->hw, W = v->hw;
     const size_t px = (size_t)n * H * W;
-    hipLaunchKernelGGL(k_nchw_to_nhwc4, dim3((px + 255) / 256), dim3(256), 0, v->s, img, n, H, W, reinterpret_cast<float4 *>(v->nhwc_in));
+    if (raw)
+        hipLaunchKernelGGL(k_prepro_u8_nhwc4, dim3((px + 255) / 256), dim3(256), 0, v->s, raw->u8, n, raw->S, v->hw, raw->xoff, raw->yoff,
+                           reinterpret_cast<float4 *>(v->nhwc_in));
+    else hipLaunchKernelGGL(k_nchw_to_nhwc4, dim3((px + 255) / 256), dim3(256), 0, v->s, img, n, H, W, reinterpret_cast<float4 *>(v->nhwc_in));
     const float *cur = v->nhwc_in;
     int which = 0;
     for (int i = 0; i < 13; ++i) {
@@ -470,9 +528,10 @@ static int vgg_network(nvqa_vgg *v, const float *img, int n, float *out)
     }
     NVQA_HIP(hipGetLastError());
     const int c5p = (v->c5 + 3) / 4 * 4;
-    if (v->g950) NVQA_TRY(fc_layer(v, cur, n, v->s5 * v->s5 * c5p, reinterpret_cast<const float *>(v->Wf16), v->bf[0], v->fc6o, true));
-    else NVQA_TRY(fc_layer(v, cur, n, v->s5 * v->s5 * c5p, v->Wf[0], v->bf[0], v->fc6o)); // fc6 + ReLU (Dropout = identity)
-    NVQA_TRY(fc_layer(v, v->fc6o, n, v->F, v->Wf[1], v->bf[1], out));                  // fc7 + ReLU -> module 38
+    // fc6 + ReLU, fc7 + ReLU -> module 38 (the two Dropouts: identity without dr)
+    if (v->g950) NVQA_TRY(fc_layer(v, cur, n, v->s5 * v->s5 * c5p, reinterpret_cast<const float *>(v->Wf16), v->bf[0], v->fc6o, true, dr, NVQA_SITE_VGG_FC6));
+    else NVQA_TRY(fc_layer(v, cur, n, v->s5 * v->s5 * c5p, v->Wf[0], v->bf[0], v->fc6o, false, dr, NVQA_SITE_VGG_FC6));
+    NVQA_TRY(fc_layer(v, v->fc6o, n, v->F, v->Wf[1], v->bf[1], out, false, dr, NVQA_SITE_VGG_FC7));
     return 0;
 }
 
@@ -485,6 +544,7 @@ static int vgg_forward(nvqa_vgg *v, const float *images, int n)
     if (!v->have_weights) { set_error("nvqa_vgg16_fc7 before nvqa_vgg16_set_weights"); return -1; }
     if (n < 1 || n > v->max_batch) { set_error("n=%d outside 1..%d", n, v->max_batch); return -1; }
     NVQA_HIP(hipSetDevice(v->device));
+    if (v->taken_rec) NVQA_HIP(hipStreamWaitEvent(v->s, v->evTaken, 0));
     const size_t per = (size_t)3 * v->hw * v->hw;
     if (n <= v->chunk) {
         NVQA_HIP(hipMemcpyAsync(v->img, images, (size_t)n * per * 4, hipMemcpyHostToDevice, v->s));
@@ -530,6 +590,92 @@ int nvqa_vgg_forward_device(nvqa_vgg *v, const float *images, int n, const float
     *F = v->F;
     *stream = v->s;
     return 0;
+}
+
+// every refusal of the raw-image route; nothing is launched or allocated
+int nvqa_vgg_check_raw(const nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff,
+                       const nvqa_dropout *dr)
+{
+    if (!v || !images) { set_error("%s: NULL argument", fn); return -1; }
+    if (!v->have_weights) { set_error("%s before nvqa_vgg16_set_weights", fn); return -1; }
+    if (n < 1 || n > v->max_batch) { set_error("%s: n=%d outside 1..%d", fn, n, v->max_batch); return -1; }
+    if (n > v->chunk) { set_error("%s: n=%d above the extractor's chunk size %d (the raw-image route runs one pass)", fn, n, v->chunk); return -1; }
+    if (S < v->hw) { set_error("%s: source size S=%d below the network's input %d", fn, S, v->hw); return -1; }
+    if (xoff < 0 || yoff < 0 || xoff > S - v->hw || yoff > S - v->hw) {
+        set_error("%s: window origin (%d, %d) outside 0..%d", fn, xoff, yoff, S - v->hw);
+        return -1;
+    }
+    if (dr && dr->mode != 0) {
+        if (dr->mode != 1) { set_error("%s: dropout mode %d (0 off, 1 seeded)", fn, dr->mode); return -1; }
+        if (!(dr->p >= 0.f && dr->p < 1.f)) { set_error("%s: dropout p=%g outside [0, 1)", fn, (double)dr->p); return -1; }
+    }
+    return 0;
+}
+
+// forward of n raw host images through the fused front end; the features (module 38's output) stay in v->fc7o [n x F]
+static int vgg_forward_raw(nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff, const nvqa_dropout *dr)
+{
+    NVQA_TRY(nvqa_vgg_check_raw(v, fn, images, n, S, xoff, yoff, dr));
+    NVQA_HIP(hipSetDevice(v->device));
+    const size_t bytes = (size_t)n * 3 * S * S;
+    if (bytes > v->raw_bytes) { // the old buffers may still feed the last pass
+        NVQA_HIP(hipStreamSynchronize(v->s));
+        if (v->raw) (void)hipFree(v->raw);
+        if (v->h_raw) (void)hipHostFree(v->h_raw);
+        v->raw = v->h_raw = nullptr; v->raw_bytes = 0; v->raw_rec = false;
+        NVQA_HIP(hipMalloc((void **)&v->raw, bytes));
+        NVQA_HIP(hipHostMalloc((void **)&v->h_raw, bytes, hipHostMallocDefault));
+        v->raw_bytes = bytes;
+    }
+    if (v->raw_rec) NVQA_HIP(hipEventSynchronize(v->evRaw)); // the staging buffer is free again
+    memcpy(v->h_raw, images, bytes);
+    if (v->taken_rec) NVQA_HIP(hipStreamWaitEvent(v->s, v->evTaken, 0));
+    NVQA_HIP(hipMemcpyAsync(v->raw, v->h_raw, bytes, hipMemcpyHostToDevice, v->s));
+    NVQA_HIP(hipEventRecord(v->evRaw, v->s));
+    v->raw_rec = true;
+    Drop d = {};
+    if (dr && dr->mode) { d.mode = 1; d.p = dr->p; d.inv_keep = 1.0f / (1.0f - dr->p); d.seed = dr->seed; d.step = dr->step; }
+    const RawSrc raw{v->raw, S, xoff, yoff};
+    NVQA_TRY(vgg_network(v, nullptr, n, v->fc7o, &raw, d.mode ? &d : nullptr));
+    NVQA_HIP(hipEventRecord(v->evDone, v->s));
+    v->done_rec = true;
+    return 0;
+}
+
+// images: n x 3 x S x S uint8 planar RGB as /images/<split> stores them; the hw x hw window at (xoff, yoff) of each, minus the
+// RGB mean, through the network; body_dropout (mode 1): drop6 / drop7 live (sites NVQA_SITE_VGG_FC6 / _FC7)
+extern "C" int nvqa_vgg16_fc7_raw(nvqa_vgg *v, const uint8_t *images, int n, int S, int xoff, int yoff,
+                                  const nvqa_dropout *body_dropout, float *feats_out)
+{
+    if (!feats_out) { set_error("nvqa_vgg16_fc7_raw: NULL argument"); return -1; }
+    NVQA_TRY(vgg_forward_raw(v, "nvqa_vgg16_fc7_raw", images, n, S, xoff, yoff, body_dropout));
+    NVQA_HIP(hipMemcpyAsync(feats_out, v->fc7o, (size_t)n * v->F * 4, hipMemcpyDeviceToHost, v->s));
+    NVQA_HIP(hipStreamSynchronize(v->s));
+    return 0;
+}
+
+// used by the weak-paired steps (ae.hip): the raw-image route with the features left on the device
+int nvqa_vgg_forward_raw_device(nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff,
+                                const nvqa_dropout *dr, const float **feats_dev, hipStream_t *stream)
+{
+    NVQA_TRY(vgg_forward_raw(v, fn, images, n, S, xoff, yoff, dr));
+    *feats_dev = v->fc7o;
+    *stream = v->s;
+    return 0;
+}
+
+// a consumer on `consumer` has enqueued its last read of the features: the next pass waits for that point
+int nvqa_vgg_features_taken(nvqa_vgg *v, hipStream_t consumer)
+{
+    NVQA_HIP(hipEventRecord(v->evTaken, consumer));
+    v->taken_rec = true;
+    return 0;
+}
+
+void nvqa_vgg_where(const nvqa_vgg *v, int *device, int *F)
+{
+    *device = v->device;
+    *F = v->F;
 }
 
 extern "C" int nvqa_vgg16_set_precision(nvqa_vgg *v, int bf16)

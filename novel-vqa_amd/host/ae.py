@@ -5,7 +5,8 @@ reads (002_convert_text_model_arch1.lua:27-39; arch2: the table of lua/convert_a
 The weak-paired auto-encoder of the second stage (004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua) runs on an
 NVQA_ARCH_AE2_WP context: WeakPairedDataLoader and WeakPairedAETrainer; its arch1 counterpart
 (004_train_arch1_weakpaired_autoencoder_{vgg,inc}.lua, misc/AutoEncoder_vqa_arch.lua) on an NVQA_ARCH_AE1_WP context:
-WeakPairedAE1Trainer."""
+WeakPairedAE1Trainer.  Both take the features from the host, or -- with body=Vgg16 and a WeakPairedImageLoader -- run the
+VGG-16 body on raw uint8 images inside the step, as the *_vgg scripts do (train_step_images)."""
 import json
 
 import numpy as np
@@ -357,11 +358,113 @@ class WeakPairedDataLoader(DataLoader):
         return labels, self.feats[split][rows], bounds
 
 
+class WeakPairedImageLoader(DataLoader):
+    """misc/DataLoaderWeakPaired.lua as the *_vgg scripts use it (:60-103): captions `labels/<split>` and the raw images
+    `/images/<split>` ([N x 3 x S x S] uint8) walked linearly in lockstep, with DataLoader's wrap-around.
+    images: {split: an array, or (h5 file path or h5.File, dataset name)}; a dataset is never read whole, only the rows of a
+    batch (h5.File.read_rows, one call per run of consecutive rows: two on a wrap)."""
+
+    def __init__(self, labels, images, ix_to_word=None, json_file=None):
+        super().__init__(labels=labels, ix_to_word=ix_to_word, json_file=json_file)
+        self.images, self._files = {}, []
+        for k, v in images.items():
+            if isinstance(v, tuple):
+                f, name = v
+                if isinstance(f, str):
+                    f = h5.File(f)
+                    self._files.append(f)
+                shape, dt = f.shape(name), f.dtype(name)
+                self.images[k] = (f, name)
+            else:
+                v = np.asarray(v)
+                shape, dt = v.shape, v.dtype
+                self.images[k] = v
+            if dt != np.uint8 or len(shape) != 4 or shape[1] != 3 or shape[2] != shape[3]:
+                raise ValueError(f"split {k}: images must be uint8 [N x 3 x S x S] (got {dt} {tuple(shape)})")
+            if k in self.labels and self.labels[k].shape[0] != shape[0]:
+                raise ValueError(f"split {k}: {self.labels[k].shape[0]} captions but {shape[0]} images")
+
+    def close(self):
+        for f in self._files:
+            f.close()
+        self._files = []
+
+    def _image_rows(self, split, rows):
+        src = self.images[split]
+        if not isinstance(src, tuple):
+            return np.ascontiguousarray(src[rows])
+        f, name = src
+        cuts = [0] + [i for i in range(1, len(rows)) if rows[i] != rows[i - 1] + 1] + [len(rows)]
+        return np.concatenate([f.read_rows(name, int(rows[a]), int(rows[b - 1]) + 1) for a, b in zip(cuts[:-1], cuts[1:])])
+
+    def get_batch(self, split, batch_size):
+        """getBatch: (labels [batch_size x D], images [batch_size x 3 x S x S] uint8, bounds)"""
+        rows, bounds = self._global_rows(split, batch_size)
+        return self.labels[split][rows], self._image_rows(split, rows), bounds
+
+
+# the VGG-16 body of the *_vgg scripts: drop6 / drop7 of the Caffe model (p = 0.5), the 224 window of net_utils.prepro
+BODY_DROP_PROB = 0.5
+
+
+def crop_origin_train(seed, it, S, hw):
+    """The 0-based window origin (xoff, yoff) of training iteration `it`: net_utils.prepro's `torch.random(w - 224)` (1-based,
+    uniform on 1..w-224) moved to 0-based, so uniform on 0..S-hw-1 -- the last valid origin S-hw is never drawn, as there.
+    Drawn from a numpy generator seeded by (seed, it), behind the iteration's null-sentence / encoder-skip draw, so it depends
+    on nothing before it.  S == hw: (0, 0)."""
+    if S < hw:
+        raise ValueError(f"source size {S} below the network's input {hw}")
+    if S == hw:
+        return 0, 0
+    rng = np.random.default_rng([seed, it])
+    rng.random()  # the iteration's null-sentence / skip draw
+    xoff, yoff = rng.integers(0, S - hw, size=2)
+    return int(xoff), int(yoff)
+
+
+def crop_origin_eval(S, hw):
+    """eval_split's central window: prepro's `math.ceil((w - 224) / 2)` (1-based) moved to 0-based; S == hw: (0, 0)."""
+    if S < hw:
+        raise ValueError(f"source size {S} below the network's input {hw}")
+    o = max(0, -(-(S - hw) // 2) - 1)
+    return o, o
+
+
+def _is_raw_images(x):
+    return getattr(x, "dtype", None) == np.uint8 and getattr(x, "ndim", 0) == 4
+
+
+class _BodyInLoop:
+    """What the two weak-paired trainers share once the body runs inside the step (body = binding.Vgg16)."""
+
+    body = None
+    body_dropout_in_eval = False
+
+    def _need_body(self):
+        if self.body is None:
+            raise ValueError("raw images need the body in the loop: pass body=binding.Vgg16(...) to the trainer")
+        if self.body.feature_dim != self.dims.I:
+            raise ValueError(f"the body's feature width {self.body.feature_dim} is not dims.I = {self.dims.I}")
+        return self.body
+
+    def _body_train(self, images):
+        """(xoff, yoff, body dropout) of the current training iteration: a random window, drop6 / drop7 live"""
+        xoff, yoff = crop_origin_train(self.seed, self.iter, images.shape[-1], self._need_body().hw)
+        return xoff, yoff, binding.Dropout(1, BODY_DROP_PROB, self.seed, self.iter)
+
+    def _body_eval(self, images):
+        """(xoff, yoff, body dropout) of eval_split: the central window; the body in evaluate mode unless
+        body_dropout_in_eval (the arch2 script never calls cnn:evaluate(), so its validation forwards drop too)"""
+        xoff, yoff = crop_origin_eval(images.shape[-1], self._need_body().hw)
+        dr = binding.Dropout(1, BODY_DROP_PROB, self.seed, self.iter) if self.body_dropout_in_eval else None
+        return xoff, yoff, dr
+
+
 # 004_train_arch2_weakpaired_autoencoder_{vgg,inc}.lua: the AE learning rate and the CNN feature width differ (:36-48, :62)
 WEAKPAIRED_DEFAULTS = {"vgg": {"learning_rate": 1e-5, "I": 4096}, "inc": {"learning_rate": 3e-5, "I": 2048}}
 
 
-class WeakPairedAETrainer:
+class WeakPairedAETrainer(_BodyInLoop):
     """The weak-paired script's loop on an NVQA_ARCH_AE2_WP context: the null-sentence draw, ae_wp_step (lossFun), the log line
     with both update counts, the learning-rate decay, the -optim rule (default adam; AETrainer's six names, sgd undecayed as
     there) on [encoder | decoder] (the lookup table is frozen) and, once fine-tuning has started (finetune_cnn_after >= 0 and
@@ -371,12 +474,20 @@ class WeakPairedAETrainer:
     variant: 'vgg' or 'inc' (the default learning rate); learning_rate None: the variant's.
 
     The null-sentence draw replaces Lua's `math.random() <= rand_val` (:289-295), whose stream cannot be reproduced: a
-    numpy generator seeded by (seed, iter), so the draw of an iteration does not depend on anything before it."""
+    numpy generator seeded by (seed, iter), so the draw of an iteration does not depend on anything before it.
+
+    body (binding.Vgg16 with feature width I): the frozen VGG-16 body runs inside the step on raw images -- train_step_images,
+    and train / eval_split on a WeakPairedImageLoader.  Training cuts a random window per batch (crop_origin_train) and keeps
+    drop6 / drop7 live (p = 0.5, the trainer's seed, the iteration as step); eval_split cuts the central window and runs the
+    body in evaluate mode, the model as designed.  body_dropout_in_eval=True reproduces the script instead, which never calls
+    cnn:evaluate() and so validates with both dropouts live."""
 
     def __init__(self, dims, device=0, variant="vgg", learning_rate=None, learning_rate_decay_start=-1,
                  learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
                  grad_clip=0.1, drop_prob=0.5, rand_val=0.5, finetune_cnn_after=-1, cnn_optim_alpha=0.8, cnn_optim_beta=0.999,
-                 cnn_learning_rate=1e-5, cnn_weight_decay=0.0, seed=123, bf16=False, optim="adam", cnn_optim="adam"):
+                 cnn_learning_rate=1e-5, cnn_weight_decay=0.0, seed=123, bf16=False, optim="adam", cnn_optim="adam", body=None,
+                 body_dropout_in_eval=False):
+        self.body, self.body_dropout_in_eval = body, bool(body_dropout_in_eval)
         if optim not in binding.OPT_RULES:
             raise ValueError("optim: rmsprop | adagrad | sgd | sgdm | sgdmom | adam (misc/optim_updates.lua)")
         if cnn_optim not in binding.CNN_OPT_RULES:
@@ -440,12 +551,21 @@ class WeakPairedAETrainer:
                                       int((w == 0).sum() + (b == 0).sum()))
         return self._frozen_cnn_stats
 
-    def train_step(self, tokens, feats):
+    def train_step_images(self, tokens, images_u8):
+        """train_step with the body in the loop: images_u8 [B x 3 x S x S] uint8 instead of features"""
+        return self.train_step(tokens, None, images_u8=images_u8)
+
+    def train_step(self, tokens, feats, images_u8=None):
         """lossFun + log line + updates of one iteration; returns (loss, # updates, paramsNorm, # cnn updates, cnnParamsNorm,
         the log line)."""
         null = self.null_sentence()
         dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.seed, self.iter)
-        loss = self.ctx.ae_wp_step(feats, tokens, enc_tokens=None if null else tokens, dropout=dr)
+        if images_u8 is not None:
+            xoff, yoff, bdr = self._body_train(images_u8)
+            loss = self.ctx.ae_wp_step_images(self.body, images_u8, xoff, yoff, tokens, enc_tokens=None if null else tokens,
+                                              body_dropout=bdr, dropout=dr)
+        else:
+            loss = self.ctx.ae_wp_step(feats, tokens, enc_tokens=None if null else tokens, dropout=dr)
         lr, cnn_lr = self.current_lr()
         norm, count = _optim_update(self.ctx, self.optim, lr, self.learning_rate, self.alpha, self.beta, self.eps,
                                     self.weight_decay, self.grad_clip)
@@ -471,7 +591,7 @@ class WeakPairedAETrainer:
         losses = []
         for _ in range(iters):
             labels, feats, _ = loader.get_batch("train", self.dims.B)
-            out = self.train_step(labels, feats)
+            out = self.train_step_images(labels, feats) if _is_raw_images(feats) else self.train_step(labels, feats)
             losses.append(out[0])
             if log:
                 log(out[-1])
@@ -485,7 +605,12 @@ class WeakPairedAETrainer:
         end = self.dims.V + 1
         while True:
             labels, feats, bounds = loader.get_batch(split, self.dims.B)
-            loss, samples = self.ctx.ae_wp_evaluate(feats, labels, enc_tokens=labels, samples=True)
+            if _is_raw_images(feats):  # a WeakPairedImageLoader: the body runs in front of the evaluation
+                xoff, yoff, bdr = self._body_eval(feats)
+                loss, samples = self.ctx.ae_wp_evaluate_images(self.body, feats, xoff, yoff, labels, enc_tokens=labels,
+                                                               body_dropout=bdr, samples=True)
+            else:
+                loss, samples = self.ctx.ae_wp_evaluate(feats, labels, enc_tokens=labels, samples=True)
             losses.append(loss)
             for p, a in zip(decode_sequence(loader.ix_to_word, samples, end), decode_sequence(loader.ix_to_word, labels, end)):
                 used += 1
@@ -511,7 +636,7 @@ class WeakPairedAETrainer:
 WEAKPAIRED1_DEFAULTS = {"vgg": {"batch_size": 16, "I": 4096}, "inc": {"batch_size": 10, "I": 2048}}
 
 
-class WeakPairedAE1Trainer:
+class WeakPairedAE1Trainer(_BodyInLoop):
     """The arch1 weak-paired script's loop on an NVQA_ARCH_AE1_WP context: the encoder-skip draw (:296-304), ae1_wp_step
     (lossFun), the log line, the learning-rate decay and the -optim rule (default adam; AETrainer's six names, sgd undecayed as
     there) over [encoder | decoder | multimodal] (clamp, then weight decay, :335-341).  The lookup table is frozen and lives outside the flat vector.
@@ -521,11 +646,17 @@ class WeakPairedAE1Trainer:
     (seed, iter), as WeakPairedAETrainer draws its null sentence.  The bridge (netdef.AxB's two Linear) starts from Torch's
     nn.Linear default, uniform(-1/sqrt(fan_in), 1/sqrt(fan_in)), drawn here from the seed: the script clones a multimodal_net
     out of the text checkpoint (:150), a module the text model does not have.  The CNN body is frozen and runs outside the
-    library, so the log line ends with paramsNorm (the script's two cnn figures describe that body)."""
+    library, so the log line ends with paramsNorm (the script's two cnn figures describe that body).
+
+    body (binding.Vgg16 with feature width I): the frozen body runs inside the step on raw images, as in WeakPairedAETrainer
+    (train_step_images; train / eval_split on a WeakPairedImageLoader).  This script switches the body with cnn:training() /
+    cnn:evaluate(), so eval_split's default -- no body dropout -- is also what the script does."""
 
     def __init__(self, dims, device=0, variant="vgg", learning_rate=3e-5, learning_rate_decay_start=-1,
                  learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
-                 grad_clip=0.1, drop_prob=0.5, skip_prob=0.5, seed=123, bf16=False, optim="adam"):
+                 grad_clip=0.1, drop_prob=0.5, skip_prob=0.5, seed=123, bf16=False, optim="adam", body=None,
+                 body_dropout_in_eval=False):
+        self.body, self.body_dropout_in_eval = body, bool(body_dropout_in_eval)
         if optim not in binding.OPT_RULES:
             raise ValueError("optim: rmsprop | adagrad | sgd | sgdm | sgdmom | adam (misc/optim_updates.lua)")
         self.optim = optim
@@ -625,16 +756,22 @@ class WeakPairedAE1Trainer:
             lr *= 0.5 ** ((self.iter - self.decay_start) / self.decay_every)
         return lr
 
-    def train_step(self, tokens, feats):
+    def train_step_images(self, tokens, images_u8):
+        """train_step with the body in the loop: images_u8 [B x 3 x S x S] uint8 instead of features"""
+        return self.train_step(tokens, None, images_u8=images_u8)
+
+    def train_step(self, tokens, feats, images_u8=None):
         """lossFun + log line + update of one iteration; returns (loss, # updates, paramsNorm, skipped, the log line)."""
         skip = self.skip_encoder()
         if skip and self.mean_vector is None:
             raise ValueError("the encoder is skipped in this iteration: set_mean_vector / mean_sentence_vector first")
         dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.seed, self.iter)
-        if skip:
-            loss = self.ctx.ae1_wp_step(feats, tokens, enc_state=np.tile(self.mean_vector, (self.dims.B, 1)), dropout=dr)
+        enc = {"enc_state": np.tile(self.mean_vector, (self.dims.B, 1))} if skip else {"enc_tokens": tokens}
+        if images_u8 is not None:
+            xoff, yoff, bdr = self._body_train(images_u8)
+            loss = self.ctx.ae1_wp_step_images(self.body, images_u8, xoff, yoff, tokens, body_dropout=bdr, dropout=dr, **enc)
         else:
-            loss = self.ctx.ae1_wp_step(feats, tokens, enc_tokens=tokens, dropout=dr)
+            loss = self.ctx.ae1_wp_step(feats, tokens, dropout=dr, **enc)
         norm, count = _optim_update(self.ctx, self.optim, self.current_lr(), self.learning_rate, self.alpha, self.beta, self.eps,
                                     self.weight_decay, self.grad_clip)
         line = "iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f" % (self.iter, loss, count, norm)
@@ -645,7 +782,7 @@ class WeakPairedAE1Trainer:
         losses = []
         for _ in range(iters):
             labels, feats, _ = loader.get_batch("train", self.dims.B)
-            out = self.train_step(labels, feats)
+            out = self.train_step_images(labels, feats) if _is_raw_images(feats) else self.train_step(labels, feats)
             losses.append(out[0])
             if log:
                 log(out[-1])
@@ -659,7 +796,12 @@ class WeakPairedAE1Trainer:
         end = self.dims.V + 1
         while True:
             labels, feats, bounds = loader.get_batch(split, self.dims.B)
-            loss, samples = self.ctx.ae1_wp_evaluate(feats, labels, enc_tokens=labels, samples=True)
+            if _is_raw_images(feats):  # a WeakPairedImageLoader: the body runs in front of the evaluation
+                xoff, yoff, bdr = self._body_eval(feats)
+                loss, samples = self.ctx.ae1_wp_evaluate_images(self.body, feats, xoff, yoff, labels, enc_tokens=labels,
+                                                                body_dropout=bdr, samples=True)
+            else:
+                loss, samples = self.ctx.ae1_wp_evaluate(feats, labels, enc_tokens=labels, samples=True)
             losses.append(loss)
             for p, a in zip(decode_sequence(loader.ix_to_word, samples, end), decode_sequence(loader.ix_to_word, labels, end)):
                 used += 1

@@ -55,6 +55,7 @@ SAMPLE_ARGMAX, SAMPLE_MULTINOMIAL, SAMPLE_BEAM = 0, 1, 2
 # every symbol include/nvqa.h declares: name -> (restype, argtypes)
 _vp, _i32p, _f32p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
 _i64p = ctypes.POINTER(ctypes.c_int64)
+_u8p = ctypes.POINTER(ctypes.c_uint8)
 SYMBOLS = {
     "nvqa_create": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.POINTER(_vp)]),
     "nvqa_destroy": (ctypes.c_int, [_vp]),
@@ -93,6 +94,7 @@ SYMBOLS = {
     "nvqa_vgg16_fc7": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, _f32p]),
     "nvqa_vgg16_set_precision": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_vgg16_preprocess": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p]),
+    "nvqa_vgg16_fc7_raw": (ctypes.c_int, [_vp, _u8p] + [ctypes.c_int] * 4 + [ctypes.POINTER(Dropout), _f32p]),
     "nvqa_step_images": (ctypes.c_int, [_vp, _vp, _f32p, _i32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_step": (ctypes.c_int, [_vp, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _i32p]),
@@ -120,6 +122,14 @@ SYMBOLS = {
     "nvqa_ae1_wp_encode": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p]),
     "nvqa_ae1_wp_set_lookup": (ctypes.c_int, [_vp, _f32p]),
     "nvqa_ae1_wp_get_lookup": (ctypes.c_int, [_vp, _f32p]),
+    "nvqa_ae_wp_step_images": (ctypes.c_int, [_vp, _vp, _u8p] + [ctypes.c_int] * 3 + [ctypes.POINTER(Dropout), _i32p, _i32p,
+                                              ctypes.POINTER(Dropout), _f32p]),
+    "nvqa_ae_wp_evaluate_images": (ctypes.c_int, [_vp, _vp, ctypes.c_int32, _u8p] + [ctypes.c_int] * 3
+                                   + [ctypes.POINTER(Dropout), _i32p, _i32p, _f32p, _i32p]),
+    "nvqa_ae1_wp_step_images": (ctypes.c_int, [_vp, _vp, _u8p] + [ctypes.c_int] * 3 + [ctypes.POINTER(Dropout), _i32p, _f32p, _i32p,
+                                               ctypes.POINTER(Dropout), _f32p, _f32p]),
+    "nvqa_ae1_wp_evaluate_images": (ctypes.c_int, [_vp, _vp, ctypes.c_int32, _u8p] + [ctypes.c_int] * 3
+                                    + [ctypes.POINTER(Dropout), _i32p, _i32p, _f32p, _i32p]),
     "nvqa_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_profile_reset": (ctypes.c_int, [_vp]),
     "nvqa_profile_count": (ctypes.c_int, [_vp]),
@@ -158,6 +168,20 @@ def _f32(a):
 
 def _i32(a):
     return None if a is None else a.ctypes.data_as(_i32p)
+
+
+def _u8(a):
+    return None if a is None else a.ctypes.data_as(_u8p)
+
+
+def _images_u8(images, n=None):
+    """uint8 planar RGB [n x 3 x S x S] as /images/<split> stores it -> (contiguous array, S); no silent conversion"""
+    x = np.asarray(images)
+    if x.dtype != np.uint8:
+        raise ValueError(f"raw images must be uint8 (got {x.dtype}): the float route is Vgg16.fc7")
+    if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or (n is not None and x.shape[0] != n):
+        raise ValueError(f"raw images must be [{'n' if n is None else n} x 3 x S x S] (got {x.shape})")
+    return np.ascontiguousarray(x), int(x.shape[2])
 
 
 class Context:
@@ -515,6 +539,68 @@ class Context:
         self._check(self.lib.nvqa_ae1_wp_get_lookup(self._h, _f32(w)))
         return w
 
+    # ---- the weak-paired steps with the VGG-16 body in the loop -----------------------
+    def ae_wp_step_images(self, vgg, images_u8, xoff, yoff, tokens, enc_tokens=None, body_dropout=None, dropout=None,
+                          want_loss=True):
+        """nvqa_ae_wp_step_images: ae_wp_step fed by the extractor `vgg` (Vgg16) on images_u8 [B x 3 x S x S] uint8, window
+        origin (xoff, yoff), body_dropout (Dropout or None: drop6 / drop7 off).  The features stay on the device; with
+        want_loss=False the call only enqueues."""
+        d = self.dims
+        x, S = _images_u8(images_u8, d.B)
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(d.B, d.T)
+        et = None if enc_tokens is None else np.ascontiguousarray(enc_tokens, np.int32).reshape(d.B, d.T)
+        loss = ctypes.c_float(0)
+        bdr = ctypes.byref(body_dropout) if body_dropout is not None else None
+        dr = ctypes.byref(dropout) if dropout is not None else None
+        self._check(self.lib.nvqa_ae_wp_step_images(self._h, vgg._h, _u8(x), S, int(xoff), int(yoff), bdr, _i32(et), _i32(tok), dr,
+                                                    ctypes.byref(loss) if want_loss else None))
+        return float(loss.value) if want_loss else None
+
+    def ae_wp_evaluate_images(self, vgg, images_u8, xoff, yoff, tokens, enc_tokens=None, body_dropout=None, samples=False):
+        """nvqa_ae_wp_evaluate_images of n = len(tokens) rows: (evaluate-mode loss, greedy samples [n x D] or None)."""
+        d = self.dims
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(-1, d.T)
+        n = tok.shape[0]
+        x, S = _images_u8(images_u8, n)
+        et = None if enc_tokens is None else np.ascontiguousarray(enc_tokens, np.int32).reshape(n, d.T)
+        out = np.empty((n, d.T), np.int32) if samples else None
+        loss = ctypes.c_float(0)
+        bdr = ctypes.byref(body_dropout) if body_dropout is not None else None
+        self._check(self.lib.nvqa_ae_wp_evaluate_images(self._h, vgg._h, n, _u8(x), S, int(xoff), int(yoff), bdr, _i32(et), _i32(tok),
+                                                        ctypes.byref(loss), _i32(out)))
+        return float(loss.value), out
+
+    def ae1_wp_step_images(self, vgg, images_u8, xoff, yoff, tokens, enc_tokens=None, enc_state=None, body_dropout=None,
+                           dropout=None, want_loss=True, want_dfeats=False):
+        """nvqa_ae1_wp_step_images: ae1_wp_step fed by the extractor; returns as ae1_wp_step does (dfeats = d(loss)/d(f^))."""
+        d = self.dims
+        x, S = _images_u8(images_u8, d.B)
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(d.B, d.T)
+        et = None if enc_tokens is None else np.ascontiguousarray(enc_tokens, np.int32).reshape(d.B, d.T)
+        es = None if enc_state is None else np.ascontiguousarray(enc_state, np.float32).reshape(d.B, 2 * d.R)
+        df = np.empty((d.B, d.I), np.float32) if want_dfeats else None
+        loss = ctypes.c_float(0)
+        bdr = ctypes.byref(body_dropout) if body_dropout is not None else None
+        dr = ctypes.byref(dropout) if dropout is not None else None
+        self._check(self.lib.nvqa_ae1_wp_step_images(self._h, vgg._h, _u8(x), S, int(xoff), int(yoff), bdr, _i32(et), _f32(es),
+                                                     _i32(tok), dr, ctypes.byref(loss) if want_loss else None, _f32(df)))
+        out = float(loss.value) if want_loss else None
+        return (out, df) if want_dfeats else out
+
+    def ae1_wp_evaluate_images(self, vgg, images_u8, xoff, yoff, tokens, enc_tokens, body_dropout=None, samples=False):
+        """nvqa_ae1_wp_evaluate_images of n = len(tokens) rows: (evaluate-mode loss, greedy samples [n x D] or None)."""
+        d = self.dims
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(-1, d.T)
+        n = tok.shape[0]
+        x, S = _images_u8(images_u8, n)
+        et = np.ascontiguousarray(enc_tokens, np.int32).reshape(n, d.T)
+        out = np.empty((n, d.T), np.int32) if samples else None
+        loss = ctypes.c_float(0)
+        bdr = ctypes.byref(body_dropout) if body_dropout is not None else None
+        self._check(self.lib.nvqa_ae1_wp_evaluate_images(self._h, vgg._h, n, _u8(x), S, int(xoff), int(yoff), bdr, _i32(et), _i32(tok),
+                                                         ctypes.byref(loss), _i32(out)))
+        return float(loss.value), out
+
     def set_fusion(self, mode):
         """0 netdef.AxB, 1 netdef.AskipB, 2 netdef.A_B (W_o becomes [A x 2C]: right after creation only)."""
         self._check(self.lib.nvqa_set_fusion(self._h, int(mode)))
@@ -630,6 +716,16 @@ class Vgg16:
         assert x.shape[1:] == (3, self.hw, self.hw)
         out = np.empty((n, self.feature_dim), np.float32)
         self._check(self.lib.nvqa_vgg16_fc7(self._h, _f32(x), n, _f32(out)))
+        return out
+
+    def fc7_raw(self, images_u8, xoff, yoff, dropout=None):
+        """nvqa_vgg16_fc7_raw: images_u8 [n x 3 x S x S] uint8 planar RGB; the hw x hw window at (xoff, yoff), mean-subtracted,
+        through the network.  dropout (Dropout, mode 1): drop6 / drop7 live.  Returns module 38's output [n x F]."""
+        x, S = _images_u8(images_u8)
+        n = x.shape[0]
+        out = np.empty((n, self.feature_dim), np.float32)
+        dr = ctypes.byref(dropout) if dropout is not None else None
+        self._check(self.lib.nvqa_vgg16_fc7_raw(self._h, _u8(x), n, S, int(xoff), int(yoff), dr, _f32(out)))
         return out
 
     def preprocess(self, rgb):

@@ -41,13 +41,14 @@ class _Dataset:
 
 
 class File:
-    """Read-only view: `File(path).read('/ques_train')` -> numpy array; `keys()`; `shape(name)`."""
+    """Read-only view: `File(path).read('/ques_train')` -> numpy array; `read_rows(name, lo, hi)`; `keys()`; `shape(name)`."""
 
     def __init__(self, path):
         self.path = path
         self.f = open(path, "rb")
         self._find_superblock()
         self._root_links = None
+        self._chunk_index = None  # read_rows: {dataset name: its chunk list}
 
     def close(self):
         if self.f:
@@ -321,6 +322,24 @@ class File:
             else:
                 out.append((offs, csize, mask, child))
 
+    def _chunk(self, ds, cshape, csize, mask, caddr):
+        """one stored chunk, its filter pipeline undone back to front, as an array of the chunk's shape"""
+        raw = self._at(caddr, csize)
+        for idx in range(len(ds.filters) - 1, -1, -1):
+            if mask & (1 << idx):
+                continue
+            fid, cd = ds.filters[idx]
+            if fid == 1:
+                raw = zlib.decompress(raw)
+            elif fid == 2:
+                es = cd[0] if cd else ds.dtype.itemsize
+                raw = np.frombuffer(raw, np.uint8).reshape(es, -1).T.tobytes()
+            elif fid == 3:
+                raw = raw[:-4]
+            else:
+                raise H5Error(f"unsupported filter {fid}")
+        return np.frombuffer(raw, ds.dtype, count=int(np.prod(cshape))).reshape(cshape)
+
     def shape(self, name):
         return self._dataset(name).shape
 
@@ -354,25 +373,59 @@ class File:
             if bt != (UNDEF >> (64 - 8 * self.O)):
                 self._chunks(bt, nd, chunks)
             for offs, csize, mask, caddr in chunks:
-                raw = self._at(caddr, csize)
-                for idx in range(len(ds.filters) - 1, -1, -1):  # undo the pipeline back to front
-                    if mask & (1 << idx):
-                        continue
-                    fid, cd = ds.filters[idx]
-                    if fid == 1:
-                        raw = zlib.decompress(raw)
-                    elif fid == 2:
-                        es = cd[0] if cd else ds.dtype.itemsize
-                        raw = np.frombuffer(raw, np.uint8).reshape(es, -1).T.tobytes()
-                    elif fid == 3:
-                        raw = raw[:-4]
-                    else:
-                        raise H5Error(f"unsupported filter {fid}")
-                c = np.frombuffer(raw, ds.dtype, count=int(np.prod(cshape))).reshape(cshape)
+                c = self._chunk(ds, cshape, csize, mask, caddr)
                 sl = tuple(slice(o, min(o + s, e)) for o, s, e in zip(offs, cshape, ds.shape))
                 arr[sl] = c[tuple(slice(0, s.stop - s.start) for s in sl)]
             return arr.astype(ds.dtype.newbyteorder("="), copy=False)
         return arr.reshape(ds.shape).astype(ds.dtype.newbyteorder("="), copy=False)
+
+    def read_rows(self, name, lo, hi):
+        """rows [lo, hi) of an N-D dataset along its first axis, `read(name)[lo:hi]` without reading the rest: a contiguous
+        dataset costs one seek and one read, a chunked one only the chunks that hold one of the rows (the chunk index is
+        walked once per dataset and kept).  For datasets too large to hold, such as /images/<split>."""
+        ds = self._dataset(name)
+        if not ds.shape:
+            raise H5Error(f"{self.path}: '{name}' is a scalar: it has no rows")
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= ds.shape[0]:
+            raise IndexError(f"{self.path}: rows [{lo}, {hi}) outside '{name}' with {ds.shape[0]} rows")
+        oshape = (hi - lo,) + tuple(ds.shape[1:])
+        per = int(np.prod(ds.shape[1:], dtype=np.int64))
+        n = (hi - lo) * per
+        native = ds.dtype.newbyteorder("=")
+        kind = ds.layout[0]
+        if kind == "compact":
+            arr = np.frombuffer(ds.layout[1], dtype=ds.dtype, count=ds.shape[0] * per)[lo * per:hi * per]
+            return arr.reshape(oshape).astype(native)
+        if kind == "contiguous":
+            addr = ds.layout[1]
+            if addr == (UNDEF >> (64 - 8 * self.O)):
+                return np.zeros(oshape, native)
+            self.f.seek(self.base + addr + lo * per * ds.dtype.itemsize)
+            arr = np.fromfile(self.f, dtype=ds.dtype, count=n)
+            if arr.size != n:
+                raise H5Error(f"{self.path}: '{name}' is truncated")
+            return arr.reshape(oshape).astype(native, copy=False)
+        _, bt, dims = ds.layout
+        cshape = tuple(dims[:-1])
+        if len(cshape) != len(ds.shape):
+            raise H5Error("chunk rank does not match the dataspace")
+        if self._chunk_index is None:
+            self._chunk_index = {}
+        if name not in self._chunk_index:
+            chunks = []
+            if bt != (UNDEF >> (64 - 8 * self.O)):
+                self._chunks(bt, len(dims), chunks)
+            self._chunk_index[name] = chunks
+        arr = np.zeros(oshape, ds.dtype)
+        for offs, csize, mask, caddr in self._chunk_index[name]:
+            r0, r1 = max(offs[0], lo), min(offs[0] + cshape[0], hi, ds.shape[0])
+            if r0 >= r1:
+                continue
+            c = self._chunk(ds, cshape, csize, mask, caddr)
+            rest = tuple(slice(o, min(o + s, e)) for o, s, e in zip(offs[1:], cshape[1:], ds.shape[1:]))
+            arr[(slice(r0 - lo, r1 - lo),) + rest] = c[(slice(r0 - offs[0], r1 - offs[0]),) + tuple(slice(0, t.stop - t.start) for t in rest)]
+        return arr.astype(native, copy=False)
 
 
 def _parse_dtype(b):

@@ -56,6 +56,8 @@ int nvqa_vgg16_set_weights(nvqa_vgg *vgg, const float *flat);
 int nvqa_vgg16_fc7(nvqa_vgg *vgg, const float *images, int n, float *feats_out);
 int nvqa_vgg16_set_precision(nvqa_vgg *vgg, int bf16);
 int nvqa_vgg16_preprocess(nvqa_vgg *vgg, const float *rgb, int n, int H, int W, float *out);
+int nvqa_vgg16_fc7_raw(nvqa_vgg *vgg, const uint8_t *images, int n, int S, int xoff, int yoff,
+                       const nvqa_dropout *body_dropout, float *feats_out);
 int nvqa_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const float *images, const int32_t *tokens,
                      const int32_t *lengths, const int32_t *labels, const nvqa_dropout *dropout, float *loss_out);
 int nvqa_ae_step(nvqa_ctx *ctx, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out);
@@ -96,6 +98,18 @@ int nvqa_ae1_wp_evaluate(nvqa_ctx *ctx, int32_t n, const float *feats, const int
 int nvqa_ae1_wp_encode(nvqa_ctx *ctx, int32_t n, const int32_t *enc_tokens, float *state_out);
 int nvqa_ae1_wp_set_lookup(nvqa_ctx *ctx, const float *w);
 int nvqa_ae1_wp_get_lookup(nvqa_ctx *ctx, float *w_out);
+int nvqa_ae_wp_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                           const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                           const nvqa_dropout *dropout, float *loss_out);
+int nvqa_ae_wp_evaluate_images(nvqa_ctx *ctx, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
+                               const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                               float *loss_out, int32_t *samples_out);
+int nvqa_ae1_wp_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                            const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const float *enc_state,
+                            const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out);
+int nvqa_ae1_wp_evaluate_images(nvqa_ctx *ctx, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                                float *loss_out, int32_t *samples_out);
 int nvqa_profile_enable(nvqa_ctx *ctx, int enable);
 int nvqa_profile_reset(nvqa_ctx *ctx);
 int nvqa_profile_count(const nvqa_ctx *ctx);
@@ -127,6 +141,7 @@ end
 function M.iptr(t) return ffi.cast('const int32_t*', t:data()) end
 function M.fptr(t) return ffi.cast('float*', t:data()) end
 function M.lptr(t) return ffi.cast('const int64_t*', t:data()) end
+function M.bptr(t) return ffi.cast('const uint8_t*', t:data()) end   -- ByteTensor: the raw images of /images/<split>
 
 function M.dropout(mode, p, seed, step)
   local d = ffi.new('nvqa_dropout'); d.mode = mode; d.p = p; d.seed = seed; d.step = step
@@ -160,6 +175,36 @@ function M.ae_sample_rows(ctx, rows, D, opt)
   local seq, lp = torch.IntTensor(n, D), torch.FloatTensor(n, D)
   check(M.lib.nvqa_ae_sample_rows(ctx, n, M.lptr(rows), M.sample_opts(opt), ffi.cast('int32_t*', seq:data()), M.fptr(lp)))
   return seq, lp
+end
+
+-- -body_in_loop 1 of train_arch{1,2}_wp_ae.lua: the VGG-16 body (full width, 224 x 224 input) on opt.gpuid with the weights of
+-- opt.cnn_weights, a flat float32 file in nvqa_vgg16_set_weights order (the caffemodel's blobs, layer by layer)
+function M.body_open(opt)
+  local out = ffi.new('nvqa_vgg*[1]')
+  check(M.lib.nvqa_vgg16_create(opt.gpuid or 0, 1, 224, opt.batch_size, out))
+  local vgg = ffi.gc(out[0], M.lib.nvqa_vgg16_destroy)
+  local w = torch.FloatTensor(torch.FloatStorage(opt.cnn_weights))
+  assert(w:nElement() == tonumber(M.lib.nvqa_vgg16_weight_count(vgg)), '-cnn_weights does not hold the VGG-16 weight vector')
+  assert(M.lib.nvqa_vgg16_feature_dim(vgg) == opt.nhimage, 'the body\'s feature width does not match -nhimage')
+  check(M.lib.nvqa_vgg16_set_weights(vgg, M.fptr(w)))
+  return vgg
+end
+
+-- net_utils.prepro's window origin, 0-based: training torch.random(S - 224) per axis (x first, as there), evaluation the centre
+function M.crop_origin(S, train)
+  if S <= 224 then return 0, 0 end
+  if train then
+    local xoff = torch.random(S - 224) - 1
+    return xoff, torch.random(S - 224) - 1
+  end
+  local c = math.max(0, math.ceil((S - 224) / 2) - 1)
+  return c, c
+end
+
+-- the body's dropout (drop6 / drop7, p = 0.5) of iteration `step`; on = false: the body in evaluate mode
+function M.body_dropout(on, seed, step)
+  if not on then return nil end
+  return M.dropout(1, 0.5, seed, step)
 end
 
 -- -optim / -cnn_optim of the scripts of 001_train_autoencoder -> NVQA_OPT_* (misc/optim_updates.lua)

@@ -7,6 +7,11 @@ Same command-line options (:27-74, minus -backend / -language_eval / -cnn_proto 
   * The CNN body is frozen (-finetune_cnn_after only starts the update of its final Linear, the projection) and runs outside:
     -input_feats_h5 holds its output per caption, /feats/train and /feats/val [N x I] (vgg: post-ReLU fc7 as nvqa_vgg16_fc7
     returns it), row i belonging to /labels/<split> row i.  DataLoaderWeakPaired's lockstep walk and wrap rule are kept.
+    With -body_in_loop 1 the body runs inside the step instead, as in the reference: uint8 images from /images/<split> of
+    -input_h5 (only a batch's rows are read), a random 224 window per training batch, the central one in eval_split, the RGB
+    mean, VGG-16 up to module 38 with the weights of -cnn_weights, all on the device (nvqa_ae_wp_step_images; DESIGN.md
+    section 9.10).  drop6 / drop7 are live in training; -body_dropout_in_eval 1 keeps them live in eval_split too, which is
+    what the reference script does (it never calls cnn:evaluate()); the default evaluates the model as designed.
   * AutoEncoderNull, L2Normalize + Linear and LanguageModelCriterion are one library context of arch NVQA_ARCH_AE2_WP;
     protos.ae's parameters come from -start_from_text, the flat-vector table AETrainer.export_params writes for a text
     auto-encoder of arch NVQA_ARCH_AE2 (the reference loads the whole protos.ae, :127-129).
@@ -28,6 +33,9 @@ cmd:option('-input_h5','data/data.h5','path to the h5file containing the preproc
 cmd:option('-input_feats_h5','data/feats.h5','path to the h5file with the frozen CNN body\'s features (/feats/<split>)')
 cmd:option('-input_json','data/data.json','path to the json file containing additional info and vocab')
 cmd:option('-start_from_text', '', 'flat-vector table of the arch2 text auto-encoder (AETrainer.export_params)')
+cmd:option('-body_in_loop', 0, '1: run the VGG-16 body inside the step on the raw images /images/<split> of -input_h5 (needs -cnn_weights)')
+cmd:option('-cnn_weights', '', 'flat float32 file of the VGG-16 weights in nvqa_vgg16_set_weights order (-body_in_loop 1)')
+cmd:option('-body_dropout_in_eval', 0, '1: drop6 / drop7 stay live in eval_split, as in the reference script (-body_in_loop 1)')
 cmd:option('-rnn_size',512,'size of the rnn in number of hidden nodes in each layer')
 cmd:option('-input_encoding_size',512,'the encoding size of each token in the vocabulary, and the image.')
 cmd:option('-nhimage', 4096, 'feature width of the CNN body (vgg fc7 4096, inception 2048)')
@@ -67,37 +75,51 @@ for _ in pairs(info.ix_to_word) do vocab_size = vocab_size + 1 end
 local h5 = hdf5.open(opt.input_h5, 'r')
 local labels = {train = h5:read('/labels/train'):all():int(), val = h5:read('/labels/val'):all():int()}
 h5:close()
-h5 = hdf5.open(opt.input_feats_h5, 'r')
-local feats = {train = h5:read('/feats/train'):all():float(), val = h5:read('/feats/val'):all():float()}
-h5:close()
-assert(feats.train:size(2) == opt.nhimage, 'feature width does not match -nhimage')
+local feats, images, body, img_size = nil, nil, nil, 0
+if opt.body_in_loop == 1 then                        -- the reference's stage: raw images, the VGG-16 body inside the step
+  assert(string.len(opt.cnn_weights) > 0, '-body_in_loop 1 needs -cnn_weights')
+  local h5i = hdf5.open(opt.input_h5, 'r')           -- stays open: a batch reads its own rows
+  images = {train = h5i:read('/images/train'), val = h5i:read('/images/val')}
+  img_size = images.train:dataspaceSize()[3]
+  body = nvqa.body_open(opt)
+else
+  h5 = hdf5.open(opt.input_feats_h5, 'r')
+  feats = {train = h5:read('/feats/train'):all():float(), val = h5:read('/feats/val'):all():float()}
+  h5:close()
+  assert(feats.train:size(2) == opt.nhimage, 'feature width does not match -nhimage')
+end
 local seq_length = labels.train:size(2)
 local iterators = {train = 1, val = 1}
 
 local function getBatch(split, batch_size)          -- DataLoaderWeakPaired:getBatch (:58-103): captions and images in lockstep
-  local data, fv, max_index, it = labels[split], feats[split], labels[split]:size(1), iterators[split]
-  local batch = torch.IntTensor(batch_size, seq_length)
-  local fb = torch.FloatTensor(batch_size, opt.nhimage)
-  local wrapped = false
+  local data, max_index, it = labels[split], labels[split]:size(1), iterators[split]
+  local ranges, wrapped = nil, false                  -- the rows of the batch, 1-based inclusive, in batch order
   if it + batch_size - 1 > max_index then
     wrapped = true
     if it < max_index then
-      local num_left = max_index - it + 1
-      batch[{{1, num_left}, {}}] = data[{{it, max_index}, {}}]
-      batch[{{num_left + 1, batch_size}, {}}] = data[{{1, batch_size - num_left}, {}}]
-      fb[{{1, num_left}, {}}] = fv[{{it, max_index}, {}}]
-      fb[{{num_left + 1, batch_size}, {}}] = fv[{{1, batch_size - num_left}, {}}]
+      ranges = {{it, max_index}, {1, batch_size - (max_index - it + 1)}}
     else
-      batch:copy(data[{{1, batch_size}, {}}])
-      fb:copy(fv[{{1, batch_size}, {}}])
+      ranges = {{1, batch_size}}
     end
     iterators[split] = 1
   else
-    batch:copy(data[{{it, it + batch_size - 1}, {}}])
-    fb:copy(fv[{{it, it + batch_size - 1}, {}}])
+    ranges = {{it, it + batch_size - 1}}
     iterators[split] = it + batch_size
   end
-  return batch:contiguous(), fb:contiguous(), wrapped
+  local batch = torch.IntTensor(batch_size, seq_length)
+  local fb = body and torch.ByteTensor(batch_size, 3, img_size, img_size) or torch.FloatTensor(batch_size, opt.nhimage)
+  local at = 1
+  for _, r in ipairs(ranges) do
+    local n = r[2] - r[1] + 1
+    batch:narrow(1, at, n):copy(data:narrow(1, r[1], n))
+    if body then                                      -- only the batch's rows of /images/<split> are ever read
+      fb:narrow(1, at, n):copy(images[split]:partial({r[1], r[2]}, {1, 3}, {1, img_size}, {1, img_size}))
+    else
+      fb:narrow(1, at, n):copy(feats[split]:narrow(1, r[1], n))
+    end
+    at = at + n
+  end
+  return batch, fb, wrapped
 end
 
 -- the context: [encoder | decoder | lookup] from the text model; W_p uniform(-0.08, 0.08), b_p = 0 (build_cnn) -----------
@@ -119,7 +141,14 @@ local function eval_split(split)                    -- eval_split (:199-260): fo
   local loss = ffi.new('float[1]')
   while true do
     local batch, fb, wrapped = getBatch(split, opt.batch_size)
-    nvqa.check(nvqa.lib.nvqa_ae_wp_evaluate(ctx, opt.batch_size, nvqa.fptr(fb), nvqa.iptr(batch), nvqa.iptr(batch), loss, nil))
+    if body then
+      local xoff, yoff = nvqa.crop_origin(img_size, false)
+      nvqa.check(nvqa.lib.nvqa_ae_wp_evaluate_images(ctx, body, opt.batch_size, nvqa.bptr(fb), img_size, xoff, yoff,
+                                                     nvqa.body_dropout(opt.body_dropout_in_eval == 1, opt.seed, 0),
+                                                     nvqa.iptr(batch), nvqa.iptr(batch), loss, nil))
+    else
+      nvqa.check(nvqa.lib.nvqa_ae_wp_evaluate(ctx, opt.batch_size, nvqa.fptr(fb), nvqa.iptr(batch), nvqa.iptr(batch), loss, nil))
+    end
     loss_sum = loss_sum + loss[0]; evals = evals + 1
     n = n + opt.batch_size
     if wrapped then break end
@@ -148,8 +177,15 @@ while true do
   local batch, fb = getBatch('train', opt.batch_size)
   local enc = batch
   if torch.uniform() <= opt.rand_val then enc = nil end                          -- the null sentence (:289-295)
-  nvqa.check(nvqa.lib.nvqa_ae_wp_step(ctx, nvqa.fptr(fb), enc and nvqa.iptr(enc) or nil, nvqa.iptr(batch),
-                                      nvqa.dropout(1, opt.drop_prob_ae, opt.seed, iter), loss))
+  if body then                                                                   -- prepro(data.images, true, ...) + cnn:forward
+    local xoff, yoff = nvqa.crop_origin(img_size, true)
+    nvqa.check(nvqa.lib.nvqa_ae_wp_step_images(ctx, body, nvqa.bptr(fb), img_size, xoff, yoff,
+                                               nvqa.body_dropout(true, opt.seed, iter), enc and nvqa.iptr(enc) or nil,
+                                               nvqa.iptr(batch), nvqa.dropout(1, opt.drop_prob_ae, opt.seed, iter), loss))
+  else
+    nvqa.check(nvqa.lib.nvqa_ae_wp_step(ctx, nvqa.fptr(fb), enc and nvqa.iptr(enc) or nil, nvqa.iptr(batch),
+                                        nvqa.dropout(1, opt.drop_prob_ae, opt.seed, iter), loss))
+  end
   local learning_rate, cnn_learning_rate = opt.learning_rate, opt.cnn_learning_rate
   if iter > opt.learning_rate_decay_start and opt.learning_rate_decay_start >= 0 then
     local decay_factor = math.pow(0.5, (iter - opt.learning_rate_decay_start) / opt.learning_rate_decay_every)

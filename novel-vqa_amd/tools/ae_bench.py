@@ -27,8 +27,15 @@ sgdm | sgdmom | adam) with the scripts' alpha 0.8 / beta 0.999; the line then ca
 nvqa_adam_update as ever.
 --resident (--arch 1 | 2, no --world): the same batches as one corpus in HBM (nvqa_ae_corpus_load), every step named by its row
 ids (nvqa_ae_step_rows); the line then carries "resident": 1.  Without the flag the tool runs as ever.
+--images (--arch 5 | 6): the weak-paired step with the VGG-16 body in the loop at the reference's shape -- B = 20 (arch 5) / 16
+(arch 6) unless --B is given, uint8 images of --S 256, the full-width body on 224 windows with drop6 / drop7 live and synthetic
+He-scaled weights -- in two arms that alternate block by block in this one job: "in_loop" = nvqa_ae*_wp_step_images (the
+features stay on the device), "composed" = nvqa_vgg16_fc7_raw to the host and the host-fed step on what came back.  Both arms
+compute the same bits per step and end every step with nvqa_adam_update; a block is timed around a final synchronise.  The
+line carries both arms' ms per step (median over blocks), their block times and spreads and the ratio.
 
     python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--bf16] [--I 4096 --null-share 0.5] [--world N] [--resident] [--optim RULE]
+                                           [--images [--S 256 --body-div 1 --body-hw 224]]
                                            [--blocks 5 --steps 10 --warmup 5] [--out FILE]
 """
 import argparse
@@ -62,6 +69,117 @@ def step_flops(B, T, V, E, R, L, arch=1, te=None, I=0):
     return 3 * fwd
 
 
+def body_weights(vgg_div, hw, count, seed=7):
+    """He-scaled random weights in nvqa_vgg16_set_weights order (no caffemodel here): activations keep their scale layer by layer"""
+    rng = np.random.default_rng(seed)
+    parts, cin = [], 3
+    for c in (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512):
+        co = max(1, c // vgg_div)
+        parts += [rng.standard_normal(co * cin * 9, np.float32) * np.float32(np.sqrt(2.0 / (cin * 9))), rng.uniform(0.0, 0.1, co).astype(np.float32)]
+        cin = co
+    F = max(4, 4096 // vgg_div)
+    for k in (cin * (hw // 32) ** 2, F):
+        parts += [rng.standard_normal(F * k, np.float32) * np.float32(np.sqrt(2.0 / k)), rng.uniform(0.0, 0.1, F).astype(np.float32)]
+    w = np.concatenate(parts)
+    assert w.size == count
+    return w
+
+
+def images_main(a, pkg):
+    """--images: the in-loop step against the composed route, alternating in one job"""
+    b = pkg.binding
+    B = a.B if a.B != 1000 else {5: 20, 6: 16}[a.arch]
+    vgg = b.Vgg16(0, a.body_div, a.body_hw, max_batch=B)
+    vgg.set_weights(body_weights(a.body_div, a.body_hw, vgg.weight_count))
+    I = vgg.feature_dim
+    arch = {5: b.ARCH_AE2_WP, 6: b.ARCH_AE1_WP}[a.arch]
+    dims = b.Dims(arch, B, a.D, a.V, a.E, a.R, a.L, I, 2 * a.R if a.arch == 6 else 0, 0)
+    lr = {5: 1e-5, 6: 3e-5}[a.arch]
+    enc_state = np.tile(np.random.default_rng(3).uniform(-0.5, 0.5, 2 * a.R).astype(np.float32), (B, 1))
+
+    def make_ctx():  # one context per arm, the same start
+        ctx = b.Context(dims, 0)
+        ctx.init_params(123, -0.08, 0.08)
+        if a.arch == 6:
+            x = ctx.get_params()
+            x[-ctx.segments()[2]:] = pkg.ae.WeakPairedAE1Trainer.bridge_init(dims, 123)
+            ctx.set_params(x)
+            ctx.ae1_wp_set_lookup(np.random.default_rng(2).uniform(-0.08, 0.08, (a.V + 1, a.E)).astype(np.float32))
+        return ctx
+
+    rng = np.random.default_rng(0)
+    batches, images = [], []
+    for _ in range(4):
+        lens = rng.integers(3, a.D + 1, B)
+        tok = np.zeros((B, a.D), np.int32)
+        for i, n in enumerate(lens):
+            tok[i, :n] = rng.integers(1, a.V + 1, n)
+        batches.append(tok)
+        images.append(rng.integers(0, 256, (B, 3, a.S, a.S), dtype=np.uint8))
+    null = np.random.default_rng(1).random(4096) < a.null_share
+    arms = {"in_loop": make_ctx(), "composed": make_ctx()}
+    its = {k: 0 for k in arms}
+
+    def one_step(arm, want_loss=False):
+        its[arm] += 1
+        it = its[arm]
+        ctx, k = arms[arm], it % len(batches)
+        xoff, yoff = pkg.ae.crop_origin_train(123, it, a.S, a.body_hw)
+        bdr, dr = b.Dropout(1, 0.5, 123, it), b.Dropout(1, 0.5, 123, it)
+        skip = bool(null[it % null.size])
+        if a.arch == 5:
+            enc = {"enc_tokens": None if skip else batches[k]}
+        else:
+            enc = {"enc_state": enc_state} if skip else {"enc_tokens": batches[k]}
+        if arm == "in_loop":
+            step = ctx.ae_wp_step_images if a.arch == 5 else ctx.ae1_wp_step_images
+            loss = step(vgg, images[k], xoff, yoff, batches[k], body_dropout=bdr, dropout=dr, want_loss=want_loss, **enc)
+        else:
+            feats = vgg.fc7_raw(images[k], xoff, yoff, dropout=bdr)  # to the host and back
+            step = ctx.ae_wp_step if a.arch == 5 else ctx.ae1_wp_step
+            loss = step(feats, batches[k], dropout=dr, want_loss=want_loss, **enc)
+        ctx.adam_update(lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
+        return loss
+
+    def timed_block(arm):
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            one_step(arm)
+        arms[arm].sync()
+        return (time.perf_counter() - t0) * 1e3 / a.steps
+
+    for arm in arms:
+        for _ in range(a.warmup):
+            one_step(arm)
+        arms[arm].sync()
+    blocks = {k: [] for k in arms}
+    for _ in range(a.blocks):
+        for arm in arms:
+            blocks[arm].append(timed_block(arm))
+    # both arms have run the same steps: the next one must give the same loss, bit for bit
+    losses = {arm: one_step(arm, want_loss=True) for arm in arms}
+    for c in arms.values():
+        c.close()
+    vgg.close()
+    med = {k: float(np.median(v)) for k, v in blocks.items()}
+    line = {"workload": "ae_arch%d_weakpaired_images" % a.arch, "B": B, "S": a.S, "body_div": a.body_div, "body_hw": a.body_hw,
+            "I": I, "D": a.D, "V": a.V, "E": a.E, "R": a.R, "L": a.L, "null_share": a.null_share,
+            "blocks": a.blocks, "steps_per_block": a.steps, "warmup": a.warmup, "order": list(arms),
+            "loss_in_loop": losses["in_loop"], "loss_composed": losses["composed"],
+            "losses_bit_equal": bool(losses["in_loop"] == losses["composed"])}
+    for k in arms:
+        line["ms_per_step_" + k] = round(med[k], 4)
+        line["block_ms_" + k] = [round(x, 4) for x in blocks[k]]
+        line["block_spread_pct_" + k] = round(100.0 * (max(blocks[k]) - min(blocks[k])) / med[k], 2)
+    line["composed_over_in_loop"] = round(med["composed"] / med["in_loop"], 4)
+    line["images_per_s_in_loop"] = round(B / (med["in_loop"] * 1e-3), 1)
+    s = json.dumps(line)
+    print(s)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", type=int, default=1, choices=(1, 2, 5, 6))
@@ -80,8 +198,16 @@ def main():
     ap.add_argument("--world", type=int, default=1)
     ap.add_argument("--resident", action="store_true")
     ap.add_argument("--optim", default="adam", choices=("rmsprop", "adagrad", "sgd", "sgdm", "sgdmom", "adam"))
+    ap.add_argument("--images", action="store_true")
+    ap.add_argument("--S", type=int, default=256)
+    ap.add_argument("--body-div", type=int, default=1)
+    ap.add_argument("--body-hw", type=int, default=224)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.images:
+        if a.arch not in (5, 6) or a.world > 1 or a.resident or a.bf16 or a.optim != "adam":
+            ap.error("--images: the body in the loop is for --arch 5 | 6 alone")
+        return images_main(a, ge.load_package())
     if a.world < 1 or (a.world > 1 and a.arch not in (1, 2)):
         ap.error("--world: data parallel is for --arch 1 | 2 (the weak-paired contexts refuse a communicator)")
     if a.resident and (a.arch not in (1, 2) or a.world > 1):
