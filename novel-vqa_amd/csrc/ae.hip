@@ -9,21 +9,11 @@
 // signature the auto-encoder calls: 003_train_vqa_arch2/misc/LSTM_decoder.lua (001's copy has only lstm_conventional and no
 // LogSoftMax).
 //
-// Layout of one step (B rows, tmax = last column of the batch with a non-null token, Q = 2 tmax + 1 chain steps):
-//   chain step q < tmax      : encoder step q                 (input: lookup of tok[:, q], 0 -> 1)
-//   chain step q = tmax + s  : decoder step s, s = 0 .. tmax   (input: START, then lookup of tok[:, s-1], 0 -> 1)
-// The image-first-token auto-encoder (NVQA_ARCH_AE2, misc/AutoEncoder.lua with 001_train_arch2_text_autoencoder.lua) runs
-// the same chain with te = tmax + 2 encoder steps (Q = 2 tmax + 3):
-//   chain step 0             : encoder step 0: the image row [B x E] (zeros in the text script)
-//   chain step 1             : encoder step 1: START
-//   chain step q in [2, te)  : encoder step q: lookup of tok[:, q-2], 0 -> 1
-//   chain step q = te + s    : decoder step s, as above
-// with a plain LookupTable (no Dropout, no Tanh), and d(images) = layer 0's d(input) rows of chain step 0.
-// The weak-paired auto-encoder (NVQA_ARCH_AE2_WP, misc/AutoEncoderNull.lua with 004_train_arch2_weakpaired_autoencoder_*.lua)
-// is AE2's chain with two token streams: the encoder reads enc_tokens (te = 2 + tmax(enc_tokens), 2 for the null sentence),
-// the decoder and the criterion read tokens (tmax(tokens) + 1 steps).  Chain step 0 is x0 = L2Normalize(feats) W_p^T + b_p,
-// written by the projection GEMM; the lookup table is frozen (no lookup gradient), so layer 0's d(input) is needed for chain
-// step 0 only, where it is dx0, the projection's output gradient.
+// The chain of one step (te encoder steps, then tmax + 1 decoder steps) and the token each step is fed on every arch are laid out
+// in ae_chain.h, which holds the integer rules of a step once for the kernels and the host paths.  The image-first-token
+// auto-encoder (NVQA_ARCH_AE2) is misc/AutoEncoder.lua with 001_train_arch2_text_autoencoder.lua; the weak-paired one
+// (NVQA_ARCH_AE2_WP: AE2's chain with two token streams, the projected features as the image row, a frozen lookup table) is
+// misc/AutoEncoderNull.lua with 004_train_arch2_weakpaired_autoencoder_*.lua.
 // Per layer, one array of states over the whole chain (slot 0 = the zero initial state, slot q+1 = after chain step q):
 // the decoder's initial state IS the encoder's final slot, and in the backward pass the decoder's state gradient at its
 // step 0 flows into the encoder's last step through the ordinary recurrent product, with the encoder's W_h2h replaced by
@@ -48,6 +38,7 @@
 #include <vector>
 
 #include "ae_bridge.h"
+#include "ae_chain.h"
 #include "ae_decode.h"
 #include "gemm_f32.h"
 #include "nvqa_ctx.h"
@@ -76,12 +67,26 @@ struct AeBody {
     const nvqa_dropout *dr;
 };
 
+// one batch as an entry point hands it over: the fields it has, the rest zero.  A parameter record and nothing more.
+struct AeBatch {
+    int n;                     // valid rows (a training step: B, set by ae_step_impl)
+    const int32_t *tokens;     // [n x D]
+    const float *images;       // AE2: [n x E], NULL: zero image rows
+    const float *feats;        // weak-paired: [n x I], NULL with body
+    const int32_t *enc_tokens; // weak-paired: [n x D], NULL: the null sentence (AE1_WP with enc_state: the encoder is skipped)
+    const float *enc_state;    // AE1_WP: [n x 2R]
+    const AeBody *body;        // weak-paired: the extractor in front of the step, in place of feats
+};
+
 struct AeState {
+    std::vector<void *> dev, pinned; // every hipMalloc / hipHostMalloc of this state but the corpus: ae_destroy's list
+    int flags = 0;       // AE_CHAIN_* (ae_chain.h)
     bool ae2 = false;    // NVQA_ARCH_AE2 (and AE2_WP): image row and START in front of the encoder's tokens
     bool wp = false;     // NVQA_ARCH_AE2_WP: projected features as the image row, encoder tokens of their own, frozen lookup
     int D = 0, QM = 0;   // seq_length; chain steps the buffers hold (AE1 2 D + 1, AE2 2 D + 3)
     int ldl = 0;         // leading dimension of the logits (V + 1 rounded up to 4 floats; the padding columns stay zero)
     int tmax = 0;        // last step's tmax
+    int ncount = 0;      // last step's criterion count n (ae_chain.h criterion_count over the valid rows)
     int te = 0;          // last step's encoder steps = the chain step of decoder step 0 (AE1 tmax, AE2 tmax + 2)
     int dstr = 0;        // the D of the dropout counter indices (AE1 D, AE2 D + 1: a step stride of D + 2, nvqa_rng.h)
     float *img = nullptr;       // AE2: [B x E] image rows of the current batch (device); NULL input -> img_live = false
@@ -176,13 +181,21 @@ struct AeState {
     int32_t *bm_cc = nullptr;
 };
 
-static int ae_alloc(void **p, size_t bytes)
+// zeroed device memory, recorded in own (NULL: the caller frees it); zs: the zero fill runs on that stream instead of the null one
+static int ae_alloc(std::vector<void *> *own, void **p, size_t bytes, hipStream_t zs = nullptr)
 {
-    NVQA_HIP(hipMalloc(p, std::max<size_t>(bytes, 16)));
-    NVQA_HIP(hipMemset(*p, 0, std::max<size_t>(bytes, 16)));
+    bytes = std::max<size_t>(bytes, 16);
+    NVQA_HIP(hipMalloc(p, bytes));
+    if (own) own->push_back(*p);
+    NVQA_HIP(zs ? hipMemsetAsync(*p, 0, bytes, zs) : hipMemset(*p, 0, bytes));
     return 0;
 }
-#define AE_ALLOC(ptr, count) NVQA_TRY(ae_alloc((void **)&(ptr), (size_t)(count) * sizeof(*(ptr))))
+#define AE_ALLOC(ptr, count) NVQA_TRY(ae_alloc(&c->ae->dev, (void **)&(ptr), (size_t)(count) * sizeof(*(ptr))))
+#define AE_PINNED(ptr, count)                                                                           \
+    do {                                                                                                \
+        NVQA_HIP(hipHostMalloc((void **)&(ptr), (size_t)(count) * sizeof(*(ptr)), hipHostMallocDefault)); \
+        c->ae->pinned.push_back(ptr);                                                                   \
+    } while (0)
 
 static GemmArgs ae_args(const float *A, int lda, const float *B, int ldb, int M, int N, int K, int kslice = 0)
 {
@@ -207,63 +220,37 @@ static Drop ae_drop(const nvqa_dropout *dr, bool train)
 // ------------------------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------------------------
-// token fed at chain step q of row b (1-based): encoder tok[b][q], decoder START (V+1) at s = 0, then tok[b][s-1]; 0 -> 1
-// (AutoEncoder_text_nostart.lua:249-262, :302-319).  `direct` (greedy decoding): the decoder's token comes from it.
-__device__ __forceinline__ int ae_token(const int32_t *tok, const int32_t *direct, int b, int q, int tmax, int D, int V)
+// the counter index of the lookup Dropout at chain row (q, b): te = tmax on AE1, the one arch that draws it
+__device__ __forceinline__ uint64_t ae_lk_idx(int b, int q, int te, int D, int E, int e, uint32_t *site)
 {
-    int v;
-    if (q < tmax) v = tok[(size_t)b * D + q];
-    else {
-        const int s = q - tmax;
-        v = s == 0 ? V + 1 : (direct ? direct[b] : tok[(size_t)b * D + s - 1]);
-    }
-    return v == 0 ? 1 : v;
-}
-__device__ __forceinline__ uint64_t ae_lk_idx(int b, int q, int tmax, int D, int E, int e, uint32_t *site)
-{
-    if (q < tmax) { *site = NVQA_SITE_AE_ENC_LK; return ((uint64_t)b * D + q) * E + e; }
+    if (q < te) { *site = NVQA_SITE_AE_ENC_LK; return ((uint64_t)b * D + q) * E + e; }
     *site = NVQA_SITE_AE_DEC_LK;
-    return ((uint64_t)b * (D + 1) + (q - tmax)) * E + e;
+    return ((uint64_t)b * (D + 1) + (q - te)) * E + e;
 }
 
-// LookupTable -> Dropout -> Tanh (AutoEncoder_text_nostart.lua:28-31) for chain steps [q0, q0 + nq): one workgroup per row
-__global__ void k_ae_embed(const int32_t *tok, const int32_t *direct, int B, int D, int V, int E, int tmax, int q0,
-                           const float *Wlk, Drop dr, float *X0)
+// LookupTable -> Dropout -> Tanh (AutoEncoder_text_nostart.lua:28-31) of chain_token, chain steps from q0 on: one workgroup per row
+__global__ void k_ae_embed(AeChain ch, const int32_t *enc, const int32_t *dec, const int32_t *direct, int E, int q0, const float *Wlk,
+                           Drop dr, float *X0)
 {
-    const int r = q0 * B + blockIdx.x, q = r / B, b = r % B;
-    const int v = ae_token(tok, direct, b, q, tmax, D, V);
-    const float *w = Wlk + (size_t)(v - 1) * E;
+    const int r = q0 * ch.B + blockIdx.x, q = r / ch.B, b = r % ch.B;
+    const float *w = Wlk + (size_t)(chain_token(ch, enc, dec, direct, q, b) - 1) * E;
     for (int e = threadIdx.x; e < E; e += blockDim.x) {
         uint32_t site;
-        const uint64_t idx = ae_lk_idx(b, q, tmax, D, E, e, &site);
+        const uint64_t idx = ae_lk_idx(b, q, ch.te, ch.D, E, e, &site);
         X0[(size_t)r * E + e] = tanhf(dr.scale(site, idx) * w[e]);
     }
 }
 
-// AE2 layer-0 input X0 of chain steps [q0, q0 + gridDim.x / B) in one pass (AutoEncoder.lua:258-291, :318-348): encoder step 0
-// = the image row (img; NULL: zeros), encoder step 1 and decoder step 0 = START (V+1), encoder step q >= 2 = lookup of
-// tok[:, q-2], decoder step s >= 1 = lookup of tok[:, s-1] (greedy decoding: of direct[b]); 0 -> 1.  A plain nn.LookupTable
-// (:28): no dropout, no tanh.  One workgroup per row.
-__global__ void k_ae2_assemble(const int32_t *tok, const int32_t *direct, const float *img, int B, int D, int V, int E, int te,
+// AE2 layer-0 input X0 of chain steps [q0, q0 + gridDim.x / B) in one pass (AutoEncoder.lua:258-291, :318-348): the image row
+// (img; NULL: zeros) where chain_token has none, else its row of a plain nn.LookupTable (:28): no dropout, no tanh.  One
+// workgroup per row.
+__global__ void k_ae2_assemble(AeChain ch, const int32_t *enc, const int32_t *dec, const int32_t *direct, const float *img, int E,
                                int q0, const float *Wlk, float *X0)
 {
-    const int r = q0 * B + blockIdx.x, q = r / B, b = r % B;
-    float *x = X0 + (size_t)r * E;
-    const float *w;
-    if (q == 0) {
-        if (!img) {
-            for (int e = threadIdx.x; e < E; e += blockDim.x) x[e] = 0.f;
-            return;
-        }
-        w = img + (size_t)b * E;
-    } else {
-        int v;
-        if (q == 1 || q == te) v = V + 1;
-        else if (q < te) v = tok[(size_t)b * D + q - 2];
-        else v = direct ? direct[b] : tok[(size_t)b * D + q - te - 1];
-        w = Wlk + (size_t)((v == 0 ? 1 : v) - 1) * E;
-    }
-    for (int e = threadIdx.x; e < E; e += blockDim.x) x[e] = w[e];
+    const int r = q0 * ch.B + blockIdx.x, q = r / ch.B, b = r % ch.B;
+    const int v = chain_token(ch, enc, dec, direct, q, b);
+    const float *w = v ? Wlk + (size_t)(v - 1) * E : (img ? img + (size_t)b * E : nullptr);
+    for (int e = threadIdx.x; e < E; e += blockDim.x) X0[(size_t)r * E + e] = w ? w[e] : 0.f;
 }
 
 // inter-layer / top-h dropout (forward: out = scale * in; backward: the same scale on the gradient).
@@ -319,8 +306,7 @@ __device__ __forceinline__ void ae_lse_combine(float &m, float &s, float m2, flo
 }
 
 // LanguageModelCriterion (AutoEncoder_text_nostart.lua:416-450) over LogSoftMax (LSTM_decoder.lua of 003, :60-61):
-// one workgroup per row (s, b) of the logits.  The target is found here from the token matrix: tok[b][s] if non-null, END
-// (= V+1) at the first null (or s = D), nothing after it.  Statistics with an online max / sum-exp (one read of the row);
+// one workgroup per row (s, b) of the logits, its target criterion_target's.  Statistics with an online max / sum-exp (one read);
 // target rows then get (softmax - onehot) / n in place, rows without a target zeros (grad != 0).  nvalid: rows b >= nvalid
 // carry no loss (nvqa_ae_evaluate with n < B).  Row losses go to rowloss; their sum is taken by k_ae_loss in a fixed order.
 // IMG (bf16 operand mode, grad != 0): the f32 logits stay as they are; (softmax - onehot) / n goes out rounded to bf16 into the
@@ -335,17 +321,7 @@ __global__ __launch_bounds__(256) void k_ae_softmax(float *logits, int ldl, int 
     __shared__ float sh_lse;
     const int row = blockIdx.x, s = row / B, b = row % B;
     float *x = logits + (size_t)row * ldl;
-    int tgt = -1;
-    if (b < nvalid) {
-        const int32_t *t = tok + (size_t)b * D;
-        const int v = s < D ? t[s] : 0;
-        if (v != 0) tgt = v - 1;
-        else {
-            bool earlier = false;
-            for (int k = 0; k < s; ++k) earlier |= t[k] == 0;
-            if (!earlier) tgt = Vp1 - 1;
-        }
-    }
+    const int tgt = b < nvalid ? criterion_target(tok + (size_t)b * D, s, D, Vp1 - 1) : -1;
     if (tgt < 0) {
         if (threadIdx.x == 0) rowloss[row] = 0.f;
         if constexpr (IMG) {
@@ -571,7 +547,6 @@ __global__ void k_ae_slab_sum(const float *slabs, int Z, size_t n, float *out)
 // sums each chunk through the backward of Tanh and Dropout, pass 2 adds a token's chunks in order.  (One workgroup per
 // token summing all its rows serially took 13 ms at the default shape: the START token alone has B rows, the padding
 // token 1 thousands.)  Rows of tokens absent from the batch were zeroed by the caller.
-#define NVQA_AE_LK_CHUNK 16
 // cnt (the device-built index of a resident step): the launch's grid is an upper bound, workgroups past *cnt return
 __global__ void k_ae_lk_part(const int32_t *lk_start, const int32_t *lk_pos, const float *X0, const float *dX, int B, int D,
                              int E, int tmax, Drop dr, float *part, const int32_t *cnt)
@@ -626,24 +601,13 @@ __global__ void k_ae_gather_rows(const int32_t *corpus, QIdxArg ids, int b0, int
     tok[(size_t)b * D + t] = b < n ? corpus[(size_t)ids.q[bl] * D + t] : 0;
 }
 
-// the token the lookup gradient books chain row (q, b) under (ae_upload's index loop): START = V + 1 at the decoder's first step
-// (AE2: also at encoder step 1; its chain step 0, the image row, is never asked for), 0 -> 1
-__device__ __forceinline__ int ae_chain_token(const int32_t *tok, int b, int q, int te, int D, int V, bool ae2)
-{
-    int v;
-    if (q == te || (ae2 && q == 1)) v = V + 1;
-    else if (q < te) v = tok[(size_t)b * D + q - (ae2 ? 2 : 0)];
-    else v = tok[(size_t)b * D + q - te - 1];
-    return v == 0 ? 1 : v;
-}
-
 // hist[q][v] = rows of chain step q that carry token v (W = V + 2 bins per step).  Integer counts: their order does not matter.
-__global__ void k_ae_lk_hist(const int32_t *tok, int B, int D, int V, int te, int ae2, int r_lo, int np, int32_t *hist)
+__global__ void k_ae_lk_hist(AeChain ch, const int32_t *tok, int r_lo, int np, int32_t *hist)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= np) return;
-    const int r = r_lo + i, q = r / B, b = r % B;
-    atomicAdd(hist + (size_t)q * (V + 2) + ae_chain_token(tok, b, q, te, D, V, ae2 != 0), 1);
+    const int r = r_lo + i, q = r / ch.B, b = r % ch.B;
+    atomicAdd(hist + (size_t)q * (ch.V + 2) + chain_token(ch, tok, tok, nullptr, q, b), 1);
 }
 
 // per token: base[q][v] = its rows in the chain steps before q, tot[v] = all its rows.  One thread per token.
@@ -727,18 +691,18 @@ __global__ __launch_bounds__(NVQA_AE_SCAN_NT) void k_ae_lk_scan(int V, int32_t *
 // chain row (q, b) goes to slot first[v] + base[q][v] + (rows b' < b of step q with the same token): ascending chain rows inside
 // a token, whatever the schedule.  Workgroup (q, block of 256 rows); the step's tokens pass through LDS 256 at a time.  A row
 // that opens a chunk writes the chunk's start.
-__global__ __launch_bounds__(256) void k_ae_lk_rank(const int32_t *tok, int B, int D, int V, int te, int ae2, int q_lo,
-                                                    const int32_t *base, const int32_t *first, const int32_t *chb, int32_t *lk_start,
-                                                    int32_t *lk_pos)
+__global__ __launch_bounds__(256) void k_ae_lk_rank(AeChain ch, const int32_t *tok, int q_lo, const int32_t *base, const int32_t *first,
+                                                    const int32_t *chb, int32_t *lk_start, int32_t *lk_pos)
 {
     __shared__ int tile[256];
+    const int B = ch.B, V = ch.V;
     const int q = q_lo + blockIdx.x, bg = blockIdx.y * 256, b = bg + (int)threadIdx.x;
-    const int v = b < B ? ae_chain_token(tok, b, q, te, D, V, ae2 != 0) : -1;
+    const int v = b < B ? chain_token(ch, tok, tok, nullptr, q, b) : -1;
     int rank = 0;
     for (int j0 = 0; j0 < min(B, bg + 256); j0 += 256) {
         __syncthreads();
         const int j = j0 + (int)threadIdx.x;
-        tile[threadIdx.x] = j < B ? ae_chain_token(tok, j, q, te, D, V, ae2 != 0) : 0;
+        tile[threadIdx.x] = j < B ? chain_token(ch, tok, tok, nullptr, q, j) : 0;
         __syncthreads();
         const int lim = min(256, b - j0);
         for (int k = 0; k < lim; ++k) rank += tile[k] == v ? 1 : 0;
@@ -983,6 +947,7 @@ int ae_create(nvqa_ctx *c)
     a.wp = d.arch == NVQA_ARCH_AE2_WP;
     a.bridge = d.arch == NVQA_ARCH_AE1_WP;
     a.feats = a.wp || a.bridge;
+    a.flags = (a.ae2 ? AE_CHAIN_AE2 : 0) | (a.bridge ? AE_CHAIN_BRIDGE : 0) | (a.feats ? AE_CHAIN_ENC : 0);
     a.D = (int)D;
     a.QM = (int)(2 * D + (a.ae2 ? 3 : 1));
     a.dstr = (int)D + (a.ae2 ? 1 : 0);
@@ -996,9 +961,9 @@ int ae_create(nvqa_ctx *c)
         c->lo.b_proj = c->lo.total - nb;
         c->lo.w_lk = total4;
     }
-    AE_ALLOC(c->P, total4 + (a.bridge ? (V + 1) * E : 0));
-    AE_ALLOC(c->G, total4);
-    AE_ALLOC(c->M2, total4);
+    NVQA_TRY(ae_alloc(nullptr, (void **)&c->P, (total4 + (a.bridge ? (V + 1) * E : 0)) * 4)); // (these three are nvqa_destroy's)
+    NVQA_TRY(ae_alloc(nullptr, (void **)&c->G, total4 * 4));
+    NVQA_TRY(ae_alloc(nullptr, (void **)&c->M2, total4 * 4));
     AE_ALLOC(a.tok, B * D);
     AE_ALLOC(a.nrows, 1);
     {
@@ -1013,20 +978,20 @@ int ae_create(nvqa_ctx *c)
         AE_ALLOC(a.lk_start, QM * B + 1);
         AE_ALLOC(a.lk_pos, QM * B);
         AE_ALLOC(a.lk_part, QM * B * E);
-        NVQA_HIP(hipHostMalloc((void **)&a.h_lk, (4 * QM * B + 4) * 4, hipHostMallocDefault));
+        AE_PINNED(a.h_lk, 4 * QM * B + 4);
     }
-    NVQA_HIP(hipHostMalloc((void **)&a.h_tok, B * D * 4, hipHostMallocDefault));
-    NVQA_HIP(hipHostMalloc((void **)&a.h_loss, 16, hipHostMallocDefault));
+    AE_PINNED(a.h_tok, B * D);
+    AE_PINNED(a.h_loss, 4);
     if (a.ae2 && !a.wp) {
         AE_ALLOC(a.img, B * E);
-        NVQA_HIP(hipHostMalloc((void **)&a.h_img, B * E * 4, hipHostMallocDefault));
+        AE_PINNED(a.h_img, B * E);
     }
     if (a.feats) {
         const size_t I = d.I;
         AE_ALLOC(a.etok, B * D);
-        NVQA_HIP(hipHostMalloc((void **)&a.h_etok, B * D * 4, hipHostMallocDefault));
+        AE_PINNED(a.h_etok, B * D);
         AE_ALLOC(a.feat, B * I);
-        NVQA_HIP(hipHostMalloc((void **)&a.h_feat, B * I * 4, hipHostMallocDefault));
+        AE_PINNED(a.h_feat, B * I);
         NVQA_HIP(hipEventCreateWithFlags(&a.staged, hipEventDisableTiming));
     }
     if (a.bridge) {
@@ -1035,7 +1000,7 @@ int ae_create(nvqa_ctx *c)
         NVQA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
         a.plan = ae1wp_bridge_plan((int)B, (int)N, (int)N, (int)I, cus > 0 ? cus : 256);
         AE_ALLOC(a.jbuf, B * N);
-        NVQA_HIP(hipHostMalloc((void **)&a.h_j, B * N * 4, hipHostMallocDefault));
+        AE_PINNED(a.h_j, B * N);
         AE_ALLOC(a.qd, B * N);
         AE_ALLOC(a.vd, B * I);
         AE_ALLOC(a.qc, B * N);
@@ -1086,19 +1051,11 @@ void ae_destroy(nvqa_ctx *c)
 {
     if (!c->ae) return;
     AeState &a = *c->ae;
-    void *ptrs[] = {a.corpus, a.lk_hist, a.lk_base, a.lk_tot, a.lk_chb, a.lk_cnt, a.Htd16, a.G16, a.Wp16, a.WpT16, a.rowlse, a.rowtgt, a.tok, a.nrows, a.cur, a.samples, a.lk_tok, a.lk_tc, a.lk_start, a.lk_pos, a.lk_part, a.X0, a.dX, a.dHx, a.dc, a.Htd,
-                    a.logits, a.rowloss, a.loss, a.dpw, a.slabs, a.colpart, a.img, a.etok, a.feat, a.wp_x, a.wp_g, a.wp_m, a.wp_v,
-                    a.wp_vel, a.wp_part, a.jbuf, a.qd, a.vd, a.qc, a.ic, a.dqp, a.dvp, a.dh0, a.dfeat, a.br_slabs,
-                    a.slp, a.bm_bp, a.bm_tk, a.bm_lp, a.bm_score, a.bm_fin, a.bm_csc, a.bm_clp, a.bm_cc};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
+    for (void *p : a.dev) (void)hipFree(p);
+    for (void *p : a.pinned) (void)hipHostFree(p);
+    if (a.corpus) (void)hipFree(a.corpus);
     if (a.staged) (void)hipEventDestroy(a.staged);
     if (a.step_ev) (void)hipEventDestroy(a.step_ev);
-    for (int l = 0; l < NVQA_MAX_LAYERS; ++l)
-        for (void *p : {(void *)a.Gt[l], (void *)a.Hs[l], (void *)a.Cs[l], (void *)a.U[l], (void *)a.bm_h[l], (void *)a.bm_c[l]})
-            if (p) (void)hipFree(p);
-    for (void *p : {(void *)a.h_lk, (void *)a.h_tok, (void *)a.h_loss, (void *)a.h_img, (void *)a.h_etok, (void *)a.h_feat, (void *)a.h_j})
-        if (p) (void)hipHostFree(p);
     delete c->ae;
     c->ae = nullptr;
 }
@@ -1195,37 +1152,25 @@ static int ae_project(nvqa_ctx *c, int s0, int s1, const Drop &dr)
     return 0;
 }
 
+static inline AeChain ae_chain(const nvqa_ctx *c) { return {c->d.B, c->ae->D, c->d.V, c->ae->te, c->ae->tmax + 1, c->ae->flags}; }
+
+// layer-0 inputs of chain steps [q0, q1): one launch.  The weak-paired archs read the encoder's tokens from etok and run the
+// frozen lookup evaluate()d (AE1_WP: no mask, AutoEncoder_vqa_arch.lua:133-134); AE2_WP's chain row 0 is ae_wp_project's
 static int ae_embed(nvqa_ctx *c, int q0, int q1, const int32_t *direct, const Drop &dr)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
+    if (a.wp) q0 = std::max(q0, 1);
     if (q1 <= q0) return 0;
     ProfScope ps(c, PF_AE_EMB, 0, (double)(q1 - q0) * d.B * d.E * 8);
-    if (a.bridge) { // AE1's lookup per token stream, evaluate()d (no mask: AutoEncoder_vqa_arch.lua:133-134), from the table behind the vector
-        const int e1 = std::min(q1, a.te), d0 = std::max(q0, a.te);
-        const dim3 nt(std::min(256, (d.E + 63) / 64 * 64));
-        const Drop none = ae_drop(nullptr, false);
-        if (e1 > q0)
-            hipLaunchKernelGGL(k_ae_embed, dim3((unsigned)((e1 - q0) * d.B)), nt, 0, c->s, a.etok, (const int32_t *)nullptr, d.B, a.D,
-                               d.V, d.E, a.te, q0, c->P + c->lo.w_lk, none, a.X0);
-        if (q1 > d0)
-            hipLaunchKernelGGL(k_ae_embed, dim3((unsigned)((q1 - d0) * d.B)), nt, 0, c->s, a.tok, direct, d.B, a.D, d.V, d.E, a.te,
-                               d0, c->P + c->lo.w_lk, none, a.X0);
-    } else if (a.wp) { // AE2's assembly per token stream: encoder rows [1, te) from etok, decoder rows from tok; row 0 is ae_wp_project's
-        const int e0 = std::max(q0, 1), e1 = std::min(q1, a.te), d0 = std::max(q0, a.te);
-        const dim3 nt(std::min(256, (d.E + 63) / 64 * 64));
-        if (e1 > e0)
-            hipLaunchKernelGGL(k_ae2_assemble, dim3((unsigned)((e1 - e0) * d.B)), nt, 0, c->s, a.etok, (const int32_t *)nullptr,
-                               (const float *)nullptr, d.B, a.D, d.V, d.E, a.te, e0, c->P + c->lo.w_lk, a.X0);
-        if (q1 > d0)
-            hipLaunchKernelGGL(k_ae2_assemble, dim3((unsigned)((q1 - d0) * d.B)), nt, 0, c->s, a.tok, direct, (const float *)nullptr,
-                               d.B, a.D, d.V, d.E, a.te, d0, c->P + c->lo.w_lk, a.X0);
-    } else if (a.ae2)
-        hipLaunchKernelGGL(k_ae2_assemble, dim3((unsigned)((q1 - q0) * d.B)), dim3(std::min(256, (d.E + 63) / 64 * 64)), 0, c->s,
-                           a.tok, direct, a.img_live ? a.img : nullptr, d.B, a.D, d.V, d.E, a.te, q0, c->P + c->lo.w_lk, a.X0);
+    const dim3 grid((unsigned)((q1 - q0) * d.B)), nt(std::min(256, (d.E + 63) / 64 * 64));
+    const int32_t *enc = a.feats ? a.etok : a.tok;
+    if (a.ae2)
+        hipLaunchKernelGGL(k_ae2_assemble, grid, nt, 0, c->s, ae_chain(c), enc, (const int32_t *)a.tok, direct,
+                           (const float *)(a.img_live ? a.img : nullptr), d.E, q0, c->P + c->lo.w_lk, a.X0);
     else
-        hipLaunchKernelGGL(k_ae_embed, dim3((unsigned)((q1 - q0) * d.B)), dim3(std::min(256, (d.E + 63) / 64 * 64)), 0, c->s, a.tok,
-                           direct, d.B, a.D, d.V, d.E, a.tmax, q0, c->P + c->lo.w_lk, dr, a.X0);
+        hipLaunchKernelGGL(k_ae_embed, grid, nt, 0, c->s, ae_chain(c), enc, (const int32_t *)a.tok, direct, d.E, q0, c->P + c->lo.w_lk,
+                           a.bridge ? ae_drop(nullptr, false) : dr, a.X0);
     NVQA_HIP(hipGetLastError());
     return 0;
 }
@@ -1308,19 +1253,54 @@ static int ae_bridge_backward(nvqa_ctx *c, const Drop &dr, bool want_df)
     return 0;
 }
 
+// bf16 operand mode: this call's bf16 images of W_proj (the weights do not move before the next step)
+static int ae_wproj_images(nvqa_ctx *c)
+{
+    AeState &a = *c->ae;
+    if (!a.p16) return 0;
+    ProfScope ps(c, PF_AE_WPROJ_IMG, 0, (c->d.V + 1.0) * c->d.R * 8);
+    hipLaunchKernelGGL(k_ae_wproj_images, dim3((a.ld16 + 63) / 64, (c->d.R + 63) / 64), dim3(256), 0, c->s, c->P + c->lo.w_proj,
+                       c->d.V + 1, c->d.R, a.ld16, a.Wp16, a.WpT16);
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
+
+// the encoder alone, chain steps [0, te) of every layer: the launches of ae_forward on the encoder's own row counts
+static int ae_run_encoder(nvqa_ctx *c, const Drop &dr)
+{
+    const int te = c->ae->te;
+    NVQA_TRY(ae_embed(c, 0, te, nullptr, dr));
+    for (int l = 0; l < c->d.L; ++l) {
+        if (l > 0) NVQA_TRY(ae_layer_input(c, l, 0, te, dr));
+        NVQA_TRY(ae_i2h(c, l, 0, te, false));
+        for (int q = 0; q < te; ++q) NVQA_TRY(ae_fwd_step(c, l, q, dr));
+    }
+    return 0;
+}
+
+// decoder step s alone, fed START (s = 0) or direct[b], down to its logits.  beam: the step reads bm_h / bm_c, not its state slot
+static int ae_decode_step(nvqa_ctx *c, int s, const int32_t *direct, bool beam)
+{
+    AeState &a = *c->ae;
+    const Drop dr = ae_drop(nullptr, false);
+    const int q = a.te + s;
+    NVQA_TRY(ae_embed(c, q, q + 1, s == 0 ? nullptr : direct, dr));
+    for (int l = 0; l < c->d.L; ++l) {
+        if (l > 0) NVQA_TRY(ae_layer_input(c, l, q, q + 1, dr));
+        NVQA_TRY(ae_i2h(c, l, q, q + 1, true));
+        NVQA_TRY(ae_fwd_step(c, l, q, dr, beam ? a.bm_h[l] : nullptr, beam ? a.bm_c[l] : nullptr));
+    }
+    return ae_project(c, s, s + 1, dr);
+}
+
 // teacher-forced forward of the whole chain (training and evaluate mode) + the criterion; grad: d(logits) in place
-static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, int ncount, bool grad)
+static int ae_forward(nvqa_ctx *c, const Drop &dr, int nvalid, bool grad)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
-    const int B = d.B, L = d.L, Q = a.te + a.tmax + 1, Vp1 = d.V + 1;
+    const int B = d.B, L = d.L, Q = a.te + a.tmax + 1, Vp1 = d.V + 1, ncount = a.ncount;
     if (a.wp) NVQA_TRY(ae_wp_project(c));
-    if (a.p16) { // this step's bf16 images of W_proj (greedy decoding reuses them: the weights do not move before the next step)
-        ProfScope ps(c, PF_AE_WPROJ_IMG, 0, (double)Vp1 * d.R * 8);
-        hipLaunchKernelGGL(k_ae_wproj_images, dim3((a.ld16 + 63) / 64, (d.R + 63) / 64), dim3(256), 0, c->s, c->P + c->lo.w_proj, Vp1,
-                           d.R, a.ld16, a.Wp16, a.WpT16);
-        NVQA_HIP(hipGetLastError());
-    }
+    NVQA_TRY(ae_wproj_images(c)); // (greedy decoding reuses them)
     NVQA_TRY(ae_embed(c, 0, Q, nullptr, dr));
     for (int l = 0; l < L; ++l) {
         if (l > 0) NVQA_TRY(ae_layer_input(c, l, 0, Q, dr));
@@ -1483,63 +1463,51 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
 }
 
 // host side of a batch: tokens -> device, tmax, the criterion's n, and (training) the token -> rows index of the lookup
-// gradient (a counting sort: deterministic row order per token).  AE2: images [n x E] (NULL: zeros) -> the device rows.
-// AE2_WP: enc_tokens [n x D] (NULL: the null sentence) -> etok and te = 2 + their tmax; feats [n x I] -> feat, L2-normalised
-// over the n rows (the padding rows stay zero).  With `body` (feats is then NULL) the features come from the extractor, which
+// gradient (ae_chain.h chain_index).  Weak-paired: enc_tokens -> etok; feats -> feat, L2-normalised over the n rows (the
+// padding rows stay zero).  With `body` the features come from the extractor, which
 // runs here, behind every check of the batch: its stream hands fc7o over by an event, the normalisation reads it straight into
 // feat, and the extractor's next pass waits for that read.
-static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *images, bool index, int *ncount,
-                     const float *feats = nullptr, const int32_t *enc_tokens = nullptr, const float *enc_state = nullptr,
-                     const AeBody *body = nullptr)
+static int ae_stage(const char *what, const int32_t *src, int n, int B, int D, int V, int32_t *dst, int *tmax)
+{
+    TokenFault bad;
+    if (stage_tokens(src, n, B, D, V, dst, tmax, &bad)) return 0;
+    set_error("ae: %s %d at (%d, %d) outside 0..%d", what, bad.value, (int)bad.row, bad.col, V);
+    return -1;
+}
+
+// src [n x w] through the pinned h onto the device's [B x w], rows from n on zero
+static int ae_stage_rows(nvqa_ctx *c, const float *src, size_t n, size_t w, float *h, float *dev)
+{
+    memcpy(h, src, n * w * 4);
+    memset(h + n * w, 0, (c->d.B - n) * w * 4);
+    NVQA_HIP(hipMemcpyAsync(dev, h, c->d.B * w * 4, hipMemcpyHostToDevice, c->s));
+    return 0;
+}
+
+static int ae_upload(nvqa_ctx *c, const AeBatch &bt, bool index)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
-    const int B = d.B, D = a.D, V = d.V;
+    const int B = d.B, D = a.D, V = d.V, n = bt.n;
+    const AeBody *body = bt.body;
     // the staging buffers may still feed the previous step's copies.  AE2_WP waits for those copies only, so that staging its
     // B x I features overlaps the previous step's kernels
     if (a.feats && a.staged_rec) NVQA_HIP(hipEventSynchronize(a.staged));
     else NVQA_HIP(hipStreamSynchronize(c->s));
-    int tmax = 0, cnt = 0;
-    for (int b = 0; b < B; ++b)
-        for (int t = 0; t < D; ++t) {
-            const int v = b < n ? tokens[(size_t)b * D + t] : 0;
-            if (v < 0 || v > V) { set_error("ae: token %d at (%d, %d) outside 0..%d", v, b, t, V); return -1; }
-            a.h_tok[(size_t)b * D + t] = v;
-            if (v) tmax = std::max(tmax, t + 1);
-        }
+    int tmax = 0, tmax_e = 0;
+    NVQA_TRY(ae_stage("token", bt.tokens, n, B, D, V, a.h_tok, &tmax));
     if (tmax == 0) { set_error("ae: the batch holds no token (every row is null)"); return -1; }
-    for (int b = 0; b < n; ++b) { // LanguageModelCriterion's n (:425-445)
-        bool first = true;
-        for (int t = 0; t <= D; ++t) {
-            const int v = t < D ? a.h_tok[(size_t)b * D + t] : 0;
-            if (v) ++cnt;
-            else if (first) { ++cnt; first = false; }
-        }
-    }
-    int tmax_e = 0;
-    if (a.feats) {
-        for (int b = 0; b < B; ++b)
-            for (int t = 0; t < D; ++t) {
-                const int v = b < n && enc_tokens ? enc_tokens[(size_t)b * D + t] : 0;
-                if (v < 0 || v > V) { set_error("ae: enc_tokens %d at (%d, %d) outside 0..%d", v, b, t, V); return -1; }
-                a.h_etok[(size_t)b * D + t] = v;
-                if (v) tmax_e = std::max(tmax_e, t + 1);
-            }
-    }
+    a.ncount = 0;
+    for (int b = 0; b < n; ++b) a.ncount += criterion_count(a.h_tok + (size_t)b * D, D);
+    if (a.feats) NVQA_TRY(ae_stage("enc_tokens", bt.enc_tokens, n, B, D, V, a.h_etok, &tmax_e));
+    a.skip = a.bridge && bt.enc_state;
     a.tmax = tmax;
-    a.te = a.wp ? tmax_e + 2 : (a.ae2 ? tmax + 2 : (a.bridge ? tmax_e : tmax));
-    a.skip = a.bridge && enc_state;
+    a.te = encoder_steps(a.flags, tmax, tmax_e, a.skip);
     if (a.bridge && !a.skip && tmax_e == 0) { set_error("ae: enc_tokens holds no token (every row is null)"); return -1; }
-    *ncount = cnt;
     NVQA_HIP(hipMemcpyAsync(a.tok, a.h_tok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
     if (a.feats) {
         const size_t I = d.I;
-        if (a.skip) {
-            const size_t N = 2 * (size_t)d.R;
-            memcpy(a.h_j, enc_state, (size_t)n * N * 4);
-            if (n < B) memset(a.h_j + (size_t)n * N, 0, (size_t)(B - n) * N * 4);
-            NVQA_HIP(hipMemcpyAsync(a.jbuf, a.h_j, (size_t)B * N * 4, hipMemcpyHostToDevice, c->s));
-        }
+        if (a.skip) NVQA_TRY(ae_stage_rows(c, bt.enc_state, n, 2 * (size_t)d.R, a.h_j, a.jbuf));
         NVQA_HIP(hipMemcpyAsync(a.etok, a.h_etok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
         if (body) {
             NVQA_HIP(hipEventRecord(a.staged, c->s));
@@ -1557,51 +1525,20 @@ static int ae_upload(nvqa_ctx *c, int n, const int32_t *tokens, const float *ima
             }
             NVQA_TRY(nvqa_vgg_features_taken(body->vgg, c->s));
         } else {
-            memcpy(a.h_feat, feats, (size_t)n * I * 4);
-            if (n < B) memset(a.h_feat + (size_t)n * I, 0, (size_t)(B - n) * I * 4);
-            NVQA_HIP(hipMemcpyAsync(a.feat, a.h_feat, (size_t)B * I * 4, hipMemcpyHostToDevice, c->s));
+            NVQA_TRY(ae_stage_rows(c, bt.feats, n, I, a.h_feat, a.feat));
             NVQA_HIP(hipEventRecord(a.staged, c->s));
             a.staged_rec = true;
             ProfScope ps(c, a.bridge ? PF_AE1WP_BRIDGE_FWD : PF_AE_WP_PROJ_FWD, 0, (double)n * I * 12);
             NVQA_TRY(l2norm_rows_launch(c->s, a.feat, n, (int)I));
         }
     }
-    a.img_live = a.ae2 && images;
-    if (a.img_live) {
-        const size_t E = d.E;
-        memcpy(a.h_img, images, (size_t)n * E * 4);
-        if (n < B) memset(a.h_img + (size_t)n * E, 0, (size_t)(B - n) * E * 4);
-        NVQA_HIP(hipMemcpyAsync(a.img, a.h_img, (size_t)B * E * 4, hipMemcpyHostToDevice, c->s));
-    }
+    a.img_live = a.ae2 && bt.images;
+    if (a.img_live) NVQA_TRY(ae_stage_rows(c, bt.images, n, d.E, a.h_img, a.img));
     if (index) {
-        // the rows of chain steps 0 .. Q-1 from r_lo on: AE2's image step (chain step 0) has no token
-        const int TE = a.te, Q = TE + tmax + 1, r_lo = a.ae2 ? B : 0, NP = Q * B - r_lo;
-        std::vector<int> ofs(V + 2, 0), tokr(NP);
-        for (int i = 0; i < NP; ++i) {
-            const int r = r_lo + i, q = r / B, b = r % B;
-            int v;
-            if (q < TE) v = a.ae2 && q == 1 ? V + 1 : a.h_tok[(size_t)b * D + q - (a.ae2 ? 2 : 0)];
-            else v = q == TE ? V + 1 : a.h_tok[(size_t)b * D + q - TE - 1];
-            tokr[i] = v == 0 ? 1 : v;
-            ++ofs[tokr[i]];
-        }
+        const int NP = (a.te + tmax + 1 - (a.ae2 ? 1 : 0)) * B; // every chain row but AE2's image step
         int32_t *ut = a.h_lk + 2, *tc = ut + NP, *cs = tc + NP + 1, *pos = cs + NP + 1;
-        int nu = 0, nch = 0, acc = 0;
-        std::vector<int> at(V + 2, 0);
-        for (int v = 1; v <= V + 1; ++v) {
-            if (!ofs[v]) continue;
-            ut[nu] = v;
-            tc[nu] = nch;
-            for (int k = 0; k < ofs[v]; k += NVQA_AE_LK_CHUNK) cs[nch++] = acc + k;
-            at[v] = acc;
-            acc += ofs[v];
-            ++nu;
-        }
-        tc[nu] = nch;
-        cs[nch] = acc;
-        for (int i = 0; i < NP; ++i) pos[at[tokr[i]]++] = r_lo + i;
-        a.h_lk[0] = nu;
-        a.h_lk[1] = nch;
+        chain_index(ae_chain(c), a.h_tok, a.h_tok, ut, tc, cs, pos, &a.h_lk[0], &a.h_lk[1]);
+        const int nu = a.h_lk[0], nch = a.h_lk[1];
         a.lk_dev = false;
         NVQA_HIP(hipMemcpyAsync(a.lk_tok, ut, (size_t)nu * 4, hipMemcpyHostToDevice, c->s));
         NVQA_HIP(hipMemcpyAsync(a.lk_tc, tc, (size_t)(nu + 1) * 4, hipMemcpyHostToDevice, c->s));
@@ -1649,40 +1586,22 @@ static int ae_check(nvqa_ctx *c)
     return 0;
 }
 
-static int ae_check_images(nvqa_ctx *c, const char *fn)
+// the context's arch must be one of `allowed` (bits 1 << NVQA_ARCH_*): one arch, or AE_TEXT for the calls that carry no features
+#define AE_ARCH(x) (1u << NVQA_ARCH_##x)
+#define AE_TEXT (AE_ARCH(AE1) | AE_ARCH(AE2))
+static int ae_check_arch(nvqa_ctx *c, const char *fn, unsigned allowed)
 {
     NVQA_TRY(ae_check(c));
-    if (c->d.arch != NVQA_ARCH_AE2) { set_error("%s: an NVQA_ARCH_AE2 context expected (arch %d)", fn, c->d.arch); return -1; }
-    return 0;
-}
-
-// AE2_WP: the step carries features; the text calls have none
-static int ae_check_not_wp(nvqa_ctx *c, const char *fn)
-{
-    NVQA_TRY(ae_check(c));
-    if (c->d.arch == NVQA_ARCH_AE2_WP) {
+    const int arch = c->d.arch;
+    if (allowed >> arch & 1u) return 0;
+    if (allowed != AE_TEXT)
+        set_error("%s: an NVQA_ARCH_%s context expected (arch %d)", fn,
+                  allowed == AE_ARCH(AE2) ? "AE2" : (allowed == AE_ARCH(AE2_WP) ? "AE2_WP" : "AE1_WP"), arch);
+    else if (arch == NVQA_ARCH_AE2_WP)
         set_error("%s: not available on a weak-paired auto-encoder context (NVQA_ARCH_AE2_WP: nvqa_ae_wp_step / nvqa_ae_wp_evaluate)", fn);
-        return -1;
-    }
-    if (c->d.arch == NVQA_ARCH_AE1_WP) {
+    else
         set_error("%s: not available on an arch1 weak-paired auto-encoder context (NVQA_ARCH_AE1_WP: nvqa_ae1_wp_step / nvqa_ae1_wp_evaluate)", fn);
-        return -1;
-    }
-    return 0;
-}
-
-static int ae_check_bridge(nvqa_ctx *c, const char *fn)
-{
-    NVQA_TRY(ae_check(c));
-    if (c->d.arch != NVQA_ARCH_AE1_WP) { set_error("%s: an NVQA_ARCH_AE1_WP context expected (arch %d)", fn, c->d.arch); return -1; }
-    return 0;
-}
-
-static int ae_check_wp(nvqa_ctx *c, const char *fn)
-{
-    NVQA_TRY(ae_check(c));
-    if (c->d.arch != NVQA_ARCH_AE2_WP) { set_error("%s: an NVQA_ARCH_AE2_WP context expected (arch %d)", fn, c->d.arch); return -1; }
-    return 0;
+    return -1;
 }
 
 // The data-parallel step's first exchange.  The ranks' criterion counts differ, and the mean of their means is not the global
@@ -1690,7 +1609,7 @@ static int ae_check_wp(nvqa_ctx *c, const char *fn)
 // another rank's count.  The communication stream is idle (the last step joined it), and nothing may read the old weight any
 // more when k_ae_set_count overwrites it: the host-fed step knows that from ae_upload, which has drained the compute stream;
 // the resident step (edge) drains nothing and makes the communication stream wait for the compute stream's position instead.
-static int ae_dp_count(nvqa_ctx *c, int ncount, bool edge)
+static int ae_dp_count(nvqa_ctx *c, bool edge)
 {
     AeState &a = *c->ae;
     if (edge) {
@@ -1698,7 +1617,7 @@ static int ae_dp_count(nvqa_ctx *c, int ncount, bool edge)
         NVQA_HIP(hipEventRecord(a.step_ev, c->s));
         NVQA_HIP(hipStreamWaitEvent(c->sc, a.step_ev, 0));
     }
-    hipLaunchKernelGGL(k_ae_set_count, dim3(1), dim3(1), 0, c->sc, a.dpw, (float)ncount);
+    hipLaunchKernelGGL(k_ae_set_count, dim3(1), dim3(1), 0, c->sc, a.dpw, (float)a.ncount);
     NVQA_HIP(hipGetLastError());
     NVQA_TRY(ae_comm_count(c, a.dpw));
     hipLaunchKernelGGL(k_ae_rank_weight, dim3(1), dim3(1), 0, c->sc, a.dpw, (float)c->world);
@@ -1708,20 +1627,38 @@ static int ae_dp_count(nvqa_ctx *c, int ncount, bool edge)
     return 0;
 }
 
-static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out,
-                        float *dimages_out, const float *feats = nullptr, const int32_t *enc_tokens = nullptr,
-                        const float *enc_state = nullptr, float *dfeats_out = nullptr, const AeBody *body = nullptr)
+// every refusal that concerns the extractor, before anything is launched (the batch's own are ae_upload's, which run first there)
+static int ae_check_body(nvqa_ctx *c, const AeBody &b, int n)
 {
-    if (!tokens) { set_error("tokens is NULL"); return -1; }
-    const Drop dr = ae_drop(dropout, true);
-    int ncount = 0;
-    NVQA_TRY(ae_upload(c, c->d.B, tokens, images, !c->ae->feats, &ncount, feats, enc_tokens, enc_state, body));
-    if (c->comm) NVQA_TRY(ae_dp_count(c, ncount, false));
-    NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
-    NVQA_TRY(ae_backward(c, dr, dfeats_out != nullptr));
+    if (!b.vgg) { set_error("%s: vgg is NULL", b.fn); return -1; }
+    if (n < 1 || n > c->d.B) { set_error("%s: n = %d outside 1..B (%d)", b.fn, n, c->d.B); return -1; }
+    int dev = 0, F = 0;
+    nvqa_vgg_where(b.vgg, &dev, &F);
+    if (F != c->d.I) { set_error("%s: extractor feature width %d != dims.I %d", b.fn, F, c->d.I); return -1; }
+    if (dev != c->device) { set_error("%s: the extractor lives on device %d, the context on device %d", b.fn, dev, c->device); return -1; }
+    return nvqa_vgg_check_raw(b.vgg, b.fn, b.images, n, b.S, b.xoff, b.yoff, b.dr);
+}
+
+// behind the forward pass of a training step: backward, the data-parallel join, and the route's counter (-1: none)
+static int ae_train_tail(nvqa_ctx *c, const Drop &dr, bool want_df, int route)
+{
+    NVQA_TRY(ae_backward(c, dr, want_df));
     NVQA_TRY(ae_comm_join(c));
     c->have_grads = true;
-    if (!c->ae->feats) c->ae->routes[0] += 1;
+    if (route >= 0) c->ae->routes[route] += 1;
+    return 0;
+}
+
+static int ae_step_impl(nvqa_ctx *c, AeBatch bt, const nvqa_dropout *dropout, float *loss_out, float *dimages_out, float *dfeats_out)
+{
+    bt.n = c->d.B;
+    if (bt.body) NVQA_TRY(ae_check_body(c, *bt.body, bt.n));
+    if (!bt.tokens) { set_error("tokens is NULL"); return -1; }
+    const Drop dr = ae_drop(dropout, true);
+    NVQA_TRY(ae_upload(c, bt, !c->ae->feats));
+    if (c->comm) NVQA_TRY(ae_dp_count(c, false));
+    NVQA_TRY(ae_forward(c, dr, c->d.B, true));
+    NVQA_TRY(ae_train_tail(c, dr, dfeats_out != nullptr, c->ae->feats ? -1 : 0));
     if (dfeats_out) {
         NVQA_HIP(hipMemcpyAsync(dfeats_out, c->ae->dfeat, (size_t)c->d.B * c->d.I * 4, hipMemcpyDeviceToHost, c->s));
         NVQA_HIP(hipStreamSynchronize(c->s));
@@ -1736,26 +1673,16 @@ static int ae_step_impl(nvqa_ctx *c, const float *images, const int32_t *tokens,
 }
 
 // evaluate mode on the batch in place (n valid rows): the teacher-forced loss and, on request, greedy decoding
-static int ae_evaluate_run(nvqa_ctx *c, int32_t n, int ncount, float *loss_out, int32_t *samples_out)
+static int ae_evaluate_run(nvqa_ctx *c, int32_t n, float *loss_out, int32_t *samples_out)
 {
     AeState &a = *c->ae;
-    const Drop dr = ae_drop(nullptr, false);
-    NVQA_TRY(ae_forward(c, dr, n, ncount, false));
+    NVQA_TRY(ae_forward(c, ae_drop(nullptr, false), n, false));
     if (samples_out) {
         // sample(): the encoder state is the one just computed (slot te); the decoder is fed START, then its own argmax
-        const nvqa_dims &d = c->d;
-        const int B = d.B, L = d.L, TE = a.te;
         for (int s = 0; s < a.D; ++s) {
-            const int q = TE + s;
-            NVQA_TRY(ae_embed(c, q, q + 1, s == 0 ? nullptr : a.cur, dr));
-            for (int l = 0; l < L; ++l) {
-                if (l > 0) NVQA_TRY(ae_layer_input(c, l, q, q + 1, dr));
-                NVQA_TRY(ae_i2h(c, l, q, q + 1, true));
-                NVQA_TRY(ae_fwd_step(c, l, q, dr));
-            }
-            NVQA_TRY(ae_project(c, s, s + 1, dr));
-            hipLaunchKernelGGL(k_ae_argmax, dim3(B), dim3(256), 0, c->s, a.logits + (size_t)s * B * a.ldl, a.ldl, d.V + 1, a.D, s,
-                               a.cur, a.samples);
+            NVQA_TRY(ae_decode_step(c, s, a.cur, false));
+            hipLaunchKernelGGL(k_ae_argmax, dim3(c->d.B), dim3(256), 0, c->s, a.logits + (size_t)s * c->d.B * a.ldl, a.ldl, c->d.V + 1,
+                               a.D, s, a.cur, a.samples);
             NVQA_HIP(hipGetLastError());
         }
         NVQA_HIP(hipMemcpyAsync(samples_out, a.samples, (size_t)n * a.D * 4, hipMemcpyDeviceToHost, c->s));
@@ -1765,14 +1692,13 @@ static int ae_evaluate_run(nvqa_ctx *c, int32_t n, int ncount, float *loss_out, 
     return 0;
 }
 
-static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, float *loss_out, int32_t *samples_out,
-                            const float *feats = nullptr, const int32_t *enc_tokens = nullptr, const AeBody *body = nullptr)
+static int ae_evaluate_impl(nvqa_ctx *c, const AeBatch &bt, float *loss_out, int32_t *samples_out)
 {
-    if (!tokens) { set_error("tokens is NULL"); return -1; }
-    if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
-    int ncount = 0;
-    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount, feats, enc_tokens, nullptr, body));
-    return ae_evaluate_run(c, n, ncount, loss_out, samples_out);
+    if (bt.body) NVQA_TRY(ae_check_body(c, *bt.body, bt.n));
+    if (!bt.tokens) { set_error("tokens is NULL"); return -1; }
+    if (bt.n < 1 || bt.n > c->d.B) { set_error("n = %d outside 1..B (%d)", bt.n, c->d.B); return -1; }
+    NVQA_TRY(ae_upload(c, bt, false));
+    return ae_evaluate_run(c, bt.n, loss_out, samples_out);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1780,7 +1706,7 @@ static int ae_evaluate_impl(nvqa_ctx *c, int32_t n, const float *images, const i
 // ------------------------------------------------------------------------------------------------------------------
 // the launch plan of a batch of corpus rows from the host tables: tmax, te, the criterion's n.  Nothing is launched: every
 // error of a resident step is raised here, before its first kernel and (data parallel) before its first collective.
-static int ae_rows_plan(nvqa_ctx *c, const char *fn, int n, const int64_t *rows, int *ncount)
+static int ae_rows_plan(nvqa_ctx *c, const char *fn, int n, const int64_t *rows)
 {
     AeState &a = *c->ae;
     if (!rows) { set_error("%s: rows is NULL", fn); return -1; }
@@ -1798,10 +1724,9 @@ static int ae_rows_plan(nvqa_ctx *c, const char *fn, int n, const int64_t *rows,
     }
     if (tmax == 0) { set_error("ae: the batch holds no token (every row is null)"); return -1; }
     a.tmax = tmax;
-    a.te = a.ae2 ? tmax + 2 : tmax;
-    a.skip = false;
-    a.img_live = false; // AE2: zero image rows, as the text script feeds
-    *ncount = cnt;
+    a.te = encoder_steps(a.flags, tmax, 0, false);
+    a.skip = a.img_live = false; // (AE2: zero image rows, as the text script feeds)
+    a.ncount = cnt;
     return 0;
 }
 
@@ -1826,14 +1751,14 @@ static int ae_rows_launch(nvqa_ctx *c, int n, const int64_t *rows, bool index)
     const int TE = a.te, Q = TE + a.tmax + 1, q_lo = a.ae2 ? 1 : 0, r_lo = q_lo * B, np = Q * B - r_lo;
     ProfScope ps(c, PF_AE_EMB_BWD, 0, (double)Q * (V + 2) * 16);
     NVQA_HIP(hipMemsetAsync(a.lk_hist, 0, (size_t)Q * (V + 2) * 4, c->s)); // every bin this step's kernels read, whatever the last step's Q was
-    hipLaunchKernelGGL(k_ae_lk_hist, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->s, (const int32_t *)a.tok, B, D, V, TE,
-                       a.ae2 ? 1 : 0, r_lo, np, a.lk_hist);
+    hipLaunchKernelGGL(k_ae_lk_hist, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->s, ae_chain(c),
+                       (const int32_t *)a.tok, r_lo, np, a.lk_hist);
     hipLaunchKernelGGL(k_ae_lk_prefix, dim3((unsigned)((V + 1 + 255) / 256)), dim3(256), 0, c->s, (const int32_t *)a.lk_hist, V, q_lo, Q,
                        a.lk_base, a.lk_tot);
     hipLaunchKernelGGL(k_ae_lk_scan, dim3(1), dim3(NVQA_AE_SCAN_NT), 0, c->s, V, a.lk_tot, a.lk_chb, a.lk_tok, a.lk_tc, a.lk_start,
                        a.lk_cnt);
-    hipLaunchKernelGGL(k_ae_lk_rank, dim3((unsigned)(Q - q_lo), (unsigned)((B + 255) / 256)), dim3(256), 0, c->s, (const int32_t *)a.tok,
-                       B, D, V, TE, a.ae2 ? 1 : 0, q_lo, (const int32_t *)a.lk_base, (const int32_t *)a.lk_tot, (const int32_t *)a.lk_chb,
+    hipLaunchKernelGGL(k_ae_lk_rank, dim3((unsigned)(Q - q_lo), (unsigned)((B + 255) / 256)), dim3(256), 0, c->s, ae_chain(c),
+                       (const int32_t *)a.tok, q_lo, (const int32_t *)a.lk_base, (const int32_t *)a.lk_tot, (const int32_t *)a.lk_chb,
                        a.lk_start, a.lk_pos);
     NVQA_HIP(hipGetLastError());
     a.lk_dev = true;
@@ -1910,27 +1835,16 @@ static int ae_sample_alloc(nvqa_ctx *c, bool beam)
         else hipLaunchKernelGGL(KERNEL<NVQA_AE_SEL_MAXV4>, grid, dim3(NVQA_AE_SEL_NT), 0, c->s, __VA_ARGS__);                 \
     } while (0)
 
-// the batch in place (n rows; tmax / te set): the encoder exactly as ae_forward runs it -- the same launches on the same row
-// counts, so the state the decoder starts from has nvqa_ae_evaluate's bits -- then D decoder steps fed START and their own picks.
-// Nothing synchronises inside the loop; one copy per output at the end.
+// the batch in place (n rows; tmax / te set): the encoder (ae_run_encoder: the state the decoder starts from has nvqa_ae_evaluate's
+// bits), then D decoder steps fed START and their own picks.  Nothing synchronises inside the loop; one copy per output at the end.
 static int ae_sample_run(nvqa_ctx *c, int32_t n, const AeSample &o, int32_t *seq_out, float *logprobs_out)
 {
     AeState &a = *c->ae;
     const nvqa_dims &d = c->d;
     const int B = d.B, R = d.R, L = d.L, D = a.D, TE = a.te, Vp1 = d.V + 1, K = o.K, nK = n * K;
     const bool beam = o.mode == 2;
-    const Drop dr = ae_drop(nullptr, false);
-    if (a.p16) { // this call's bf16 images of W_proj (ae_forward)
-        hipLaunchKernelGGL(k_ae_wproj_images, dim3((a.ld16 + 63) / 64, (R + 63) / 64), dim3(256), 0, c->s, c->P + c->lo.w_proj, Vp1, R,
-                           a.ld16, a.Wp16, a.WpT16);
-        NVQA_HIP(hipGetLastError());
-    }
-    NVQA_TRY(ae_embed(c, 0, TE, nullptr, dr));
-    for (int l = 0; l < L; ++l) {
-        if (l > 0) NVQA_TRY(ae_layer_input(c, l, 0, TE, dr));
-        NVQA_TRY(ae_i2h(c, l, 0, TE, false));
-        for (int q = 0; q < TE; ++q) NVQA_TRY(ae_fwd_step(c, l, q, dr));
-    }
+    NVQA_TRY(ae_wproj_images(c));
+    NVQA_TRY(ae_run_encoder(c, ae_drop(nullptr, false)));
     const dim3 ggrid((unsigned)std::min<size_t>(((size_t)nK * (R / 4) + 255) / 256, 1024));
     if (beam) { // sentence i's final encoder state (slot te, row i) to its K decoder rows
         for (int l = 0; l < L; ++l)
@@ -1941,13 +1855,7 @@ static int ae_sample_run(nvqa_ctx *c, int32_t n, const AeSample &o, int32_t *seq
     for (int s = 0; s < D; ++s) {
         const int q = TE + s;
         const float *lg = a.logits + (size_t)s * B * a.ldl;
-        NVQA_TRY(ae_embed(c, q, q + 1, s == 0 ? nullptr : a.cur, dr));
-        for (int l = 0; l < L; ++l) {
-            if (l > 0) NVQA_TRY(ae_layer_input(c, l, q, q + 1, dr));
-            NVQA_TRY(ae_i2h(c, l, q, q + 1, true));
-            NVQA_TRY(ae_fwd_step(c, l, q, dr, beam ? a.bm_h[l] : nullptr, beam ? a.bm_c[l] : nullptr));
-        }
-        NVQA_TRY(ae_project(c, s, s + 1, dr));
+        NVQA_TRY(ae_decode_step(c, s, a.cur, beam));
         if (!beam) {
             AE_SEL_DISPATCH(k_ae_select, dim3(n), lg, a.ldl, Vp1, D, s, o.mode, o.T, o.seed, o.step, a.cur, a.samples, a.slp);
             NVQA_HIP(hipGetLastError());
@@ -1984,8 +1892,7 @@ extern "C" int nvqa_ae_sample(nvqa_ctx *c, int32_t n, const float *images, const
     NVQA_TRY(ae_sample_check(c, "nvqa_ae_sample", n, opts, images != nullptr, seq_out, &o));
     if (!tokens) { set_error("nvqa_ae_sample: tokens is NULL"); return -1; }
     NVQA_TRY(ae_sample_alloc(c, o.mode == 2));
-    int ncount = 0;
-    NVQA_TRY(ae_upload(c, n, tokens, images, false, &ncount));
+    NVQA_TRY(ae_upload(c, AeBatch{.n = n, .tokens = tokens, .images = images}, false));
     return ae_sample_run(c, n, o, seq_out, logprobs_out);
 }
 
@@ -1994,8 +1901,7 @@ extern "C" int nvqa_ae_sample_rows(nvqa_ctx *c, int32_t n, const int64_t *rows, 
 {
     AeSample o;
     NVQA_TRY(ae_sample_check(c, "nvqa_ae_sample_rows", n, opts, false, seq_out, &o));
-    int ncount = 0;
-    NVQA_TRY(ae_rows_plan(c, "nvqa_ae_sample_rows", n, rows, &ncount));
+    NVQA_TRY(ae_rows_plan(c, "nvqa_ae_sample_rows", n, rows));
     NVQA_TRY(ae_sample_alloc(c, o.mode == 2));
     NVQA_TRY(ae_rows_launch(c, n, rows, false));
     return ae_sample_run(c, n, o, seq_out, logprobs_out);
@@ -2003,25 +1909,22 @@ extern "C" int nvqa_ae_sample_rows(nvqa_ctx *c, int32_t n, const int64_t *rows, 
 
 extern "C" int nvqa_ae_corpus_load(nvqa_ctx *c, int64_t n_rows, const int32_t *tokens)
 {
-    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_corpus_load"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_corpus_load", AE_TEXT));
     if (!tokens) { set_error("nvqa_ae_corpus_load: tokens is NULL"); return -1; }
     AeState &a = *c->ae;
     const int D = a.D, V = c->d.V;
     if (n_rows < 1 || n_rows > INT32_MAX) { set_error("nvqa_ae_corpus_load: n_rows = %lld outside 1..2^31-1", (long long)n_rows); return -1; }
     if (D >= 65535) { set_error("nvqa_ae_corpus_load: seq_length %d does not fit the per-row host tables", D); return -1; }
+    int tmax = 0;
+    TokenFault bad;
+    if (!stage_tokens(tokens, n_rows, n_rows, D, V, nullptr, &tmax, &bad)) {
+        set_error("nvqa_ae_corpus_load: token %d at (row %lld, column %d) outside 0..%d", bad.value, (long long)bad.row, bad.col, V);
+        return -1;
+    }
     std::vector<uint16_t> last((size_t)n_rows), cnt((size_t)n_rows);
     for (int64_t r = 0; r < n_rows; ++r) {
-        int lastc = 0, nn = 0;
-        for (int t = 0; t < D; ++t) {
-            const int v = tokens[(size_t)r * D + t];
-            if (v < 0 || v > V) {
-                set_error("nvqa_ae_corpus_load: token %d at (row %lld, column %d) outside 0..%d", v, (long long)r, t, V);
-                return -1;
-            }
-            if (v) { lastc = t + 1; ++nn; }
-        }
-        last[(size_t)r] = (uint16_t)lastc;
-        cnt[(size_t)r] = (uint16_t)(nn + 1); // LanguageModelCriterion's n (ae_upload's loop): every token and the first null, which position D always is
+        last[(size_t)r] = (uint16_t)row_last(tokens + (size_t)r * D, D);
+        cnt[(size_t)r] = (uint16_t)criterion_count(tokens + (size_t)r * D, D);
     }
     if (!a.lk_cnt) { // the index build's scratch, on first use
         const size_t W = (size_t)V + 2;
@@ -2055,17 +1958,13 @@ extern "C" int nvqa_ae_corpus_load(nvqa_ctx *c, int64_t n_rows, const int32_t *t
 
 extern "C" int nvqa_ae_step_rows(nvqa_ctx *c, const int64_t *rows, const nvqa_dropout *dropout, float *loss_out)
 {
-    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_step_rows"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_step_rows", AE_TEXT));
     const Drop dr = ae_drop(dropout, true);
-    int ncount = 0;
-    NVQA_TRY(ae_rows_plan(c, "nvqa_ae_step_rows", c->d.B, rows, &ncount));
-    if (c->comm) NVQA_TRY(ae_dp_count(c, ncount, true));
+    NVQA_TRY(ae_rows_plan(c, "nvqa_ae_step_rows", c->d.B, rows));
+    if (c->comm) NVQA_TRY(ae_dp_count(c, true));
     NVQA_TRY(ae_rows_launch(c, c->d.B, rows, true));
-    NVQA_TRY(ae_forward(c, dr, c->d.B, ncount, true));
-    NVQA_TRY(ae_backward(c, dr));
-    NVQA_TRY(ae_comm_join(c));
-    c->have_grads = true;
-    c->ae->routes[1] += 1;
+    NVQA_TRY(ae_forward(c, dr, c->d.B, true));
+    NVQA_TRY(ae_train_tail(c, dr, false, 1));
     if (loss_out) {
         NVQA_HIP(hipStreamSynchronize(c->s));
         *loss_out = ae_last_loss(c);
@@ -2075,12 +1974,11 @@ extern "C" int nvqa_ae_step_rows(nvqa_ctx *c, const int64_t *rows, const nvqa_dr
 
 extern "C" int nvqa_ae_evaluate_rows(nvqa_ctx *c, int32_t n, const int64_t *rows, float *loss_out, int32_t *samples_out)
 {
-    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_evaluate_rows"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_evaluate_rows", AE_TEXT));
     if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
-    int ncount = 0;
-    NVQA_TRY(ae_rows_plan(c, "nvqa_ae_evaluate_rows", n, rows, &ncount));
+    NVQA_TRY(ae_rows_plan(c, "nvqa_ae_evaluate_rows", n, rows));
     NVQA_TRY(ae_rows_launch(c, n, rows, false));
-    return ae_evaluate_run(c, n, ncount, loss_out, samples_out);
+    return ae_evaluate_run(c, n, loss_out, samples_out);
 }
 
 extern "C" int nvqa_ae_step_routes(const nvqa_ctx *c, int64_t out[2])
@@ -2135,149 +2033,127 @@ extern "C" int nvqa_ae_set_precision(nvqa_ctx *c, int bf16)
 // AE2: images = NULL (the text script's zero image rows)
 extern "C" int nvqa_ae_step(nvqa_ctx *c, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out)
 {
-    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_step"));
-    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr);
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_step", AE_TEXT));
+    return ae_step_impl(c, AeBatch{.tokens = tokens}, dropout, loss_out, nullptr, nullptr);
 }
 
 extern "C" int nvqa_ae_evaluate(nvqa_ctx *c, int32_t n, const int32_t *tokens, float *loss_out, int32_t *samples_out)
 {
-    NVQA_TRY(ae_check_not_wp(c, "nvqa_ae_evaluate"));
-    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out);
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_evaluate", AE_TEXT));
+    return ae_evaluate_impl(c, AeBatch{.n = n, .tokens = tokens}, loss_out, samples_out);
 }
 
 extern "C" int nvqa_ae_step_images(nvqa_ctx *c, const float *images, const int32_t *tokens, const nvqa_dropout *dropout,
                                    float *loss_out, float *dimages_out)
 {
-    NVQA_TRY(ae_check_images(c, "nvqa_ae_step_images"));
-    return ae_step_impl(c, images, tokens, dropout, loss_out, dimages_out);
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_step_images", AE_ARCH(AE2)));
+    return ae_step_impl(c, AeBatch{.tokens = tokens, .images = images}, dropout, loss_out, dimages_out, nullptr);
 }
 
 extern "C" int nvqa_ae_evaluate_images(nvqa_ctx *c, int32_t n, const float *images, const int32_t *tokens, float *loss_out,
                                        int32_t *samples_out)
 {
-    NVQA_TRY(ae_check_images(c, "nvqa_ae_evaluate_images"));
-    return ae_evaluate_impl(c, n, images, tokens, loss_out, samples_out);
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_evaluate_images", AE_ARCH(AE2)));
+    return ae_evaluate_impl(c, AeBatch{.n = n, .tokens = tokens, .images = images}, loss_out, samples_out);
 }
 
 extern "C" int nvqa_ae_wp_step(nvqa_ctx *c, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
                                const nvqa_dropout *dropout, float *loss_out)
 {
-    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_step"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_step", AE_ARCH(AE2_WP)));
     if (!feats) { set_error("nvqa_ae_wp_step: feats is NULL"); return -1; }
-    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr, feats, enc_tokens);
+    return ae_step_impl(c, AeBatch{.tokens = tokens, .feats = feats, .enc_tokens = enc_tokens}, dropout, loss_out, nullptr, nullptr);
 }
 
 extern "C" int nvqa_ae_wp_evaluate(nvqa_ctx *c, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
                                    float *loss_out, int32_t *samples_out)
 {
-    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_evaluate"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_evaluate", AE_ARCH(AE2_WP)));
     if (!feats) { set_error("nvqa_ae_wp_evaluate: feats is NULL"); return -1; }
-    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, feats, enc_tokens);
+    return ae_evaluate_impl(c, AeBatch{.n = n, .tokens = tokens, .feats = feats, .enc_tokens = enc_tokens}, loss_out, samples_out);
 }
 
 extern "C" int nvqa_ae1_wp_step(nvqa_ctx *c, const float *feats, const int32_t *enc_tokens, const float *enc_state,
                                 const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out)
 {
-    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_step"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae1_wp_step", AE_ARCH(AE1_WP)));
     if (!feats) { set_error("nvqa_ae1_wp_step: feats is NULL"); return -1; }
     if ((enc_tokens != nullptr) == (enc_state != nullptr)) {
         set_error("nvqa_ae1_wp_step: exactly one of enc_tokens and enc_state must be given");
         return -1;
     }
-    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr, feats, enc_tokens, enc_state, dfeats_out);
+    return ae_step_impl(c, AeBatch{.tokens = tokens, .feats = feats, .enc_tokens = enc_tokens, .enc_state = enc_state}, dropout, loss_out,
+                        nullptr, dfeats_out);
 }
 
 extern "C" int nvqa_ae1_wp_evaluate(nvqa_ctx *c, int32_t n, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
                                     float *loss_out, int32_t *samples_out)
 {
-    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_evaluate"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae1_wp_evaluate", AE_ARCH(AE1_WP)));
     if (!feats || !enc_tokens) { set_error("nvqa_ae1_wp_evaluate: feats or enc_tokens is NULL"); return -1; }
-    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, feats, enc_tokens);
+    return ae_evaluate_impl(c, AeBatch{.n = n, .tokens = tokens, .feats = feats, .enc_tokens = enc_tokens}, loss_out, samples_out);
 }
 
 // ---- the weak-paired steps with the VGG-16 body in the loop ----
-// every refusal that concerns the extractor, before anything is launched (the batch's own are ae_upload's, which run first there)
-static int ae_check_body(nvqa_ctx *c, const AeBody &b, int n)
-{
-    if (!b.vgg) { set_error("%s: vgg is NULL", b.fn); return -1; }
-    if (n < 1 || n > c->d.B) { set_error("%s: n = %d outside 1..B (%d)", b.fn, n, c->d.B); return -1; }
-    int dev = 0, F = 0;
-    nvqa_vgg_where(b.vgg, &dev, &F);
-    if (F != c->d.I) { set_error("%s: extractor feature width %d != dims.I %d", b.fn, F, c->d.I); return -1; }
-    if (dev != c->device) { set_error("%s: the extractor lives on device %d, the context on device %d", b.fn, dev, c->device); return -1; }
-    return nvqa_vgg_check_raw(b.vgg, b.fn, b.images, n, b.S, b.xoff, b.yoff, b.dr);
-}
-
 extern "C" int nvqa_ae_wp_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
                                       const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
                                       const nvqa_dropout *dropout, float *loss_out)
 {
-    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_step_images"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_step_images", AE_ARCH(AE2_WP)));
     const AeBody body{vgg, "nvqa_ae_wp_step_images", images_u8, S, xoff, yoff, body_dropout};
-    NVQA_TRY(ae_check_body(c, body, c->d.B));
-    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr, nullptr, enc_tokens, nullptr, nullptr, &body);
+    return ae_step_impl(c, AeBatch{.tokens = tokens, .enc_tokens = enc_tokens, .body = &body}, dropout, loss_out, nullptr, nullptr);
 }
 
 extern "C" int nvqa_ae_wp_evaluate_images(nvqa_ctx *c, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
                                           const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
                                           float *loss_out, int32_t *samples_out)
 {
-    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_evaluate_images"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_evaluate_images", AE_ARCH(AE2_WP)));
     const AeBody body{vgg, "nvqa_ae_wp_evaluate_images", images_u8, S, xoff, yoff, body_dropout};
-    NVQA_TRY(ae_check_body(c, body, n));
-    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, nullptr, enc_tokens, &body);
+    return ae_evaluate_impl(c, AeBatch{.n = n, .tokens = tokens, .enc_tokens = enc_tokens, .body = &body}, loss_out, samples_out);
 }
 
 extern "C" int nvqa_ae1_wp_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
                                        const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const float *enc_state,
                                        const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out)
 {
-    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_step_images"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae1_wp_step_images", AE_ARCH(AE1_WP)));
     if ((enc_tokens != nullptr) == (enc_state != nullptr)) {
         set_error("nvqa_ae1_wp_step_images: exactly one of enc_tokens and enc_state must be given");
         return -1;
     }
     const AeBody body{vgg, "nvqa_ae1_wp_step_images", images_u8, S, xoff, yoff, body_dropout};
-    NVQA_TRY(ae_check_body(c, body, c->d.B));
-    return ae_step_impl(c, nullptr, tokens, dropout, loss_out, nullptr, nullptr, enc_tokens, enc_state, dfeats_out, &body);
+    return ae_step_impl(c, AeBatch{.tokens = tokens, .enc_tokens = enc_tokens, .enc_state = enc_state, .body = &body}, dropout, loss_out,
+                        nullptr, dfeats_out);
 }
 
 extern "C" int nvqa_ae1_wp_evaluate_images(nvqa_ctx *c, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
                                            const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
                                            float *loss_out, int32_t *samples_out)
 {
-    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_evaluate_images"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae1_wp_evaluate_images", AE_ARCH(AE1_WP)));
     if (!enc_tokens) { set_error("nvqa_ae1_wp_evaluate_images: enc_tokens is NULL"); return -1; }
     const AeBody body{vgg, "nvqa_ae1_wp_evaluate_images", images_u8, S, xoff, yoff, body_dropout};
-    NVQA_TRY(ae_check_body(c, body, n));
-    return ae_evaluate_impl(c, n, nullptr, tokens, loss_out, samples_out, nullptr, enc_tokens, &body);
+    return ae_evaluate_impl(c, AeBatch{.n = n, .tokens = tokens, .enc_tokens = enc_tokens, .body = &body}, loss_out, samples_out);
 }
 
 // the evaluate-mode encoder alone: [c_T | h_T] of the state slot te, joined by the bridge's prep kernel
 extern "C" int nvqa_ae1_wp_encode(nvqa_ctx *c, int32_t n, const int32_t *enc_tokens, float *state_out)
 {
-    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_encode"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae1_wp_encode", AE_ARCH(AE1_WP)));
     if (!enc_tokens || !state_out) { set_error("nvqa_ae1_wp_encode: NULL argument"); return -1; }
     if (n < 1 || n > c->d.B) { set_error("n = %d outside 1..B (%d)", n, c->d.B); return -1; }
     AeState &a = *c->ae;
     const int B = c->d.B, D = a.D, V = c->d.V, R = c->d.R, I = c->d.I;
     NVQA_HIP(hipStreamSynchronize(c->s));
     int te = 0;
-    for (int b = 0; b < B; ++b)
-        for (int t = 0; t < D; ++t) {
-            const int v = b < n ? enc_tokens[(size_t)b * D + t] : 0;
-            if (v < 0 || v > V) { set_error("ae: enc_tokens %d at (%d, %d) outside 0..%d", v, b, t, V); return -1; }
-            a.h_etok[(size_t)b * D + t] = v;
-            if (v) te = std::max(te, t + 1);
-        }
+    NVQA_TRY(ae_stage("enc_tokens", enc_tokens, n, B, D, V, a.h_etok, &te));
     if (te == 0) { set_error("ae: enc_tokens holds no token (every row is null)"); return -1; }
-    a.te = te;
+    a.te = encoder_steps(a.flags, 0, te, false);
     a.skip = false;
     NVQA_HIP(hipMemcpyAsync(a.etok, a.h_etok, (size_t)B * D * 4, hipMemcpyHostToDevice, c->s));
     const Drop dr = ae_drop(nullptr, false);
-    NVQA_TRY(ae_embed(c, 0, te, nullptr, dr));
-    NVQA_TRY(ae_i2h(c, 0, 0, te, false));
-    for (int q = 0; q < te; ++q) NVQA_TRY(ae_fwd_step(c, 0, q, dr));
+    NVQA_TRY(ae_run_encoder(c, dr));
     const size_t sl = (size_t)te * B * R;
     hipLaunchKernelGGL(k_ae1wp_bridge_prep, dim3((unsigned)std::min<size_t>(((size_t)B * (2 * R + I) + 255) / 256, 2048)), dim3(256), 0,
                        c->s, (const float *)(a.Cs[0] + sl), (const float *)(a.Hs[0] + sl), a.jbuf, (const float *)a.feat, B, R, I, dr,
@@ -2290,7 +2166,7 @@ extern "C" int nvqa_ae1_wp_encode(nvqa_ctx *c, int32_t n, const int32_t *enc_tok
 
 extern "C" int nvqa_ae1_wp_set_lookup(nvqa_ctx *c, const float *w)
 {
-    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_set_lookup"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae1_wp_set_lookup", AE_ARCH(AE1_WP)));
     if (!w) { set_error("NULL argument"); return -1; }
     NVQA_HIP(hipStreamSynchronize(c->s));
     NVQA_HIP(hipMemcpy(c->P + c->lo.w_lk, w, ((size_t)c->d.V + 1) * c->d.E * 4, hipMemcpyHostToDevice));
@@ -2299,7 +2175,7 @@ extern "C" int nvqa_ae1_wp_set_lookup(nvqa_ctx *c, const float *w)
 
 extern "C" int nvqa_ae1_wp_get_lookup(nvqa_ctx *c, float *w_out)
 {
-    NVQA_TRY(ae_check_bridge(c, "nvqa_ae1_wp_get_lookup"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae1_wp_get_lookup", AE_ARCH(AE1_WP)));
     if (!w_out) { set_error("NULL argument"); return -1; }
     NVQA_HIP(hipStreamSynchronize(c->s));
     NVQA_HIP(hipMemcpy(w_out, c->P + c->lo.w_lk, ((size_t)c->d.V + 1) * c->d.E * 4, hipMemcpyDeviceToHost));
@@ -2308,7 +2184,7 @@ extern "C" int nvqa_ae1_wp_get_lookup(nvqa_ctx *c, float *w_out)
 
 extern "C" int nvqa_ae_wp_set_projection(nvqa_ctx *c, const float *w, const float *b)
 {
-    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_set_projection"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_set_projection", AE_ARCH(AE2_WP)));
     if (!w || !b) { set_error("NULL argument"); return -1; }
     AeState &a = *c->ae;
     const size_t nw = (size_t)c->d.E * c->d.I;
@@ -2330,13 +2206,13 @@ static int ae_wp_copy_out(nvqa_ctx *c, const float *src, float *w_out, float *b_
 
 extern "C" int nvqa_ae_wp_get_projection(nvqa_ctx *c, float *w_out, float *b_out)
 {
-    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_get_projection"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_get_projection", AE_ARCH(AE2_WP)));
     return ae_wp_copy_out(c, c->ae->wp_x, w_out, b_out);
 }
 
 extern "C" int nvqa_ae_wp_get_projection_grads(nvqa_ctx *c, float *w_out, float *b_out)
 {
-    NVQA_TRY(ae_check_wp(c, "nvqa_ae_wp_get_projection_grads"));
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_get_projection_grads", AE_ARCH(AE2_WP)));
     if (!c->have_grads) { set_error("nvqa_ae_wp_get_projection_grads before any nvqa_ae_wp_step"); return -1; }
     return ae_wp_copy_out(c, c->ae->wp_g, w_out, b_out);
 }
@@ -2363,7 +2239,7 @@ static float adam_step_size(float lr, float beta1, float beta2, int64_t t)
 static int ae_wp_projection_rule(nvqa_ctx *c, const char *fn, int rule, float lr, float alpha, float beta, float eps, float wd,
                                  float clamp, float stats_out[2])
 {
-    NVQA_TRY(ae_check_wp(c, fn));
+    NVQA_TRY(ae_check_arch(c, fn, AE_ARCH(AE2_WP)));
     if (rule != NVQA_OPT_SGD && rule != NVQA_OPT_SGDM && rule != NVQA_OPT_ADAM) {
         set_error("%s: rule %d is not one of -cnn_optim's (NVQA_OPT_SGD, NVQA_OPT_SGDM, NVQA_OPT_ADAM)", fn, rule);
         return -1;
@@ -2372,10 +2248,7 @@ static int ae_wp_projection_rule(nvqa_ctx *c, const char *fn, int rule, float lr
     AeState &a = *c->ae;
     const size_t nw = (size_t)c->d.E * c->d.I, n = nw + c->d.E;
     const int NB = 1024;
-    if (rule == NVQA_OPT_SGDM && !a.wp_vel) {
-        NVQA_HIP(hipMalloc((void **)&a.wp_vel, n * 4));
-        NVQA_HIP(hipMemsetAsync(a.wp_vel, 0, n * 4, c->s));
-    }
+    if (rule == NVQA_OPT_SGDM && !a.wp_vel) NVQA_TRY(ae_alloc(&a.dev, (void **)&a.wp_vel, n * 4, c->s)); // (zeroed in stream order)
     RuleArgs r = {lr, alpha, beta, eps, 0.f};
     if (rule == NVQA_OPT_ADAM) r.step = adam_step_size(lr, alpha, beta, ++a.wp_t);
     double *part = stats_out ? a.wp_part : (double *)nullptr;

@@ -1,7 +1,7 @@
 """The preconditions of tests/test_gpu_ae_tiles.py, on the CPU.
 
 Boundary census: a Python restatement of the two host rules of novel-vqa_amd/csrc/ae.hip that decide how a step is cut up --
-wgrad()'s tiles -> Z -> slab budget -> kslice -> Z and colsum()'s row splits S (ae.hip:681-731) -- plus the tile shapes of the
+wgrad()'s tiles -> Z -> slab budget -> kslice -> Z and colsum()'s row splits S -- plus the tile shapes of the
 GEMM configurations and the lookup gradient's chunking, evaluated on every case of tests/ae_tile_cases.py.  Each case must
 cross the boundaries it is listed for; shrinking one back inside a tile, a slab or a chunk fails here.
 
@@ -34,7 +34,7 @@ def tiling(n, t):
     return k, n - (k - 1) * t
 
 
-# ---- restatement of ae.hip:681-731 ---------------------------------------------------------------------------------------------
+# ---- restatement of wgrad() and colsum() -----------------------------------------------------------------------------------------
 def slab_floats(case):
     """ae_create: a.slab_floats"""
     E, R = case.dims[3], case.dims[4]
