@@ -206,6 +206,10 @@ int nvqa_persistent_state(const nvqa_ctx *ctx, int out[2]);
  * (NVQA_WGRAD_SPLIT=0, or a shape the six-term kernels do not take), out[1] k_wgrad_split (NVQA_WGRAD_KERNEL=1), out[2]
  * k_wgrad_split2 (the default).  The two six-term kernels give the same bits; the counters say which one ran. */
 int nvqa_wgrad_routes(const nvqa_ctx *ctx, int64_t out[3]);
+/* How many f32-mode d(layer-0 input) products this context has launched so far, by route: out[0] the f32 MFMA GEMM
+ * (NVQA_DX0_KERNEL=1, or a shape k_dx0_split does not take), out[1] k_dx0_split (six bf16 MFMA terms per product, the
+ * default).  NVQA_DX0_KERNEL is independent of NVQA_WGRAD_SPLIT. */
+int nvqa_dx0_routes(const nvqa_ctx *ctx, int64_t out[2]);
 /* Per-segment gradient scale applied before the clamp: {lr_scale, lr_scale, 1} reproduces
  * -lr_scale of 003_train_ae_based_wp.lua:30,344. */
 int nvqa_set_grad_scales(nvqa_ctx *ctx, const float scales[3]);

@@ -45,6 +45,9 @@ struct TransposeJob {
     const float *W = nullptr; // nullptr: no job
     unsigned short *out = nullptr;
     int rows = 0, cols = 0, first_block = 0, nblocks = 0;
+    // f32 mode (dx0_split.h): `out` takes hi = bf16(w) and these two mid = bf16(w - hi) and lo = bf16(w - hi - mid), all three in
+    // blocks of 32 rows of W, [rows / 32][cols][32] (rows % 32 == 0), instead of [cols][rows]; nullptr: the one [cols][rows] image
+    unsigned short *out_mid = nullptr, *out_lo = nullptr;
 };
 __device__ __forceinline__ void transpose_to_bf16_block(const TransposeJob &j, int blk, float (*t)[33])
 {
@@ -57,7 +60,18 @@ __device__ __forceinline__ void transpose_to_bf16_block(const TransposeJob &j, i
     __syncthreads();
     for (int i = ty; i < 32; i += 8) {
         const int cc = c0 + i, r = r0 + tx;
-        if (cc < j.cols && r < j.rows) reinterpret_cast<__bf16 *>(j.out)[(size_t)cc * j.rows + r] = (__bf16)t[tx][i];
+        if (cc < j.cols && r < j.rows) {
+            const size_t o = j.out_mid ? ((size_t)(r0 / 32) * j.cols + cc) * 32 + tx : (size_t)cc * j.rows + r;
+            const float w = t[tx][i];
+            const __bf16 hi = (__bf16)w;
+            reinterpret_cast<__bf16 *>(j.out)[o] = hi;
+            if (j.out_mid) {
+                const float r1 = w - (float)hi;
+                const __bf16 mid = (__bf16)r1;
+                reinterpret_cast<__bf16 *>(j.out_mid)[o] = mid;
+                reinterpret_cast<__bf16 *>(j.out_lo)[o] = (__bf16)(r1 - (float)mid);
+            }
+        }
     }
 }
 

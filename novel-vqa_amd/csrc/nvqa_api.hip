@@ -21,6 +21,7 @@
 #include "wgrad_bf16.h"
 #include "wgrad_split.h"
 #include "wgrad_split2.h"
+#include "dx0_split.h"
 #include "nvqa_ctx.h"
 #include "persist_host.h"
 
@@ -329,6 +330,7 @@ static int create_impl(nvqa_ctx *c)
     NVQA_TRY(dalloc(&c->chain_slabs, (size_t)L * 2 * NVQA_BWD_ZMAX * ((B + 63) / 64 * 64) * ((R + 63) / 64 * 64)));
     c->wgrad_split_on = env_on("NVQA_WGRAD_SPLIT"); // 0: the f32 weight gradients as the exact f32 MFMA chain (wgrad_split.h)
     c->wgrad_kernel = env_int("NVQA_WGRAD_KERNEL", 2) == 1 ? 1 : 2; // 1: k_wgrad_split, the 128 x 128 form (same bits as the default, wgrad_split2.h)
+    c->dx0_kernel = env_int("NVQA_DX0_KERNEL", 0) == 1 ? 1 : 0; // 1: d(layer-0 input) of the f32 mode as the f32 MFMA GEMM (default: dx0_split.h); independent of NVQA_WGRAD_SPLIT
     c->fold_i2h = env_on("NVQA_FOLD_I2H"); // 0: layer 0's input projection as a separate time-batched GEMM (A/B runs of the per-level path)
     {   // persistent forward LSTM (lstm_persist.h) where the shape is eligible; NVQA_PERSIST=0: one launch per wavefront level
         c->persist_on = env_on("NVQA_PERSIST");
@@ -567,6 +569,13 @@ extern "C" int nvqa_wgrad_routes(const nvqa_ctx *c, int64_t out[3])
 {
     if (!c || !out) { set_error("NULL argument"); return -1; }
     for (int i = 0; i < 3; ++i) out[i] = c->wgrad_launches[i];
+    return 0;
+}
+
+extern "C" int nvqa_dx0_routes(const nvqa_ctx *c, int64_t out[2])
+{
+    if (!c || !out) { set_error("NULL argument"); return -1; }
+    for (int i = 0; i < 2; ++i) out[i] = c->dx0_launches[i];
     return 0;
 }
 
@@ -1086,6 +1095,32 @@ __global__ void k_transpose_to_bf16(const float *W, int rows, int cols, __bf16 *
     }
 }
 
+// The image(s) of W_i2h[0]^T that lstm_dx0 multiplies by, as a TransposeJob (kernels.h): one bf16 image (bf16 mode) or the
+// hi, mid and lo images of the six-term form (f32 mode, dx0_split.h).  Per step: the weights move with every update.
+static int wi2h0_job_fill(nvqa_ctx *c, bool three, int first_block, TransposeJob *tj)
+{
+    const int R = c->d.R, E = c->d.E;
+    const size_t n = (size_t)E * 4 * R;
+    if (!c->wi2h0_t16) NVQA_HIP(hipMalloc((void **)&c->wi2h0_t16, 3 * n * 2)); // (the precision may change between steps: room for three)
+    *tj = TransposeJob{};
+    tj->W = c->P + c->lo.w_i2h[0]; tj->out = c->wi2h0_t16; tj->rows = 4 * R; tj->cols = E;
+    if (three) { tj->out_mid = c->wi2h0_t16 + n; tj->out_lo = c->wi2h0_t16 + 2 * n; }
+    tj->first_block = first_block; tj->nblocks = ((E + 31) / 32) * ((4 * R + 31) / 32);
+    return 0;
+}
+// the job as a launch of its own (a step that reaches lstm_dx0 without the images)
+__global__ __launch_bounds__(256) void k_transpose_job(TransposeJob tj)
+{
+    __shared__ float tt[32][33];
+    transpose_to_bf16_block(tj, blockIdx.x, tt);
+}
+// f32 mode: does d(layer-0 input) run as k_dx0_split (dx0_split.h)?  NVQA_DX0_KERNEL=1: no.  (Not tied to NVQA_WGRAD_SPLIT: the
+// embedding gradients, which dX0 feeds, are the same bits whichever way the LSTM weight gradients go.)
+static bool dx0_split_route(const nvqa_ctx *c)
+{
+    return !c->bf16 && c->dx0_kernel == 0 && dx0_split_takes(c->TS * c->d.B, c->d.E, 4 * c->d.R, 4 * c->d.R);
+}
+
 // dL/d(layer-0 input) for all steps at once; runs after the LSTM weight gradients so that their
 // all-reduce (data parallel) overlaps it.
 static int lstm_dx0(nvqa_ctx *c, float *dX0)
@@ -1093,13 +1128,31 @@ static int lstm_dx0(nvqa_ctx *c, float *dX0)
     const nvqa_dims &d = c->d;
     const int R = d.R, TB = c->TS * d.B;
     ProfScope ps(c, PF_GEMM_DGRAD, 2.0 * TB * d.E * 4 * R, ((double)TB * (4 * R + d.E) + 4.0 * R * d.E) * 4);
+    // f32 mode: six bf16 MFMA terms per product, dG straight from global memory into the fragment registers (dx0_split.h)
+    if (dx0_split_route(c)) {
+        if (c->wi2h0_img_step != 3) { // (normally made by the embedding launch of this step: wi2h0_image_job)
+            TransposeJob tj;
+            NVQA_TRY(wi2h0_job_fill(c, true, 0, &tj));
+            hipLaunchKernelGGL(k_transpose_job, dim3(tj.nblocks), dim3(256), 0, c->s, tj);
+            NVQA_HIP(hipGetLastError());
+        }
+        c->wi2h0_img_step = 0; // the images are this step's alone
+        Dx0SplitArgs g = {};
+        g.A = c->Gt[0]; g.lda = 4 * R; g.W3 = c->wi2h0_t16; g.out = dX0; g.ldo = d.E;
+        g.M = TB; g.N = d.E; g.K = 4 * R;
+        g.nrows = c->nrows; g.seg_rows = d.B;
+        NVQA_HIP(dx0_split_launch(c->s, g));
+        c->dx0_launches[1] += 1;
+        return 0;
+    }
+    if (!c->bf16) c->dx0_launches[0] += 1;
     // bf16 mode behind the persistent BPTT kernel: dG exists as a bf16 image ([TS*B][4R], K-contiguous); with a transposed
     // bf16 image of W_i2h (made here, per step: the weights move) both operands are K-contiguous bf16 and the product runs
     // in the gfx950 form (BF = 2: bf16 LDS images, v_mfma_f32_16x16x32_bf16) instead of rounding f32 LDS images per MFMA.
     // Same operand values, f32 accumulate, f32 result.  (Without the dG image -- the per-level bf16 route -- the BF = 1 form below.)
     if (c->bf16 && c->img_bwd_valid && (4 * R) % 64 == 0) {
-        if (!c->wi2h0_img_step) { // (normally made by the embedding launch of this step: wi2h0_image_job)
-            if (!c->wi2h0_t16) NVQA_HIP(hipMalloc((void **)&c->wi2h0_t16, (size_t)d.E * 4 * R * 2));
+        if (c->wi2h0_img_step != 1) { // (normally made by the embedding launch of this step: wi2h0_image_job)
+            if (!c->wi2h0_t16) NVQA_HIP(hipMalloc((void **)&c->wi2h0_t16, 3 * (size_t)d.E * 4 * R * 2)); // (room for three: wi2h0_job_fill)
             hipLaunchKernelGGL(k_transpose_to_bf16, dim3((d.E + 31) / 32, (4 * R + 31) / 32), dim3(32, 8), 0, c->s, c->P + c->lo.w_i2h[0], 4 * R, d.E,
                                reinterpret_cast<__bf16 *>(c->wi2h0_t16));
         }
@@ -1210,19 +1263,20 @@ static int x0_image_begin(nvqa_ctx *c, int TB)
     return 0;
 }
 
-// bf16 mode, training step, persistent BPTT ahead: the bf16 image of W_i2h[0]^T that lstm_dx0's gfx950-form product wants is
-// made by extra workgroups of the embedding launch (the weights do not move during a step).
+// Training step: the image(s) of W_i2h[0]^T that lstm_dx0 wants are made by extra workgroups of the embedding launch (the
+// weights do not move during a step).  bf16 mode with the persistent BPTT ahead: the one bf16 image of the gfx950-form
+// product; f32 mode where k_dx0_split runs: its hi, mid and lo images.
 static int wi2h0_image_job(nvqa_ctx *c, bool train, int first_block, TransposeJob *tj)
 {
     *tj = TransposeJob{};
-    c->wi2h0_img_step = false;
+    c->wi2h0_img_step = 0;
     int rb = 0;
-    const int R = c->d.R, E = c->d.E;
-    if (!train || !c->bf16 || (4 * R) % 64 || persist_bwd_rows(c, &rb) == 0) return 0;
-    if (!c->wi2h0_t16) NVQA_HIP(hipMalloc((void **)&c->wi2h0_t16, (size_t)E * 4 * R * 2));
-    tj->W = c->P + c->lo.w_i2h[0]; tj->out = c->wi2h0_t16; tj->rows = 4 * R; tj->cols = E;
-    tj->first_block = first_block; tj->nblocks = ((E + 31) / 32) * ((4 * R + 31) / 32);
-    c->wi2h0_img_step = true;
+    const int R = c->d.R;
+    if (!train) return 0;
+    const bool three = dx0_split_route(c);
+    if (!three && (!c->bf16 || (4 * R) % 64 || persist_bwd_rows(c, &rb) == 0)) return 0;
+    NVQA_TRY(wi2h0_job_fill(c, three, first_block, tj));
+    c->wi2h0_img_step = three ? 3 : 1; // the two layouts share the buffer: lstm_dx0 takes only the one its route reads
     return 0;
 }
 

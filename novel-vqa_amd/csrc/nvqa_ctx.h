@@ -190,6 +190,8 @@ struct nvqa_ctx {
     bool wgrad_split_on = true;   // f32 mode: weight gradients as six bf16 MFMA terms per product (wgrad_split.h); NVQA_WGRAD_SPLIT=0: the f32 MFMA chain
     int wgrad_kernel = 2;         // which six-term kernel: 2 = k_wgrad_split2 (wgrad_split2.h), NVQA_WGRAD_KERNEL=1: k_wgrad_split (same bits)
     long long wgrad_launches[3] = {0, 0, 0}; // weight-gradient products so far by route: f32 chain, k_wgrad_split, k_wgrad_split2 (nvqa_wgrad_routes)
+    int dx0_kernel = 0;           // f32 mode, d(layer-0 input): 0 = k_dx0_split (dx0_split.h: six bf16 MFMA terms), NVQA_DX0_KERNEL=1: the f32 MFMA GEMM
+    long long dx0_launches[2] = {0, 0}; // f32-mode d(layer-0 input) products so far by route: f32 MFMA GEMM, k_dx0_split (nvqa_dx0_routes)
     bool fold_i2h = true;         // layer-0 input projection as a first K segment of the level kernel; NVQA_FOLD_I2H=0: separate time-batched GEMM
     bool batch_uniform = false;   // current batch: all lengths equal (known on the host)
     float batch_len_frac = 1.f;   // current batch: filled share of its B x T (row, step) slots (host batches: exact; dataset route: the dataset's mean)
@@ -203,8 +205,10 @@ struct nvqa_ctx {
     unsigned *pb_bias_cnt = nullptr; // [L][32] arrivals per (layer, unit tile): the last row block's workgroup writes the bias gradients
     int pb_bias_rb = 0;           // row blocks of this step's partial sums; > 0: the persistent BPTT launch wrote b_i2h / b_h2h of every
                                   // layer itself (0: lstm_wgrads runs the column-sum kernels)
-    bool wi2h0_img_step = false;         // ... made by this step's embedding launch (else lstm_dx0 makes it)
-    unsigned short *wi2h0_t16 = nullptr; // bf16 image of W_i2h[0]^T ([E][4R]) for the gfx950-form d(input) product, remade every step
+    int wi2h0_img_step = 0;              // ... made by this step's embedding launch (else lstm_dx0 makes it): 0 none, 1 the one [E][4R] image (bf16 mode),
+                                         // 3 the hi, mid and lo images in blocks of 32 k (f32 mode, dx0_split.h)
+    unsigned short *wi2h0_t16 = nullptr; // bf16 image of W_i2h[0]^T ([E][4R]) for the gfx950-form d(input) product, remade every step;
+                                         // f32 mode: its hi, mid and lo images, [3][E][4R] (dx0_split.h); allocated for three either way
     unsigned short *dg_b16 = nullptr;  // bf16 image of dG for the persistent BPTT kernel's bf16 instance (lstm_persist_bwd2.h)
     unsigned short *x0_b16 = nullptr;  // bf16 image of X0 ([TS*B][E]), written by the embedding kernels in bf16 mode (E % 8 == 0)
     bool x0_img_valid = false;         // ... for the current step

@@ -79,6 +79,7 @@ SYMBOLS = {
     "nvqa_param_norms": (ctypes.c_int, [_vp, _f32p]),
     "nvqa_persistent_state": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "nvqa_wgrad_routes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "nvqa_dx0_routes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     "nvqa_set_grad_scales": (ctypes.c_int, [_vp, _f32p]),
     "nvqa_dataset_load": (ctypes.c_int, [_vp, ctypes.c_int64, _i32p, _i32p, _i32p, _i32p,
                                          ctypes.c_int64, _f32p, ctypes.c_int]),
@@ -640,6 +641,12 @@ class Context:
         out = (ctypes.c_int64 * 3)()
         self._check(self.lib.nvqa_wgrad_routes(self._h, out))
         return {"f32_chain": int(out[0]), "split": int(out[1]), "split2": int(out[2])}
+
+    def dx0_routes(self):
+        """f32-mode d(layer-0 input) products launched so far by route: {'f32_gemm', 'split'} (NVQA_DX0_KERNEL)."""
+        out = (ctypes.c_int64 * 2)()
+        self._check(self.lib.nvqa_dx0_routes(self._h, out))
+        return {"f32_gemm": int(out[0]), "split": int(out[1])}
 
     # ---- dataset ------------------------------------------------------------------
     def dataset_load(self, questions, lengths, img_pos, answers, feats, l2_normalize=False):

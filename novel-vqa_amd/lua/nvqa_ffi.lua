@@ -39,6 +39,7 @@ int nvqa_set_ref_quirks(nvqa_ctx *ctx, int flags);
 int nvqa_param_norms(nvqa_ctx *ctx, float out[3]);
 int nvqa_persistent_state(const nvqa_ctx *ctx, int out[2]);
 int nvqa_wgrad_routes(const nvqa_ctx *ctx, int64_t out[3]);
+int nvqa_dx0_routes(const nvqa_ctx *ctx, int64_t out[2]);
 int nvqa_set_grad_scales(nvqa_ctx *ctx, const float scales[3]);
 int nvqa_dataset_load(nvqa_ctx *ctx, int64_t n_q, const int32_t *questions, const int32_t *lengths,
                       const int32_t *img_pos, const int32_t *answers, int64_t n_img,

@@ -23,7 +23,8 @@ GROUPS = [
     # time-batched one is the launch with more than a million threads
     ("gemm_i2h_fwd", lambda n, grid=0: "gemm_f32_kernel" in n and "EpiBias2" in n and grid > (1 << 20)),
     # d(input): the one K-contiguous x N-contiguous product with a plain store and a time-batched grid
-    ("gemm_dgrad", lambda n, grid=0: "gemm_f32_kernel" in n and ", 0, 1, false" in n and "EpiStore" in n and grid > 500000),
+    # (f32 mode by default: k_dx0_split, dx0_split.h)
+    ("gemm_dgrad", lambda n, grid=0: "k_dx0_split" in n or ("gemm_f32_kernel" in n and ", 0, 1, false" in n and "EpiStore" in n and grid > 500000)),
     ("rmsprop", lambda n: "k_rmsprop" in n),
     ("emb_bwd", lambda n: "k_emb_bwd" in n),
     ("emb_fwd", lambda n: "k_emb_fwd" in n),
