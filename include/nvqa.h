@@ -269,6 +269,35 @@ int nvqa_vgg16_preprocess(nvqa_vgg *vgg, const float *rgb, int n, int H, int W, 
 int nvqa_vgg16_fc7_raw(nvqa_vgg *vgg, const uint8_t *images, int n, int S, int xoff, int yoff,
                        const nvqa_dropout *body_dropout, float *feats_out);
 
+/* Fine-tuning the f32 body (protos.cnn:backward and the cnn update of 004_train_arch{1,2}_weakpaired_autoencoder_vgg.lua,
+ * arch2 :307-310, :457-466; arch1 :329, :477-484).
+ * nvqa_vgg16_train_enable(vgg, 1) allocates the training state -- every layer's output of a training forward, two gradient
+ * buffers, the gradients, the tap-flipped weight images of d(input), the split-K workspace; about 60 MB per image of max_batch
+ * at full width and 224 x 224 -- and (vgg, 0) or destroy frees it; an extractor that never trains pays nothing.  Refused on a
+ * bf16 extractor, and nvqa_vgg16_set_precision(vgg, 1) is refused while it is enabled.
+ * nvqa_vgg16_train_forward_raw: nvqa_vgg16_fc7_raw's arguments, launches and bits, every layer kept; feats_out may be NULL.
+ * nvqa_vgg16_train_activation: the saved output of layer which = 0..12 (convolution, post-ReLU, NCHW, true channels), 13 (fc6),
+ * 14 (fc7: post-ReLU, post-dropout) of the last training forward.
+ * nvqa_vgg16_backward: dfeats [n x F] on the host = d(loss)/d(features); through_l2norm = 1: dfeats is d/d(f^) of the
+ * row-normalised features and nn.L2Normalize's backward (misc/L2Normalize.lua:22-40, from the saved features; a row of norm zero
+ * gives NaN there as in the forward) runs first.  Bit-reproducible: no atomics, split-K slabs summed in a fixed order.
+ * nvqa_vgg16_get_grads / nvqa_vgg16_get_weights: one flat vector in nvqa_vgg16_set_weights' layout (get_weights is its exact inverse).
+ * nvqa_vgg16_update: rule NVQA_OPT_SGD, NVQA_OPT_SGDM or NVQA_OPT_ADAM in the lrs forms of misc/optim_updates.lua with
+ * cnnFinalLearningScales = scale everywhere (arch2: 0.01, arch1: 1): g += wd scale x (wd != 0), clamp (clamp > 0), the rule with
+ * every step times scale.  stats_out (may be NULL) = {|x|_2, count(|lr g| >= 0.01 |x|)} over the true weights, of x before the
+ * update and g after wd and clamp.
+ * An error before anything is launched: training not enabled, bf16, backward without a training forward or with another n,
+ * n outside 1..max_batch, any other rule. */
+int nvqa_vgg16_train_enable(nvqa_vgg *vgg, int on);
+int nvqa_vgg16_train_forward_raw(nvqa_vgg *vgg, const uint8_t *images, int n, int S, int xoff, int yoff,
+                                 const nvqa_dropout *dropout, float *feats_out);
+int nvqa_vgg16_train_activation(nvqa_vgg *vgg, int which, float *out);
+int nvqa_vgg16_backward(nvqa_vgg *vgg, const float *dfeats, int n, int through_l2norm);
+int nvqa_vgg16_get_grads(nvqa_vgg *vgg, float *flat_out);
+int nvqa_vgg16_get_weights(nvqa_vgg *vgg, float *flat_out);
+int nvqa_vgg16_update(nvqa_vgg *vgg, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
+                      float scale, float stats_out[2]);
+
 /* The extractor run on the fly in front of the training step (BASELINE config "end-to-end"):
  * images [B x 3 x hw x hw] as loadim returns them -> fc7 -> row L2 norm (002_train_baseline.lua:117-121)
  * -> the JdJ body of nvqa_step.  The extractor's feature width must equal dims.I; the features
@@ -454,6 +483,22 @@ int nvqa_ae1_wp_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_
 int nvqa_ae1_wp_evaluate_images(nvqa_ctx *ctx, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
                                 const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
                                 float *loss_out, int32_t *samples_out);
+/* The weak-paired steps with the body fine-tuning.  nvqa_ae_wp_step_dfeats: nvqa_ae_wp_step that also
+ * returns d(loss)/d(f^) = dx0 W_p [B x I] (one more product; loss and gradients keep nvqa_ae_wp_step's bits).  The two
+ * *_finetune steps take a training-enabled extractor and run its training forward, the step of the same name without the
+ * suffix, nn.L2Normalize's backward and the body's backward; d f^ goes from the context's stream to the extractor's on the
+ * device and the extractor's stream waits for it.  The result -- loss, nvqa_get_grads, the projection's gradients,
+ * nvqa_vgg16_get_grads -- is bit-equal to nvqa_vgg16_train_forward_raw, the host-fed step with dfeats_out, then
+ * nvqa_vgg16_backward(vgg, dfeats, B, 1).  Errors before anything is launched: those of the step without the suffix, and an
+ * extractor that is not training-enabled. */
+int nvqa_ae_wp_step_dfeats(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                           const nvqa_dropout *dropout, float *loss_out, float *dfeats_out);
+int nvqa_ae_wp_step_images_finetune(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                    const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                                    const nvqa_dropout *dropout, float *loss_out);
+int nvqa_ae1_wp_step_images_finetune(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                     const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const float *enc_state,
+                                     const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out);
 /* Valid on every context.  One pass over the flat vector: g = clamp(g, -clamp, clamp) (clamp > 0), g += wd * x, then
  * adam() of misc/optim_updates.lua:78-111 (step counter held by the context, reset by nvqa_init_params).
  * stats_out (may be NULL; synchronises) = {||x||_2, count(|lr g| >= 0.01 |x|)} of x before the update, g after clamp + wd

@@ -54,6 +54,10 @@ int nvqa_vgg_check_raw(const nvqa_vgg *v, const char *fn, const uint8_t *images,
 int nvqa_vgg_forward_raw_device(nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff,
                                 const nvqa_dropout *dr, const float **feats_dev, hipStream_t *stream);
 int nvqa_vgg_features_taken(nvqa_vgg *v, hipStream_t consumer);
+int nvqa_vgg_train_check_device(const nvqa_vgg *v, const char *fn);
+int nvqa_vgg_train_forward_raw_device(nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff,
+                                      const nvqa_dropout *dr, const float **feats_dev, hipStream_t *stream);
+int nvqa_vgg_backward_device(nvqa_vgg *v, const char *fn, const float *dfhat_dev, int n, hipStream_t producer);
 void nvqa_vgg_where(const nvqa_vgg *v, int *device, int *F);
 
 namespace nvqa {
@@ -65,6 +69,7 @@ struct AeBody {
     const uint8_t *images;
     int S, xoff, yoff;
     const nvqa_dropout *dr;
+    bool finetune = false; // the training forward, and the body's backward behind the step
 };
 
 // one batch as an entry point hands it over: the fields it has, the rest zero.  A parameter record and nothing more.
@@ -1435,6 +1440,12 @@ static int ae_backward(nvqa_ctx *c, const Drop &dr, bool want_df = false)
         ProfScope ps(c, PF_AE_WP_PROJ_BWD, 2.0 * B * E * (double)I);
         NVQA_TRY(wgrad(c, a.dX, E, a.feat, I, E, I, B, a.wp_g));
         NVQA_TRY(colsum(c, a.dX, B, E, E, a.wp_g + (size_t)E * I, nullptr));
+        if (want_df) { // d(loss)/d(f^) = dx0 W_p (W_p [E x I]); its buffer on first use: a context that never asks pays nothing
+            if (!a.dfeat) NVQA_TRY(ae_alloc(&a.dev, (void **)&a.dfeat, (size_t)B * I * 4, c->s));
+            GemmArgs g = ae_args(a.dX, E, a.wp_x, I, B, I, E);
+            const EpiStore e{a.dfeat, I, 0};
+            AE_LAUNCH(AeCfgStepBwd, A_KC, B_NC, false, EpiStore, 0, g, e);
+        }
         return 0;
     }
     if (a.bridge) return 0; // the frozen table has no gradient
@@ -1514,7 +1525,10 @@ static int ae_upload(nvqa_ctx *c, const AeBatch &bt, bool index)
             a.staged_rec = true;
             const float *fdev = nullptr;
             hipStream_t vs = nullptr;
-            NVQA_TRY(nvqa_vgg_forward_raw_device(body->vgg, body->fn, body->images, n, body->S, body->xoff, body->yoff, body->dr, &fdev, &vs));
+            if (body->finetune)
+                NVQA_TRY(nvqa_vgg_train_forward_raw_device(body->vgg, body->fn, body->images, n, body->S, body->xoff, body->yoff, body->dr, &fdev, &vs));
+            else
+                NVQA_TRY(nvqa_vgg_forward_raw_device(body->vgg, body->fn, body->images, n, body->S, body->xoff, body->yoff, body->dr, &fdev, &vs));
             if (!c->evStart) NVQA_HIP(hipEventCreateWithFlags(&c->evStart, hipEventDisableTiming)); // (nvqa_destroy releases it)
             NVQA_HIP(hipEventRecord(c->evStart, vs));
             NVQA_HIP(hipStreamWaitEvent(c->s, c->evStart, 0));
@@ -1653,12 +1667,16 @@ static int ae_step_impl(nvqa_ctx *c, AeBatch bt, const nvqa_dropout *dropout, fl
 {
     bt.n = c->d.B;
     if (bt.body) NVQA_TRY(ae_check_body(c, *bt.body, bt.n));
+    const bool finetune = bt.body && bt.body->finetune;
+    if (finetune) NVQA_TRY(nvqa_vgg_train_check_device(bt.body->vgg, bt.body->fn));
     if (!bt.tokens) { set_error("tokens is NULL"); return -1; }
     const Drop dr = ae_drop(dropout, true);
     NVQA_TRY(ae_upload(c, bt, !c->ae->feats));
     if (c->comm) NVQA_TRY(ae_dp_count(c, false));
     NVQA_TRY(ae_forward(c, dr, c->d.B, true));
-    NVQA_TRY(ae_train_tail(c, dr, dfeats_out != nullptr, c->ae->feats ? -1 : 0));
+    NVQA_TRY(ae_train_tail(c, dr, dfeats_out != nullptr || finetune, c->ae->feats ? -1 : 0));
+    // fine-tuning: d f^ goes to the extractor on the device -- L2Normalize's backward and the body's backward on its stream
+    if (finetune) NVQA_TRY(nvqa_vgg_backward_device(bt.body->vgg, bt.body->fn, c->ae->dfeat, bt.n, c->s));
     if (dfeats_out) {
         NVQA_HIP(hipMemcpyAsync(dfeats_out, c->ae->dfeat, (size_t)c->d.B * c->d.I * 4, hipMemcpyDeviceToHost, c->s));
         NVQA_HIP(hipStreamSynchronize(c->s));
@@ -2094,6 +2112,15 @@ extern "C" int nvqa_ae1_wp_evaluate(nvqa_ctx *c, int32_t n, const float *feats, 
     return ae_evaluate_impl(c, AeBatch{.n = n, .tokens = tokens, .feats = feats, .enc_tokens = enc_tokens}, loss_out, samples_out);
 }
 
+// nvqa_ae_wp_step with d(loss)/d(f^) = dx0 W_p returned (one more product): what nvqa_vgg16_backward(..., 1) takes
+extern "C" int nvqa_ae_wp_step_dfeats(nvqa_ctx *c, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                                      const nvqa_dropout *dropout, float *loss_out, float *dfeats_out)
+{
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_step_dfeats", AE_ARCH(AE2_WP)));
+    if (!feats || !dfeats_out) { set_error("nvqa_ae_wp_step_dfeats: feats or dfeats_out is NULL"); return -1; }
+    return ae_step_impl(c, AeBatch{.tokens = tokens, .feats = feats, .enc_tokens = enc_tokens}, dropout, loss_out, nullptr, dfeats_out);
+}
+
 // ---- the weak-paired steps with the VGG-16 body in the loop ----
 extern "C" int nvqa_ae_wp_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
                                       const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
@@ -2101,6 +2128,16 @@ extern "C" int nvqa_ae_wp_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const uint8_t 
 {
     NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_step_images", AE_ARCH(AE2_WP)));
     const AeBody body{vgg, "nvqa_ae_wp_step_images", images_u8, S, xoff, yoff, body_dropout};
+    return ae_step_impl(c, AeBatch{.tokens = tokens, .enc_tokens = enc_tokens, .body = &body}, dropout, loss_out, nullptr, nullptr);
+}
+
+// the same step with the body fine-tuning (section 9.11): training forward, the step, L2Normalize's backward, the body's backward
+extern "C" int nvqa_ae_wp_step_images_finetune(nvqa_ctx *c, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                               const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                                               const nvqa_dropout *dropout, float *loss_out)
+{
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae_wp_step_images_finetune", AE_ARCH(AE2_WP)));
+    const AeBody body{vgg, "nvqa_ae_wp_step_images_finetune", images_u8, S, xoff, yoff, body_dropout, true};
     return ae_step_impl(c, AeBatch{.tokens = tokens, .enc_tokens = enc_tokens, .body = &body}, dropout, loss_out, nullptr, nullptr);
 }
 
@@ -2123,6 +2160,20 @@ extern "C" int nvqa_ae1_wp_step_images(nvqa_ctx *c, nvqa_vgg *vgg, const uint8_t
         return -1;
     }
     const AeBody body{vgg, "nvqa_ae1_wp_step_images", images_u8, S, xoff, yoff, body_dropout};
+    return ae_step_impl(c, AeBatch{.tokens = tokens, .enc_tokens = enc_tokens, .enc_state = enc_state, .body = &body}, dropout, loss_out,
+                        nullptr, dfeats_out);
+}
+
+extern "C" int nvqa_ae1_wp_step_images_finetune(nvqa_ctx *c, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                                const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const float *enc_state,
+                                                const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out)
+{
+    NVQA_TRY(ae_check_arch(c, "nvqa_ae1_wp_step_images_finetune", AE_ARCH(AE1_WP)));
+    if ((enc_tokens != nullptr) == (enc_state != nullptr)) {
+        set_error("nvqa_ae1_wp_step_images_finetune: exactly one of enc_tokens and enc_state must be given");
+        return -1;
+    }
+    const AeBody body{vgg, "nvqa_ae1_wp_step_images_finetune", images_u8, S, xoff, yoff, body_dropout, true};
     return ae_step_impl(c, AeBatch{.tokens = tokens, .enc_tokens = enc_tokens, .enc_state = enc_state, .body = &body}, dropout, loss_out,
                         nullptr, dfeats_out);
 }

@@ -16,6 +16,8 @@
 //   A_IM2COL: implicit im2col of an NHWC tensor (3x3 conv), K-contiguous like A_KC
 //   B_KC: B stored [N][K]  (k contiguous)     Torch nn.Linear weight [out][in] in forward
 //   B_NC: B stored [K][N]  (n contiguous)     the same weight in dgrad, activations in wgrad
+//   B_NCTAP: B_NC whose rows are the pixels of an NHWC tensor seen through the 9 taps of a 3x3 convolution (the weight
+//            gradient of a convolution): B(k, n) = X[pixel k shifted by tap n / cC][channel n % cC], zero outside the image
 // LDS images: K-contiguous operands are stored [rows][BK] with the 16-byte chunk index XOR-swizzled
 // by the row (conflict-free ds_read_b128 for the hardware's lane groups); one such read feeds 4
 // MFMAs, with the k order permuted identically for A and B: k(q, w, h) = QK*q + 4*h + w (h = lane
@@ -46,7 +48,7 @@ namespace nvqa {
 template <class E> struct EpiTraits; // epilogues.h
 
 enum { A_KC = 0, A_MC = 1, A_IM2COL = 2, A_IM2COLF = 3 }; // A_IM2COLF: A_IM2COL when no K-tile straddles two taps (C_in % BK == 0)
-enum { B_KC = 0, B_NC = 1 };
+enum { B_KC = 0, B_NC = 1, B_NCTAP = 2 };
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -67,6 +69,8 @@ struct GemmArgs {
     int lda2, ldb2, K2;
     // A_IM2COL: A is an NHWC activation [n][cH][cW][cC]; row m = output pixel (n, y, x) of a 3x3,
     // stride-1, pad-1 convolution, k = (ky*3 + kx)*cC + ci (cC % 4 == 0): implicit GEMM, no im2col buffer
+    // B_NCTAP: B is that tensor; k = pixel (n, y, x), column = tap * cC + ci (N = 9 cC): the input of the layer whose
+    // weight gradient dW[co][tap][ci] = sum_pixels dZ[pixel][co] X[pixel + tap][ci] the product is
     int cH, cW, cC;
     // Ragged time-batched operands: rows come in groups of seg_rows (= B, one group per LSTM step) of
     // which only the first seg_limits[group] are active (the rest are zero padding: questions that
@@ -199,6 +203,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const Epi &epi,
     // conflict-free only for the 32-wide MFMA operand read)
     constexpr bool DMA = C::DMA != 0;
     static_assert(!DMA || MF == 32 || (AMODE != A_MC && BMODE == B_KC), "DMA with k-major operands needs MF = 32");
+    static_assert(BMODE != B_NCTAP || (!DMA && !GATES && SEG == 0 && !IM), "B_NCTAP: register-staged, one segment, plain A");
     constexpr int LDA = AMODE != A_MC ? BK : (DMA ? BM : BM + 4);
     constexpr int LDB = BMODE == B_KC ? BK : (DMA ? BN : BN + 4);
     constexpr int A_FL = AMODE != A_MC ? BM * BK : BK * LDA;
@@ -304,6 +309,10 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const Epi &epi,
     constexpr int NSEG = SEG > 0 ? 2 : 1;
     const float *pA[NSEG][NA], *pB[NSEG][NB];
     int kA[NA], kB[NB], sA[NA], sB[NB];
+    // B_NCTAP: a staged float4 keeps its columns, so its tap (dy, dx) is fixed over the K loop: pB carries the tap's offset, and
+    // (tpY, tpX) is the pixel row / column inside its image of the NEXT tile's row of this float4 (tiles are requested in order)
+    constexpr bool TAP = BMODE == B_NCTAP;
+    int tpDy[TAP ? NB : 1], tpDx[TAP ? NB : 1], tpY[TAP ? NB : 1], tpX[TAP ? NB : 1];
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
         const int f = tid + j * NT;
@@ -350,9 +359,17 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const Epi &epi,
             const int kr = f / (BN / 4), nq = f % (BN / 4), n = n0 + 4 * nq;
             kB[j] = kr;
             sB[j] = kr * LDB + 4 * nq;
+            if constexpr (TAP) {
+                const int tap = n / g.cC, ci = n - tap * g.cC, ky = tap / 3, kx = tap - 3 * ky;
+                const int p = kbeg + kr, t = p / g.cW;
+                tpDy[j] = ky - 1; tpDx[j] = kx - 1;
+                tpX[j] = p - t * g.cW; tpY[j] = t % g.cH;
+                pB[0][j] = (inb && n < g.N) ? g.B + ((ptrdiff_t)(ky - 1) * g.cW + (kx - 1)) * g.cC + ci : nullptr;
+            } else {
 #pragma unroll
-            for (int sg = 0; sg < NSEG; ++sg)
-                pB[sg][j] = (inb && n < g.N) ? (sg ? g.B2 + (size_t)kr * g.ldb2 : g.B + (size_t)kr * g.ldb) + n : nullptr;
+                for (int sg = 0; sg < NSEG; ++sg)
+                    pB[sg][j] = (inb && n < g.N) ? (sg ? g.B2 + (size_t)kr * g.ldb2 : g.B + (size_t)kr * g.ldb) + n : nullptr;
+            }
         }
         if (!inb) sB[j] = -1;
     }
@@ -452,7 +469,17 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const Epi &epi,
         for (int j = 0; j < NB; ++j) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             const float *p = SEG > 0 && s2 ? pB[NSEG - 1][j] : pB[0][j];
-            if constexpr (IM) { // the convolutions: unconditional load + select instead of a branch per load
+            if constexpr (TAP) {
+                // the shifted pixel lies in the same image exactly when its row and column do: the address is then inside X
+                const int iy = tpY[j] + tpDy[j], ix = tpX[j] + tpDx[j];
+                if (p && k0 + kB[j] < kend && iy >= 0 && iy < g.cH && ix >= 0 && ix < g.cW)
+                    v = *reinterpret_cast<const float4 *>(p + (size_t)(k0 + kB[j]) * g.cC);
+                tpX[j] += BK;
+                while (tpX[j] >= g.cW) {
+                    tpX[j] -= g.cW;
+                    if (++tpY[j] == g.cH) tpY[j] = 0;
+                }
+            } else if constexpr (IM) { // the convolutions: unconditional load + select instead of a branch per load
                 const bool ok = p && k0 + kB[j] < kend;
                 const float4 t = *reinterpret_cast<const float4 *>(ok ? (BMODE == B_KC ? p + k0 : p + (size_t)k0 * gldb) : g.B);
                 if (ok) v = t;

@@ -1,4 +1,4 @@
-// vgg.hip -- VGG-16 fc7 feature extractor (forward only) on gfx950.
+// vgg.hip -- VGG-16 fc7 feature extractor on gfx950; its f32 form can also be trained (backward and update: vgg_bwd.h).
 //
 // Replaces 002_train_vqa_arch1/001_prepro_img_vgg.lua: loadcaffe.load(...,'cudnn') + net:forward(ims)
 // + net.modules[38].output (:36-37,109-110), i.e. 13 conv3x3/ReLU, 5 max-pools, fc6+ReLU, fc7+ReLU
@@ -10,6 +10,7 @@
 // K = 9*C_in), bias+ReLU fused in the epilogue; fc6/fc7 are split-K GEMMs (M = batch is small, the
 // 411 MB fc6 weight stream is the cost) with bias+ReLU fused into the slab reduction.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -20,6 +21,7 @@
 #include "../../include/nvqa.h"
 #include "gemm_f32.h"
 #include "nvqa_ctx.h"
+#include "vgg_bwd.h"
 
 using namespace nvqa;
 
@@ -236,6 +238,29 @@ typedef Cfg<16, 64, 64, 32, 2, 2, 2, 1> CfgFc;
 typedef Cfg<16, 128, 128, 32, 4, 2, 1, 1, 0, 0, 2, 1> CfgConvB;
 typedef Cfg<16, 128, 64, 32, 4, 2, 1, 1, 0, 0, 2, 1> CfgConv64B;
 typedef Cfg<16, 64, 64, 32, 2, 2, 2, 1, 0, 0, 2> CfgFcB;
+typedef Cfg<16, 64, 32, 64, 4, 2, 1, 1> CfgFcDx; // dA = dZ W of fc6 / fc7 (M = batch): the small-M dgrad form of the LSTM steps
+
+// Training state of an extractor (nvqa_vgg16_train_enable): every layer's output of the last training forward, the gradient
+// buffers, the gradients in the device's repacked layouts, W', the optimiser state (on first use) and the split-K workspace.
+struct VggTrain {
+    float *in = nullptr;                     // the network's NHWC4 input (conv1_1's dW operand)
+    float *a[13] = {}, *pl[5] = {};          // post-ReLU convolution outputs, pool outputs (NHWC, padded channels)
+    float *fc6o = nullptr, *fc7o = nullptr;  // post-ReLU, post-dropout
+    float *gbuf[2] = {};                     // gradient ping-pong, each the largest activation
+    float *dY = nullptr, *dY2 = nullptr, *dz7 = nullptr, *dz6 = nullptr; // [max_batch x F]
+    float *gWc[13] = {}, *gbc[13] = {}, *gWf[2] = {}, *gbf[2] = {};      // gradients, laid out as Wc / bc / Wf / bf
+    float *Wt[13] = {};                      // W' [C_in][9][C_out_pad] of conv1_2 .. conv5_3
+    float *sgdm_v[30] = {}, *adam_m[30] = {}, *adam_v[30] = {};
+    int64_t adam_t = 0;
+    float *ws = nullptr, *colpart = nullptr;
+    size_t ws_floats = 0;
+    hipEvent_t evGrad = nullptr, evGradTaken = nullptr; // a step's d f^ is ready on its stream / has been read on ours
+    double *part = nullptr;
+    int fwd_n = 0;          // batch of the last training forward (0: none)
+    float inv_keep = 1.0f;  // of its drop6 / drop7 (1: not live)
+    bool have_grads = false;
+};
+enum { kOptBlocks = 256, kColSplits = 128 };
 
 } // namespace
 
@@ -271,8 +296,12 @@ struct nvqa_vgg {
     // and the activation buffers, waits for it
     hipEvent_t evTaken = nullptr;
     bool taken_rec = false;
+    VggTrain *train = nullptr;
     int chunk = 256; // measured at B = 512 (configs[4]): one shot 142.0 ms, chunks of 256 140.1, of 128 143.2 (smaller launches fill the chip worse)
 };
+
+static void vgg_train_free(nvqa_vgg *v);
+static int vgg_repack_wt(nvqa_vgg *v);
 
 static int vgg_layout(nvqa_vgg *v)
 {
@@ -346,6 +375,25 @@ extern "C" int nvqa_vgg16_create(int device, int width_div, int input_hw, int ma
     return 0;
 }
 
+static void vgg_train_free(nvqa_vgg *v)
+{
+    VggTrain *t = v->train;
+    if (!t) return;
+    (void)hipStreamSynchronize(v->s);
+    auto fr = [](float *p) { if (p) (void)hipFree(p); };
+    fr(t->in); fr(t->fc6o); fr(t->fc7o); fr(t->gbuf[0]); fr(t->gbuf[1]); fr(t->dY); fr(t->dY2); fr(t->dz7); fr(t->dz6);
+    fr(t->ws); fr(t->colpart);
+    for (int i = 0; i < 13; ++i) { fr(t->a[i]); fr(t->gWc[i]); fr(t->gbc[i]); fr(t->Wt[i]); }
+    for (int i = 0; i < 5; ++i) fr(t->pl[i]);
+    for (int i = 0; i < 2; ++i) { fr(t->gWf[i]); fr(t->gbf[i]); }
+    for (int i = 0; i < 30; ++i) { fr(t->sgdm_v[i]); fr(t->adam_m[i]); fr(t->adam_v[i]); }
+    if (t->part) (void)hipFree(t->part);
+    if (t->evGrad) (void)hipEventDestroy(t->evGrad);
+    if (t->evGradTaken) (void)hipEventDestroy(t->evGradTaken);
+    delete t;
+    v->train = nullptr;
+}
+
 extern "C" int nvqa_vgg16_destroy(nvqa_vgg *v)
 {
     if (!v) return 0;
@@ -363,6 +411,7 @@ extern "C" int nvqa_vgg16_destroy(nvqa_vgg *v)
     if (v->evRaw) (void)hipEventDestroy(v->evRaw);
     if (v->raw) (void)hipFree(v->raw);
     if (v->h_raw) (void)hipHostFree(v->h_raw);
+    vgg_train_free(v);
     if (v->sc) (void)hipStreamDestroy(v->sc);
     (void)hipStreamDestroy(v->s);
     delete v;
@@ -387,6 +436,18 @@ static int vgg_bf16_images(nvqa_vgg *v)
 
 extern "C" size_t nvqa_vgg16_weight_count(const nvqa_vgg *v) { return v ? v->flat_total : 0; }
 extern "C" int nvqa_vgg16_feature_dim(const nvqa_vgg *v) { return v ? v->F : 0; }
+
+// W' of every convolution that computes a dX, from the current W
+static int vgg_repack_wt(nvqa_vgg *v)
+{
+    for (int i = 1; i < 13; ++i) {
+        const size_t n = (size_t)v->cin[i] * 9 * v->coutp[i];
+        hipLaunchKernelGGL(k_vgg_repack_wt, dim3((n + 255) / 256), dim3(256), 0, v->s, v->Wc[i], v->cout[i], v->cin[i], v->cinp[i], v->coutp[i],
+                           v->train->Wt[i]);
+    }
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
 
 // weights: one flat vector in Caffe order and layout -- for each conv W [Cout][Cin][3][3], b [Cout];
 // fc6 W [F][C5*S*S] (columns in CHW order), b; fc7 W [F][F], b.
@@ -419,6 +480,7 @@ extern "C" int nvqa_vgg16_set_weights(nvqa_vgg *v, const float *flat)
     }
     v->have_weights = true;
     if (v->g950) NVQA_TRY(vgg_bf16_images(v));
+    if (v->train) NVQA_TRY(vgg_repack_wt(v));
     return 0;
 }
 
@@ -455,18 +517,22 @@ struct RawSrc {
 
 // the network on n images that are already on the device (img [n][3][hw][hw], or raw); post-ReLU fc7 features -> out [n x F],
 // with dr (mode 1) module 38's training-mode output: drop6 and drop7 live
-static int vgg_network(nvqa_vgg *v, const float *img, int n, float *out, const RawSrc *raw = nullptr, const Drop *dr = nullptr)
+// t: the training forward -- the same launches, every layer into its own buffer of the training state
+static int vgg_network(nvqa_vgg *v, const float *img, int n, float *out, const RawSrc *raw = nullptr, const Drop *dr = nullptr,
+                       VggTrain *t = nullptr)
 {
+    float *const in = t ? t->in : v->nhwc_in, *const fc6o = t ? t->fc6o : v->fc6o;
+    int npool = 0;
     int H = v->hw, W = v->hw;
     const size_t px = (size_t)n * H * W;
     if (raw)
         hipLaunchKernelGGL(k_prepro_u8_nhwc4, dim3((px + 255) / 256), dim3(256), 0, v->s, raw->u8, n, raw->S, v->hw, raw->xoff, raw->yoff,
-                           reinterpret_cast<float4 *>(v->nhwc_in));
-    else hipLaunchKernelGGL(k_nchw_to_nhwc4, dim3((px + 255) / 256), dim3(256), 0, v->s, img, n, H, W, reinterpret_cast<float4 *>(v->nhwc_in));
-    const float *cur = v->nhwc_in;
+                           reinterpret_cast<float4 *>(in));
+    else hipLaunchKernelGGL(k_nchw_to_nhwc4, dim3((px + 255) / 256), dim3(256), 0, v->s, img, n, H, W, reinterpret_cast<float4 *>(in));
+    const float *cur = in;
     int which = 0;
     for (int i = 0; i < 13; ++i) {
-        float *dst = v->act[which];
+        float *dst = t ? t->a[i] : v->act[which];
         GemmArgs g = {};
         g.A = cur; g.B = v->Wc[i]; g.ldb = 9 * v->cinp[i];
         g.M = n * H * W; g.N = v->cout[i]; g.K = 9 * v->cinp[i]; g.kslice = g.K;
@@ -519,7 +585,7 @@ static int vgg_network(nvqa_vgg *v, const float *img, int n, float *out, const R
 #undef NVQA_CONV_GO
         cur = dst; which ^= 1;
         if (kPoolAfter[i]) {
-            float *pd = v->act[which];
+            float *pd = t ? t->pl[npool++] : v->act[which];
             const size_t total = (size_t)n * (H / 2) * (W / 2) * (ldc / 4);
             hipLaunchKernelGGL(k_maxpool2_nhwc, dim3((total + 255) / 256), dim3(256), 0, v->s, reinterpret_cast<const float4 *>(cur), n, H, W, ldc / 4, reinterpret_cast<float4 *>(pd));
             H /= 2; W /= 2;
@@ -529,9 +595,9 @@ static int vgg_network(nvqa_vgg *v, const float *img, int n, float *out, const R
     NVQA_HIP(hipGetLastError());
     const int c5p = (v->c5 + 3) / 4 * 4;
     // fc6 + ReLU, fc7 + ReLU -> module 38 (the two Dropouts: identity without dr)
-    if (v->g950) NVQA_TRY(fc_layer(v, cur, n, v->s5 * v->s5 * c5p, reinterpret_cast<const float *>(v->Wf16), v->bf[0], v->fc6o, true, dr, NVQA_SITE_VGG_FC6));
-    else NVQA_TRY(fc_layer(v, cur, n, v->s5 * v->s5 * c5p, v->Wf[0], v->bf[0], v->fc6o, false, dr, NVQA_SITE_VGG_FC6));
-    NVQA_TRY(fc_layer(v, v->fc6o, n, v->F, v->Wf[1], v->bf[1], out, false, dr, NVQA_SITE_VGG_FC7));
+    if (v->g950) NVQA_TRY(fc_layer(v, cur, n, v->s5 * v->s5 * c5p, reinterpret_cast<const float *>(v->Wf16), v->bf[0], fc6o, true, dr, NVQA_SITE_VGG_FC6));
+    else NVQA_TRY(fc_layer(v, cur, n, v->s5 * v->s5 * c5p, v->Wf[0], v->bf[0], fc6o, false, dr, NVQA_SITE_VGG_FC6));
+    NVQA_TRY(fc_layer(v, fc6o, n, v->F, v->Wf[1], v->bf[1], out, false, dr, NVQA_SITE_VGG_FC7));
     return 0;
 }
 
@@ -613,7 +679,9 @@ int nvqa_vgg_check_raw(const nvqa_vgg *v, const char *fn, const uint8_t *images,
 }
 
 // forward of n raw host images through the fused front end; the features (module 38's output) stay in v->fc7o [n x F]
-static int vgg_forward_raw(nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff, const nvqa_dropout *dr)
+// t: the training forward (features in t->fc7o)
+static int vgg_forward_raw(nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff, const nvqa_dropout *dr,
+                           VggTrain *t = nullptr)
 {
     NVQA_TRY(nvqa_vgg_check_raw(v, fn, images, n, S, xoff, yoff, dr));
     NVQA_HIP(hipSetDevice(v->device));
@@ -636,7 +704,8 @@ static int vgg_forward_raw(nvqa_vgg *v, const char *fn, const uint8_t *images, i
     Drop d = {};
     if (dr && dr->mode) { d.mode = 1; d.p = dr->p; d.inv_keep = 1.0f / (1.0f - dr->p); d.seed = dr->seed; d.step = dr->step; }
     const RawSrc raw{v->raw, S, xoff, yoff};
-    NVQA_TRY(vgg_network(v, nullptr, n, v->fc7o, &raw, d.mode ? &d : nullptr));
+    NVQA_TRY(vgg_network(v, nullptr, n, t ? t->fc7o : v->fc7o, &raw, d.mode ? &d : nullptr, t));
+    if (t) { t->fwd_n = n; t->inv_keep = d.mode ? d.inv_keep : 1.0f; }
     NVQA_HIP(hipEventRecord(v->evDone, v->s));
     v->done_rec = true;
     return 0;
@@ -682,6 +751,7 @@ extern "C" int nvqa_vgg16_set_precision(nvqa_vgg *v, int bf16)
 {
     if (!v) { set_error("vgg is NULL"); return -1; }
     if (bf16 != 0 && bf16 != 1) { set_error("precision must be 0 (f32) or 1 (bf16 operands)"); return -1; }
+    if (bf16 && v->train) { set_error("nvqa_vgg16_set_precision: bf16 operands while training is enabled (the body trains in f32)"); return -1; }
     v->bf16 = bf16 != 0;
     const char *form = getenv("NVQA_VGG_BF16_FORM"); // read at every call: the tests compare the two forms in one process
     const bool old_form = form && form[0] == '1';
@@ -712,4 +782,436 @@ extern "C" int nvqa_vgg16_preprocess(nvqa_vgg *v, const float *rgb, int n, int H
     NVQA_HIP(hipStreamSynchronize(v->s));
     (void)hipFree(din); (void)hipFree(dout);
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Training the f32 body: protos.cnn:backward(data.imgs, dfeats) and the cnn update of
+// 004_train_arch{1,2}_weakpaired_autoencoder_vgg.lua (kernels and the derivation: vgg_bwd.h)
+// ---------------------------------------------------------------------------------------------------------------------------
+
+// the 30 parameter arrays in ABI order (conv W, b; fc6 W, b; fc7 W, b) in their device layouts: element i of a weight array is a
+// true weight when i % period < real
+struct VggParam {
+    float *x, *g;
+    size_t n;
+    int period, real;
+};
+static void vgg_params(const nvqa_vgg *v, VggParam (&p)[30])
+{
+    const VggTrain *t = v->train;
+    const int c5p = (v->c5 + 3) / 4 * 4;
+    for (int i = 0; i < 13; ++i) {
+        p[2 * i] = {v->Wc[i], t->gWc[i], (size_t)v->cout[i] * 9 * v->cinp[i], v->cinp[i], v->cin[i]};
+        p[2 * i + 1] = {v->bc[i], t->gbc[i], (size_t)v->cout[i], 1, 1};
+    }
+    p[26] = {v->Wf[0], t->gWf[0], (size_t)v->F * v->s5 * v->s5 * c5p, c5p, v->c5};
+    p[27] = {v->bf[0], t->gbf[0], (size_t)v->F, 1, 1};
+    p[28] = {v->Wf[1], t->gWf[1], (size_t)v->F * v->F, 1, 1};
+    p[29] = {v->bf[1], t->gbf[1], (size_t)v->F, 1, 1};
+}
+
+// K slices of convolution i's weight gradient at K = px pixels: enough workgroups for the chip's 256 CUs twice over, as fc_layer
+// chooses.  ks_bound: the power of two the rule stops at -- non-decreasing in px and never below the slices actually used (the
+// slice length is rounded up to whole K-tiles, which can only lower their number), so the workspace is sized from it at max_batch
+static void vgg_dw_split(const nvqa_vgg *v, int i, size_t px, int *ks_out, int *kslice_out, int *ks_bound = nullptr)
+{
+    const int BM = v->cout[i] > 64 ? 128 : 64;
+    const size_t tiles = (size_t)((v->cout[i] + BM - 1) / BM) * ((9 * v->cinp[i] + 127) / 128);
+    int ks = 1;
+    while (ks < 64 && tiles * ks < 512 && px / (ks * 2) >= 128) ks *= 2;
+    const int kslice = (int)(((px + ks - 1) / ks + 31) / 32 * 32);
+    *ks_out = (int)((px + kslice - 1) / kslice);
+    *kslice_out = kslice;
+    if (ks_bound) *ks_bound = ks;
+}
+static void vgg_fc_split(int N, int K, int *ks_out, int *kslice_out)
+{
+    int ks = 1;
+    while (ks < 16 && (size_t)((N + 31) / 32) * ks < 512 && K / (ks * 2) >= 256) ks *= 2;
+    const int kslice = ((K + ks - 1) / ks + 63) / 64 * 64;
+    *ks_out = (K + kslice - 1) / kslice;
+    *kslice_out = kslice;
+}
+
+extern "C" int nvqa_vgg16_train_enable(nvqa_vgg *v, int on)
+{
+    if (!v) { set_error("vgg is NULL"); return -1; }
+    if (on != 0 && on != 1) { set_error("nvqa_vgg16_train_enable: on must be 0 or 1"); return -1; }
+    NVQA_HIP(hipSetDevice(v->device));
+    if (!on) { vgg_train_free(v); return 0; }
+    if (v->bf16) { set_error("nvqa_vgg16_train_enable: the extractor is in bf16 mode (the body trains in f32)"); return -1; }
+    if (v->train) return 0;
+    VggTrain *t = v->train = new VggTrain();
+    auto alloc = [&](float **p, size_t floats) -> int {
+        NVQA_HIP(hipMalloc((void **)p, floats * 4));
+        NVQA_HIP(hipMemsetAsync(*p, 0, floats * 4, v->s));
+        return 0;
+    };
+    auto all = [&]() -> int {
+        const int mb = v->max_batch, F = v->F, c5p = (v->c5 + 3) / 4 * 4;
+        size_t H = v->hw;
+        NVQA_TRY(alloc(&t->in, (size_t)mb * H * H * 4));
+        size_t ws = (size_t)16 * mb * std::max(F, v->s5 * v->s5 * c5p); // the fc products' slabs: dA of fc7 (N = F) and of fc6 (N = fc6's columns)
+        int maxn = std::max(F, 4);
+        for (int i = 0, np = 0; i < 13; ++i) {
+            const size_t px = (size_t)mb * H * H, wn = (size_t)v->cout[i] * 9 * v->cinp[i];
+            NVQA_TRY(alloc(&t->a[i], px * v->coutp[i]));
+            NVQA_TRY(alloc(&t->gWc[i], wn));
+            NVQA_TRY(alloc(&t->gbc[i], v->cout[i]));
+            if (i > 0) NVQA_TRY(alloc(&t->Wt[i], (size_t)v->cin[i] * 9 * v->coutp[i]));
+            int ks, kslice, ks_bound;
+            vgg_dw_split(v, i, px, &ks, &kslice, &ks_bound);
+            ws = std::max(ws, ks_bound * wn);
+            maxn = std::max(maxn, v->cout[i]);
+            if (kPoolAfter[i]) { H /= 2; NVQA_TRY(alloc(&t->pl[np++], (size_t)mb * H * H * v->coutp[i])); }
+        }
+        NVQA_TRY(alloc(&t->fc6o, (size_t)mb * F));
+        NVQA_TRY(alloc(&t->fc7o, (size_t)mb * F));
+        for (float **p : {&t->dY, &t->dY2, &t->dz7, &t->dz6}) NVQA_TRY(alloc(p, (size_t)mb * F));
+        NVQA_TRY(alloc(&t->gbuf[0], v->act_floats));
+        NVQA_TRY(alloc(&t->gbuf[1], v->act_floats));
+        NVQA_TRY(alloc(&t->gWf[0], (size_t)F * v->s5 * v->s5 * c5p));
+        NVQA_TRY(alloc(&t->gWf[1], (size_t)F * F));
+        NVQA_TRY(alloc(&t->gbf[0], F));
+        NVQA_TRY(alloc(&t->gbf[1], F));
+        NVQA_TRY(alloc(&t->ws, ws));
+        t->ws_floats = ws;
+        NVQA_TRY(alloc(&t->colpart, (size_t)kColSplits * maxn));
+        NVQA_HIP(hipMalloc((void **)&t->part, (size_t)30 * 2 * kOptBlocks * sizeof(double)));
+        NVQA_HIP(hipEventCreateWithFlags(&t->evGrad, hipEventDisableTiming));
+        NVQA_HIP(hipEventCreateWithFlags(&t->evGradTaken, hipEventDisableTiming));
+        if (v->have_weights) NVQA_TRY(vgg_repack_wt(v));
+        NVQA_HIP(hipStreamSynchronize(v->s));
+        return 0;
+    };
+    if (all() != 0) { vgg_train_free(v); return -1; }
+    return 0;
+}
+
+static int vgg_train_check(const nvqa_vgg *v, const char *fn)
+{
+    if (!v) { set_error("%s: vgg is NULL", fn); return -1; }
+    if (v->bf16) { set_error("%s: the extractor is in bf16 mode (the body trains in f32)", fn); return -1; }
+    if (!v->train) { set_error("%s before nvqa_vgg16_train_enable(vgg, 1)", fn); return -1; }
+    return 0;
+}
+
+extern "C" int nvqa_vgg16_train_forward_raw(nvqa_vgg *v, const uint8_t *images, int n, int S, int xoff, int yoff,
+                                            const nvqa_dropout *dropout, float *feats_out)
+{
+    NVQA_TRY(vgg_train_check(v, "nvqa_vgg16_train_forward_raw"));
+    NVQA_TRY(vgg_forward_raw(v, "nvqa_vgg16_train_forward_raw", images, n, S, xoff, yoff, dropout, v->train));
+    if (feats_out) {
+        NVQA_HIP(hipMemcpyAsync(feats_out, v->train->fc7o, (size_t)n * v->F * 4, hipMemcpyDeviceToHost, v->s));
+        NVQA_HIP(hipStreamSynchronize(v->s));
+    }
+    return 0;
+}
+
+extern "C" int nvqa_vgg16_train_activation(nvqa_vgg *v, int which, float *out)
+{
+    NVQA_TRY(vgg_train_check(v, "nvqa_vgg16_train_activation"));
+    VggTrain *t = v->train;
+    if (!out || which < 0 || which > 14) { set_error("nvqa_vgg16_train_activation: which=%d outside 0..14, or out is NULL", which); return -1; }
+    if (!t->fwd_n) { set_error("nvqa_vgg16_train_activation before nvqa_vgg16_train_forward_raw"); return -1; }
+    NVQA_HIP(hipSetDevice(v->device));
+    const int n = t->fwd_n;
+    if (which >= 13) {
+        NVQA_HIP(hipMemcpyAsync(out, which == 13 ? t->fc6o : t->fc7o, (size_t)n * v->F * 4, hipMemcpyDeviceToHost, v->s));
+        NVQA_HIP(hipStreamSynchronize(v->s));
+        return 0;
+    }
+    int H = v->hw;
+    for (int i = 0; i < which; ++i) H >>= kPoolAfter[i];
+    const int C = v->cout[which], Cp = v->coutp[which];
+    std::vector<float> h((size_t)n * H * H * Cp);
+    NVQA_HIP(hipMemcpyAsync(h.data(), t->a[which], h.size() * 4, hipMemcpyDeviceToHost, v->s));
+    NVQA_HIP(hipStreamSynchronize(v->s));
+    for (int b = 0; b < n; ++b)
+        for (int c = 0; c < C; ++c)
+            for (int p = 0; p < H * H; ++p) out[((size_t)b * C + c) * H * H + p] = h[((size_t)b * H * H + p) * Cp + c];
+    return 0;
+}
+
+static int vgg_colsum(nvqa_vgg *v, const float *X, size_t M, int N, int ld, float *out)
+{
+    VggTrain *t = v->train;
+    int S = (int)std::min<size_t>(kColSplits, std::max<size_t>(1, M / 256));
+    const int rps = (int)((M + S - 1) / S);
+    S = (int)((M + rps - 1) / rps);
+    hipLaunchKernelGGL(k_vgg_colsum_part, dim3((N + 63) / 64, S), dim3(256), 0, v->s, X, (int)M, N, ld, rps, t->colpart);
+    hipLaunchKernelGGL(k_vgg_colsum_final, dim3((N + 255) / 256), dim3(256), 0, v->s, t->colpart, S, N, out);
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
+
+// dW = dZ^T A (K = n rows) and db = colsum(dZ) of an fc layer
+static int vgg_fc_wgrad(nvqa_vgg *v, const float *dz, const float *A, int n, int K, float *gW, float *gb)
+{
+    GemmArgs g = {};
+    g.A = dz; g.lda = v->F; g.B = A; g.ldb = K; g.M = v->F; g.N = K; g.K = n; g.kslice = n;
+    g.xcd = 1;
+    NVQA_HIP((launch_gemm<CfgVggDw, A_MC, B_NC, false, EpiStore>(v->s, g, EpiStore{gW, K, 0})));
+    return vgg_colsum(v, dz, n, v->F, v->F, gb);
+}
+
+// dA [n x N] = dZ [n x F] W [F x N]; y (fc6's stored output): the sum goes through that layer's ReLU / Dropout mask
+static int vgg_fc_dgrad(nvqa_vgg *v, const float *dz, const float *W, int n, int N, const float *y, float s, float *out)
+{
+    VggTrain *t = v->train;
+    int ks, kslice;
+    vgg_fc_split(N, v->F, &ks, &kslice);
+    GemmArgs g = {};
+    g.A = dz; g.lda = v->F; g.B = W; g.ldb = N; g.M = n; g.N = N; g.K = v->F; g.kslice = kslice;
+    g.xcd = 1;
+    if (ks == 1 && !y) {
+        NVQA_HIP((launch_gemm<CfgFcDx, A_KC, B_NC, false, EpiStore>(v->s, g, EpiStore{out, N, 0})));
+        return 0;
+    }
+    const size_t count = (size_t)n * N;
+    if (ks * count > t->ws_floats) { set_error("vgg backward: split-K workspace too small"); return -1; }
+    NVQA_HIP((launch_gemm<CfgFcDx, A_KC, B_NC, false, EpiStore>(v->s, g, EpiStore{t->ws, N, count})));
+    hipLaunchKernelGGL(k_vgg_slab_sum, dim3((count + 255) / 256), dim3(256), 0, v->s, t->ws, ks, count, y, s, out);
+    NVQA_HIP(hipGetLastError());
+    return 0;
+}
+
+template <class CFG> static int vgg_conv_dx_go(nvqa_vgg *v, const GemmArgs &g, const EpiGradMask &ep)
+{
+    if (g.cC % CFG::BK == 0) NVQA_HIP((launch_gemm<CFG, A_IM2COLF, B_KC, false, EpiGradMask>(v->s, g, ep)));
+    else NVQA_HIP((launch_gemm<CFG, A_IM2COL, B_KC, false, EpiGradMask>(v->s, g, ep)));
+    return 0;
+}
+
+// the whole backward from dY = d(loss)/d(module 38's output) [n x F] on the device; everything on the extractor's stream
+static int vgg_backward_device(nvqa_vgg *v, const float *dY, int n)
+{
+    VggTrain *t = v->train;
+    const int F = v->F, c5p = (v->c5 + 3) / 4 * 4, fcin_p = v->s5 * v->s5 * c5p;
+    const size_t nf = (size_t)n * F;
+    // fc7, fc6
+    hipLaunchKernelGGL(k_vgg_fc_dz, dim3((nf + 255) / 256), dim3(256), 0, v->s, dY, t->fc7o, t->inv_keep, nf, t->dz7);
+    NVQA_TRY(vgg_fc_wgrad(v, t->dz7, t->fc6o, n, F, t->gWf[1], t->gbf[1]));
+    NVQA_TRY(vgg_fc_dgrad(v, t->dz7, v->Wf[1], n, F, t->fc6o, t->inv_keep, t->dz6));
+    NVQA_TRY(vgg_fc_wgrad(v, t->dz6, t->pl[4], n, fcin_p, t->gWf[0], t->gbf[0]));
+    int cur = 0;
+    NVQA_TRY(vgg_fc_dgrad(v, t->dz6, v->Wf[0], n, fcin_p, nullptr, 1.0f, t->gbuf[cur])); // = d(pool5), NHWC
+    // the convolutions, top down; gbuf[cur] holds d(pool output) behind a pool, else dZ of layer i
+    int H = v->s5, np = 5;
+    for (int i = 12; i >= 0; --i) {
+        const int Cp = v->coutp[i];
+        if (kPoolAfter[i]) {
+            --np;
+            H *= 2;
+            const size_t total = (size_t)n * (H / 2) * (H / 2) * (Cp / 4);
+            hipLaunchKernelGGL(k_vgg_pool_relu_bwd, dim3((total + 255) / 256), dim3(256), 0, v->s, reinterpret_cast<const float4 *>(t->a[i]),
+                               reinterpret_cast<const float4 *>(t->gbuf[cur]), n, H, H, Cp / 4, reinterpret_cast<float4 *>(t->gbuf[cur ^ 1]));
+            cur ^= 1;
+        }
+        const float *dz = t->gbuf[cur];
+        const size_t px = (size_t)n * H * H;
+        const bool pool_below = i > 0 && kPoolAfter[i - 1];
+        const float *x = i == 0 ? t->in : (pool_below ? t->pl[np - 1] : t->a[i - 1]);
+        {   // dW: slabs over K = pixels, summed in slab order
+            int ks, kslice;
+            vgg_dw_split(v, i, px, &ks, &kslice);
+            const size_t wn = (size_t)v->cout[i] * 9 * v->cinp[i];
+            if (ks * wn > t->ws_floats) { set_error("vgg backward: split-K workspace too small"); return -1; }
+            GemmArgs g = {};
+            g.A = dz; g.lda = Cp; g.B = x; g.M = v->cout[i]; g.N = 9 * v->cinp[i]; g.K = (int)px; g.kslice = kslice;
+            g.cH = H; g.cW = H; g.cC = v->cinp[i];
+            g.xcd = 1;
+            const EpiStore ep{ks == 1 ? t->gWc[i] : t->ws, g.N, wn};
+            if (v->cout[i] > 64) NVQA_HIP((launch_gemm<CfgVggDw, A_MC, B_NCTAP, false, EpiStore>(v->s, g, ep)));
+            else NVQA_HIP((launch_gemm<CfgVggDw64, A_MC, B_NCTAP, false, EpiStore>(v->s, g, ep)));
+            if (ks > 1)
+                hipLaunchKernelGGL(k_vgg_slab_sum, dim3((wn + 255) / 256), dim3(256), 0, v->s, t->ws, ks, wn, (const float *)nullptr, 1.0f, t->gWc[i]);
+        }
+        NVQA_TRY(vgg_colsum(v, dz, px, v->cout[i], Cp, t->gbc[i]));
+        if (i == 0) break; // conv1_1 computes no dX
+        // dX: the forward implicit GEMM on dZ with W'; x [y_below > 0] when the layer below feeds this one directly
+        float *dx = t->gbuf[cur ^ 1];
+        GemmArgs g = {};
+        g.A = dz; g.B = t->Wt[i]; g.ldb = 9 * Cp;
+        g.M = (int)px; g.N = v->cin[i]; g.K = 9 * Cp; g.kslice = g.K;
+        g.cH = H; g.cW = H; g.cC = Cp;
+        g.xcd = 1;
+        const int ldc = v->cinp[i];
+        if (ldc != v->cin[i]) NVQA_HIP(hipMemsetAsync(dx, 0, px * ldc * 4, v->s));
+        const EpiGradMask ep{dx, ldc, pool_below ? nullptr : t->a[i - 1]};
+        const long tiles128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
+        if (Cp % 32 != 0 && v->cin[i] <= 64) NVQA_TRY(vgg_conv_dx_go<CfgConvFirst>(v, g, ep));
+        else if (v->cin[i] > 64 && tiles128 >= 256) NVQA_TRY(vgg_conv_dx_go<CfgConv>(v, g, ep));
+        else NVQA_TRY(vgg_conv_dx_go<CfgConv64>(v, g, ep));
+        cur ^= 1;
+    }
+    NVQA_HIP(hipGetLastError());
+    t->have_grads = true;
+    return 0;
+}
+
+extern "C" int nvqa_vgg16_backward(nvqa_vgg *v, const float *dfeats, int n, int through_l2norm)
+{
+    NVQA_TRY(vgg_train_check(v, "nvqa_vgg16_backward"));
+    VggTrain *t = v->train;
+    if (!dfeats) { set_error("nvqa_vgg16_backward: dfeats is NULL"); return -1; }
+    if (n < 1 || n > v->max_batch) { set_error("nvqa_vgg16_backward: n=%d outside 1..%d", n, v->max_batch); return -1; }
+    if (!t->fwd_n) { set_error("nvqa_vgg16_backward before a training forward (nvqa_vgg16_train_forward_raw)"); return -1; }
+    if (n != t->fwd_n) { set_error("nvqa_vgg16_backward: n=%d, the training forward ran %d images", n, t->fwd_n); return -1; }
+    NVQA_HIP(hipSetDevice(v->device));
+    NVQA_HIP(hipMemcpyAsync(t->dY, dfeats, (size_t)n * v->F * 4, hipMemcpyHostToDevice, v->s));
+    const float *dY = t->dY;
+    if (through_l2norm) {
+        hipLaunchKernelGGL(k_vgg_l2norm_bwd, dim3((n + 3) / 4), dim3(256), 0, v->s, t->dY, t->fc7o, n, v->F, t->dY2);
+        dY = t->dY2;
+    }
+    NVQA_TRY(vgg_backward_device(v, dY, n));
+    NVQA_HIP(hipStreamSynchronize(v->s));
+    return 0;
+}
+
+// the 30 arrays `src` (device layouts, ABI order) -> one flat vector in the ABI (Caffe) layout: set_weights' inverse
+static int vgg_unpack(nvqa_vgg *v, float *const (&src)[30], float *flat)
+{
+    NVQA_HIP(hipStreamSynchronize(v->s));
+    std::vector<float> h;
+    auto fetch = [&](const float *d, size_t n) -> int {
+        h.resize(n);
+        NVQA_HIP(hipMemcpy(h.data(), d, n * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    for (int i = 0; i < 13; ++i) {
+        const int co = v->cout[i], ci = v->cin[i], cp = v->cinp[i];
+        NVQA_TRY(fetch(src[2 * i], (size_t)co * 9 * cp));
+        float *dst = flat + v->w_off[i];
+        for (int o = 0; o < co; ++o)
+            for (int c = 0; c < ci; ++c)
+                for (int k = 0; k < 9; ++k) dst[((size_t)o * ci + c) * 9 + k] = h[((size_t)o * 9 + k) * cp + c];
+        NVQA_HIP(hipMemcpy(flat + v->b_off[i], src[2 * i + 1], (size_t)co * 4, hipMemcpyDeviceToHost));
+    }
+    const int c5 = v->c5, c5p = (c5 + 3) / 4 * 4, S = v->s5, F = v->F;
+    NVQA_TRY(fetch(src[26], (size_t)F * S * S * c5p));
+    float *dst = flat + v->w_off[13];
+    for (int f = 0; f < F; ++f)
+        for (int c = 0; c < c5; ++c)
+            for (int p = 0; p < S * S; ++p) dst[(size_t)f * v->fcin + (size_t)c * S * S + p] = h[((size_t)f * S * S + p) * c5p + c];
+    NVQA_HIP(hipMemcpy(flat + v->b_off[13], src[27], (size_t)F * 4, hipMemcpyDeviceToHost));
+    NVQA_HIP(hipMemcpy(flat + v->w_off[14], src[28], (size_t)F * F * 4, hipMemcpyDeviceToHost));
+    NVQA_HIP(hipMemcpy(flat + v->b_off[14], src[29], (size_t)F * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nvqa_vgg16_get_grads(nvqa_vgg *v, float *flat_out)
+{
+    NVQA_TRY(vgg_train_check(v, "nvqa_vgg16_get_grads"));
+    if (!flat_out) { set_error("nvqa_vgg16_get_grads: NULL argument"); return -1; }
+    if (!v->train->have_grads) { set_error("nvqa_vgg16_get_grads before nvqa_vgg16_backward"); return -1; }
+    NVQA_HIP(hipSetDevice(v->device));
+    VggParam p[30];
+    vgg_params(v, p);
+    float *src[30];
+    for (int i = 0; i < 30; ++i) src[i] = p[i].g;
+    return vgg_unpack(v, src, flat_out);
+}
+
+extern "C" int nvqa_vgg16_get_weights(nvqa_vgg *v, float *flat_out)
+{
+    if (!v || !flat_out) { set_error("nvqa_vgg16_get_weights: NULL argument"); return -1; }
+    if (!v->have_weights) { set_error("nvqa_vgg16_get_weights before nvqa_vgg16_set_weights"); return -1; }
+    NVQA_HIP(hipSetDevice(v->device));
+    float *src[30];
+    for (int i = 0; i < 13; ++i) { src[2 * i] = v->Wc[i]; src[2 * i + 1] = v->bc[i]; }
+    src[26] = v->Wf[0]; src[27] = v->bf[0]; src[28] = v->Wf[1]; src[29] = v->bf[1];
+    return vgg_unpack(v, src, flat_out);
+}
+
+template <int RULE>
+static void vgg_optim_launch(nvqa_vgg *v, const VggParam &p, float *m, float *vv, const VggRule &r, float wd, float clamp, float scale,
+                             double *part, int nb)
+{
+    hipLaunchKernelGGL(k_vgg_optim<RULE>, dim3(nb), dim3(256), 0, v->s, p.x, m, vv, p.g, p.n, p.period, p.real, r, wd, clamp, scale, part);
+}
+
+extern "C" int nvqa_vgg16_update(nvqa_vgg *v, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
+                                 float scale, float stats_out[2])
+{
+    NVQA_TRY(vgg_train_check(v, "nvqa_vgg16_update"));
+    VggTrain *t = v->train;
+    if (rule != NVQA_OPT_SGD && rule != NVQA_OPT_SGDM && rule != NVQA_OPT_ADAM) {
+        set_error("nvqa_vgg16_update: rule %d is not one of -cnn_optim's (NVQA_OPT_SGD, NVQA_OPT_SGDM, NVQA_OPT_ADAM)", rule);
+        return -1;
+    }
+    if (!t->have_grads) { set_error("nvqa_vgg16_update before nvqa_vgg16_backward"); return -1; }
+    NVQA_HIP(hipSetDevice(v->device));
+    VggParam p[30];
+    vgg_params(v, p);
+    // the rule's state, allocated and zeroed on first use
+    auto state = [&](float *(&st)[30]) -> int {
+        for (int i = 0; i < 30; ++i)
+            if (!st[i]) {
+                NVQA_HIP(hipMalloc((void **)&st[i], p[i].n * 4));
+                NVQA_HIP(hipMemsetAsync(st[i], 0, p[i].n * 4, v->s));
+            }
+        return 0;
+    };
+    VggRule r = {lr, alpha, beta, eps, 0.f};
+    if (rule == NVQA_OPT_SGDM) NVQA_TRY(state(t->sgdm_v));
+    if (rule == NVQA_OPT_ADAM) {
+        NVQA_TRY(state(t->adam_m));
+        NVQA_TRY(state(t->adam_v));
+        t->adam_t += 1;
+        r.step = (float)(lr * sqrt(1.0 - pow((double)beta, (double)t->adam_t)) / (1.0 - pow((double)alpha, (double)t->adam_t)));
+    }
+    int nb[30];
+    for (int i = 0; i < 30; ++i) {
+        nb[i] = (int)std::min<size_t>(kOptBlocks, (p[i].n + 255) / 256);
+        double *part = t->part + (size_t)i * 2 * kOptBlocks;
+        if (rule == NVQA_OPT_ADAM) vgg_optim_launch<NVQA_OPT_ADAM>(v, p[i], t->adam_m[i], t->adam_v[i], r, wd, clamp, scale, part, nb[i]);
+        else if (rule == NVQA_OPT_SGDM) vgg_optim_launch<NVQA_OPT_SGDM>(v, p[i], t->sgdm_v[i], nullptr, r, wd, clamp, scale, part, nb[i]);
+        else vgg_optim_launch<NVQA_OPT_SGD>(v, p[i], nullptr, nullptr, r, wd, clamp, scale, part, nb[i]);
+    }
+    NVQA_HIP(hipGetLastError());
+    NVQA_TRY(vgg_repack_wt(v)); // W' follows W
+    if (stats_out) {
+        std::vector<double> h((size_t)30 * 2 * kOptBlocks);
+        NVQA_HIP(hipMemcpyAsync(h.data(), t->part, h.size() * sizeof(double), hipMemcpyDeviceToHost, v->s));
+        NVQA_HIP(hipStreamSynchronize(v->s));
+        double sq = 0, cnt = 0;
+        for (int i = 0; i < 30; ++i)
+            for (int b = 0; b < nb[i]; ++b) { sq += h[((size_t)i * kOptBlocks + b) * 2]; cnt += h[((size_t)i * kOptBlocks + b) * 2 + 1]; }
+        stats_out[0] = (float)sqrt(sq);
+        stats_out[1] = (float)cnt;
+    }
+    return 0;
+}
+
+// ---- used by the fine-tuning weak-paired steps (ae.hip) ----
+int nvqa_vgg_train_check_device(const nvqa_vgg *v, const char *fn) { return vgg_train_check(v, fn); }
+
+// the training forward with the features left on the device
+int nvqa_vgg_train_forward_raw_device(nvqa_vgg *v, const char *fn, const uint8_t *images, int n, int S, int xoff, int yoff,
+                                      const nvqa_dropout *dr, const float **feats_dev, hipStream_t *stream)
+{
+    NVQA_TRY(vgg_train_check(v, fn));
+    NVQA_TRY(vgg_forward_raw(v, fn, images, n, S, xoff, yoff, dr, v->train));
+    *feats_dev = v->train->fc7o;
+    *stream = v->s;
+    return 0;
+}
+
+// dfhat_dev [n x F] = d(loss)/d(f^), written on `producer`: the extractor's stream waits for it (the mirror of evTaken), runs
+// L2Normalize's backward into its own buffer -- after which the producer may overwrite dfhat_dev -- and the body's backward.
+// The kernels and their order are nvqa_vgg16_backward(..., 1)'s; nothing visits the host and nothing is synchronised.
+int nvqa_vgg_backward_device(nvqa_vgg *v, const char *fn, const float *dfhat_dev, int n, hipStream_t producer)
+{
+    NVQA_TRY(vgg_train_check(v, fn));
+    VggTrain *t = v->train;
+    if (n != t->fwd_n) { set_error("%s: n=%d, the training forward ran %d images", fn, n, t->fwd_n); return -1; }
+    NVQA_HIP(hipEventRecord(t->evGrad, producer));
+    NVQA_HIP(hipStreamWaitEvent(v->s, t->evGrad, 0));
+    hipLaunchKernelGGL(k_vgg_l2norm_bwd, dim3((n + 3) / 4), dim3(256), 0, v->s, dfhat_dev, t->fc7o, n, v->F, t->dY2);
+    NVQA_HIP(hipGetLastError());
+    NVQA_HIP(hipEventRecord(t->evGradTaken, v->s));
+    NVQA_HIP(hipStreamWaitEvent(producer, t->evGradTaken, 0));
+    return vgg_backward_device(v, t->dY2, n);
 }

@@ -452,6 +452,33 @@ class _BodyInLoop:
         xoff, yoff = crop_origin_train(self.seed, self.iter, images.shape[-1], self._need_body().hw)
         return xoff, yoff, binding.Dropout(1, BODY_DROP_PROB, self.seed, self.iter)
 
+    finetune_body = False
+    _frozen_body_stats = None
+
+    def _init_finetune_body(self, finetune_body):
+        """finetune_body=True: once finetuning() holds, the step hands d(loss)/d(f^) to the body (the *_finetune step) and
+        body.update runs the -cnn_optim rule on the whole body -- what the scripts do with protos.cnn from finetune_cnn_after on"""
+        self.finetune_body = bool(finetune_body)
+        if self.finetune_body:
+            if self.body is None:
+                raise ValueError("finetune_body=True needs body=binding.Vgg16(...)")
+            self.body.train_enable(True)
+
+    def _body_update(self, cnn_lr, scale):
+        """the cnn update of the scripts on the body: wd through the scales, then the clamp, only when cnn_weight_decay > 0
+        (arch2 :318-322), then -cnn_optim at the decayed rate.  Returns (cnnParamsNorm, # cnn updates) of the body."""
+        clamp = self.grad_clip if self.cnn_weight_decay > 0 else 0.0
+        self._frozen_body_stats = None
+        return self.body.update(binding.CNN_OPT_RULES[self.cnn_optim], cnn_lr, self.cnn_alpha, self.cnn_beta, self.eps,
+                                self.cnn_weight_decay, clamp, scale)
+
+    def _body_stats_frozen(self):
+        """the body's log figures before fine-tuning starts: its gradient is zero, so the count is that of the zero weights"""
+        if self._frozen_body_stats is None:
+            w = self.body.get_weights()
+            self._frozen_body_stats = (float(np.sqrt((w.astype(np.float64) ** 2).sum())), int((w == 0).sum()))
+        return self._frozen_body_stats
+
     def _body_eval(self, images):
         """(xoff, yoff, body dropout) of eval_split: the central window; the body in evaluate mode unless
         body_dropout_in_eval (the arch2 script never calls cnn:evaluate(), so its validation forwards drop too)"""
@@ -480,14 +507,20 @@ class WeakPairedAETrainer(_BodyInLoop):
     and train / eval_split on a WeakPairedImageLoader.  Training cuts a random window per batch (crop_origin_train) and keeps
     drop6 / drop7 live (p = 0.5, the trainer's seed, the iteration as step); eval_split cuts the central window and runs the
     body in evaluate mode, the model as designed.  body_dropout_in_eval=True reproduces the script instead, which never calls
-    cnn:evaluate() and so validates with both dropouts live."""
+    cnn:evaluate() and so validates with both dropouts live.
+
+    finetune_body=True (needs body): from finetune_cnn_after on the body learns too -- nvqa_ae_wp_step_images_finetune, then
+    body.update with the -cnn_optim rule, the decayed cnn rate, cnn_weight_decay and the script's scale 0.01
+    (cnnFinalLearningScales, :194).  The projection's update and the log line's cnn figures (the projection's, :353-354) are
+    unchanged.  The default, False, keeps the projection-only meaning of finetune_cnn_after."""
 
     def __init__(self, dims, device=0, variant="vgg", learning_rate=None, learning_rate_decay_start=-1,
                  learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
                  grad_clip=0.1, drop_prob=0.5, rand_val=0.5, finetune_cnn_after=-1, cnn_optim_alpha=0.8, cnn_optim_beta=0.999,
                  cnn_learning_rate=1e-5, cnn_weight_decay=0.0, seed=123, bf16=False, optim="adam", cnn_optim="adam", body=None,
-                 body_dropout_in_eval=False):
+                 body_dropout_in_eval=False, finetune_body=False):
         self.body, self.body_dropout_in_eval = body, bool(body_dropout_in_eval)
+        self._init_finetune_body(finetune_body)
         if optim not in binding.OPT_RULES:
             raise ValueError("optim: rmsprop | adagrad | sgd | sgdm | sgdmom | adam (misc/optim_updates.lua)")
         if cnn_optim not in binding.CNN_OPT_RULES:
@@ -562,11 +595,15 @@ class WeakPairedAETrainer(_BodyInLoop):
         dr = binding.Dropout(1 if self.drop_prob > 0 else 0, self.drop_prob, self.seed, self.iter)
         if images_u8 is not None:
             xoff, yoff, bdr = self._body_train(images_u8)
+            body_learns = self.finetune_body and self.finetuning()
             loss = self.ctx.ae_wp_step_images(self.body, images_u8, xoff, yoff, tokens, enc_tokens=None if null else tokens,
-                                              body_dropout=bdr, dropout=dr)
+                                              body_dropout=bdr, dropout=dr, **({"finetune": True} if body_learns else {}))
         else:
+            body_learns = False
             loss = self.ctx.ae_wp_step(feats, tokens, enc_tokens=None if null else tokens, dropout=dr)
         lr, cnn_lr = self.current_lr()
+        if body_learns:
+            self._body_update(cnn_lr, 0.01)
         norm, count = _optim_update(self.ctx, self.optim, lr, self.learning_rate, self.alpha, self.beta, self.eps,
                                     self.weight_decay, self.grad_clip)
         if self.finetuning():
@@ -650,16 +687,29 @@ class WeakPairedAE1Trainer(_BodyInLoop):
 
     body (binding.Vgg16 with feature width I): the frozen body runs inside the step on raw images, as in WeakPairedAETrainer
     (train_step_images; train / eval_split on a WeakPairedImageLoader).  This script switches the body with cnn:training() /
-    cnn:evaluate(), so eval_split's default -- no body dropout -- is also what the script does."""
+    cnn:evaluate(), so eval_split's default -- no body dropout -- is also what the script does.
+
+    finetune_body=True (needs body) with finetune_cnn_after / cnn_optim / cnn_optim_alpha / cnn_optim_beta / cnn_learning_rate /
+    cnn_weight_decay, the script's options: from finetune_cnn_after on the step is nvqa_ae1_wp_step_images_finetune and
+    body.update runs -cnn_optim at the decayed cnn rate with scale 1 (cnnFinalLearningScales is all ones, :182).  The log line
+    then carries the script's two cnn fields, taken from the body (:374-375), and train_step returns them behind the line's
+    other figures.  The default, False, keeps the trainer as it was: none of these options is read."""
 
     def __init__(self, dims, device=0, variant="vgg", learning_rate=3e-5, learning_rate_decay_start=-1,
                  learning_rate_decay_every=50000, optim_alpha=0.8, optim_beta=0.999, optim_epsilon=1e-8, weight_decay=1e-6,
                  grad_clip=0.1, drop_prob=0.5, skip_prob=0.5, seed=123, bf16=False, optim="adam", body=None,
-                 body_dropout_in_eval=False):
+                 body_dropout_in_eval=False, finetune_cnn_after=-1, cnn_optim="adam", cnn_optim_alpha=0.8, cnn_optim_beta=0.999,
+                 cnn_learning_rate=1e-5, cnn_weight_decay=0.0, finetune_body=False):
         self.body, self.body_dropout_in_eval = body, bool(body_dropout_in_eval)
+        self._init_finetune_body(finetune_body)
         if optim not in binding.OPT_RULES:
             raise ValueError("optim: rmsprop | adagrad | sgd | sgdm | sgdmom | adam (misc/optim_updates.lua)")
-        self.optim = optim
+        if cnn_optim not in binding.CNN_OPT_RULES:
+            raise ValueError("cnn_optim: sgd | sgdm | adam")
+        self.optim, self.cnn_optim = optim, cnn_optim
+        self.finetune_cnn_after = finetune_cnn_after
+        self.cnn_alpha, self.cnn_beta = cnn_optim_alpha, cnn_optim_beta
+        self.cnn_learning_rate, self.cnn_weight_decay = cnn_learning_rate, cnn_weight_decay
         if bf16:
             raise ValueError("bf16: the weak-paired auto-encoders have no bf16 operand mode (their step is launch-bound)")
         if dims.arch != binding.ARCH_AE1_WP:
@@ -756,12 +806,16 @@ class WeakPairedAE1Trainer(_BodyInLoop):
             lr *= 0.5 ** ((self.iter - self.decay_start) / self.decay_every)
         return lr
 
+    def finetuning(self):
+        return self.finetune_cnn_after >= 0 and self.iter >= self.finetune_cnn_after
+
     def train_step_images(self, tokens, images_u8):
         """train_step with the body in the loop: images_u8 [B x 3 x S x S] uint8 instead of features"""
         return self.train_step(tokens, None, images_u8=images_u8)
 
     def train_step(self, tokens, feats, images_u8=None):
-        """lossFun + log line + update of one iteration; returns (loss, # updates, paramsNorm, skipped, the log line)."""
+        """lossFun + log line + update of one iteration; returns (loss, # updates, paramsNorm, skipped, the log line); with
+        finetune_body (loss, # updates, paramsNorm, skipped, # cnn updates, cnnParamsNorm, the log line)."""
         skip = self.skip_encoder()
         if skip and self.mean_vector is None:
             raise ValueError("the encoder is skipped in this iteration: set_mean_vector / mean_sentence_vector first")
@@ -769,14 +823,25 @@ class WeakPairedAE1Trainer(_BodyInLoop):
         enc = {"enc_state": np.tile(self.mean_vector, (self.dims.B, 1))} if skip else {"enc_tokens": tokens}
         if images_u8 is not None:
             xoff, yoff, bdr = self._body_train(images_u8)
-            loss = self.ctx.ae1_wp_step_images(self.body, images_u8, xoff, yoff, tokens, body_dropout=bdr, dropout=dr, **enc)
+            body_learns = self.finetune_body and self.finetuning()
+            loss = self.ctx.ae1_wp_step_images(self.body, images_u8, xoff, yoff, tokens, body_dropout=bdr, dropout=dr,
+                                               **({"finetune": True} if body_learns else {}), **enc)
         else:
+            body_learns = False
             loss = self.ctx.ae1_wp_step(feats, tokens, dropout=dr, **enc)
-        norm, count = _optim_update(self.ctx, self.optim, self.current_lr(), self.learning_rate, self.alpha, self.beta, self.eps,
+        lr = self.current_lr()
+        norm, count = _optim_update(self.ctx, self.optim, lr, self.learning_rate, self.alpha, self.beta, self.eps,
                                     self.weight_decay, self.grad_clip)
         line = "iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f" % (self.iter, loss, count, norm)
+        if not self.finetune_body:
+            self.iter += 1
+            return loss, count, norm, skip, line
+        # the cnn rate decays with the AE rate (:465-473)
+        cnn_norm, cnn_count = (self._body_update(self.cnn_learning_rate * lr / self.learning_rate, 1.0) if body_learns
+                               else self._body_stats_frozen())
+        line += " | # cnn updates: %4d | cnnParamsNorm: %.4f" % (cnn_count, cnn_norm)
         self.iter += 1
-        return loss, count, norm, skip, line
+        return loss, count, norm, skip, cnn_count, cnn_norm, line
 
     def train(self, loader, iters, log=print):
         losses = []

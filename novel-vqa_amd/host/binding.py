@@ -96,6 +96,13 @@ SYMBOLS = {
     "nvqa_vgg16_set_precision": (ctypes.c_int, [_vp, ctypes.c_int]),
     "nvqa_vgg16_preprocess": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p]),
     "nvqa_vgg16_fc7_raw": (ctypes.c_int, [_vp, _u8p] + [ctypes.c_int] * 4 + [ctypes.POINTER(Dropout), _f32p]),
+    "nvqa_vgg16_train_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "nvqa_vgg16_train_forward_raw": (ctypes.c_int, [_vp, _u8p] + [ctypes.c_int] * 4 + [ctypes.POINTER(Dropout), _f32p]),
+    "nvqa_vgg16_train_activation": (ctypes.c_int, [_vp, ctypes.c_int, _f32p]),
+    "nvqa_vgg16_backward": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_int]),
+    "nvqa_vgg16_get_grads": (ctypes.c_int, [_vp, _f32p]),
+    "nvqa_vgg16_get_weights": (ctypes.c_int, [_vp, _f32p]),
+    "nvqa_vgg16_update": (ctypes.c_int, [_vp, ctypes.c_int] + [ctypes.c_float] * 7 + [_f32p]),
     "nvqa_step_images": (ctypes.c_int, [_vp, _vp, _f32p, _i32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_step": (ctypes.c_int, [_vp, _i32p, ctypes.POINTER(Dropout), _f32p]),
     "nvqa_ae_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _i32p]),
@@ -112,6 +119,11 @@ SYMBOLS = {
     "nvqa_adam_update": (ctypes.c_int, [_vp] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_optim_update": (ctypes.c_int, [_vp, ctypes.c_int] + [ctypes.c_float] * 6 + [_f32p]),
     "nvqa_ae_wp_step": (ctypes.c_int, [_vp, _f32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p]),
+    "nvqa_ae_wp_step_dfeats": (ctypes.c_int, [_vp, _f32p, _i32p, _i32p, ctypes.POINTER(Dropout), _f32p, _f32p]),
+    "nvqa_ae_wp_step_images_finetune": (ctypes.c_int, [_vp, _vp, _u8p] + [ctypes.c_int] * 3 + [ctypes.POINTER(Dropout), _i32p, _i32p,
+                                                       ctypes.POINTER(Dropout), _f32p]),
+    "nvqa_ae1_wp_step_images_finetune": (ctypes.c_int, [_vp, _vp, _u8p] + [ctypes.c_int] * 3 + [ctypes.POINTER(Dropout), _i32p, _f32p, _i32p,
+                                                        ctypes.POINTER(Dropout), _f32p, _f32p]),
     "nvqa_ae_wp_evaluate": (ctypes.c_int, [_vp, ctypes.c_int32, _f32p, _i32p, _i32p, _f32p, _i32p]),
     "nvqa_ae_wp_set_projection": (ctypes.c_int, [_vp, _f32p, _f32p]),
     "nvqa_ae_wp_get_projection": (ctypes.c_int, [_vp, _f32p, _f32p]),
@@ -433,15 +445,21 @@ class Context:
         return (float(out[0]), int(out[1])) if stats else None
 
     # ---- weak-paired auto-encoder (arch ARCH_AE2_WP) --------------------------------
-    def ae_wp_step(self, feats, tokens, enc_tokens=None, dropout=None, want_loss=True):
+    def ae_wp_step(self, feats, tokens, enc_tokens=None, dropout=None, want_loss=True, want_dfeats=False):
         """nvqa_ae_wp_step: feats [B x I] (the frozen CNN body's output; the library L2-normalises its copy), tokens [B x D]
-        for the decoder and criterion, enc_tokens [B x D] for the encoder (None = the null sentence)."""
+        for the decoder and criterion, enc_tokens [B x D] for the encoder (None = the null sentence).  want_dfeats:
+        nvqa_ae_wp_step_dfeats, returning (loss, d(loss)/d(f^) [B x I])."""
         d = self.dims
         f = np.ascontiguousarray(feats, np.float32).reshape(d.B, d.I)
         tok = np.ascontiguousarray(tokens, np.int32).reshape(d.B, d.T)
         et = None if enc_tokens is None else np.ascontiguousarray(enc_tokens, np.int32).reshape(d.B, d.T)
         loss = ctypes.c_float(0)
         dr = ctypes.byref(dropout) if dropout is not None else None
+        if want_dfeats:
+            df = np.empty((d.B, d.I), np.float32)
+            self._check(self.lib.nvqa_ae_wp_step_dfeats(self._h, _f32(f), _i32(et), _i32(tok), dr,
+                                                        ctypes.byref(loss) if want_loss else None, _f32(df)))
+            return (float(loss.value) if want_loss else None), df
         self._check(self.lib.nvqa_ae_wp_step(self._h, _f32(f), _i32(et), _i32(tok), dr, ctypes.byref(loss) if want_loss else None))
         return float(loss.value) if want_loss else None
 
@@ -542,7 +560,7 @@ class Context:
 
     # ---- the weak-paired steps with the VGG-16 body in the loop -----------------------
     def ae_wp_step_images(self, vgg, images_u8, xoff, yoff, tokens, enc_tokens=None, body_dropout=None, dropout=None,
-                          want_loss=True):
+                          want_loss=True, finetune=False):
         """nvqa_ae_wp_step_images: ae_wp_step fed by the extractor `vgg` (Vgg16) on images_u8 [B x 3 x S x S] uint8, window
         origin (xoff, yoff), body_dropout (Dropout or None: drop6 / drop7 off).  The features stay on the device; with
         want_loss=False the call only enqueues."""
@@ -553,8 +571,12 @@ class Context:
         loss = ctypes.c_float(0)
         bdr = ctypes.byref(body_dropout) if body_dropout is not None else None
         dr = ctypes.byref(dropout) if dropout is not None else None
-        self._check(self.lib.nvqa_ae_wp_step_images(self._h, vgg._h, _u8(x), S, int(xoff), int(yoff), bdr, _i32(et), _i32(tok), dr,
+        # finetune: nvqa_ae_wp_step_images_finetune -- a training-enabled extractor also gets its gradients (vgg.get_grads)
+        fn = self.lib.nvqa_ae_wp_step_images_finetune if finetune else self.lib.nvqa_ae_wp_step_images
+        self._check(fn(self._h, vgg._h, _u8(x), S, int(xoff), int(yoff), bdr, _i32(et), _i32(tok), dr,
                                                     ctypes.byref(loss) if want_loss else None))
+        if finetune:
+            vgg._train_n = d.B
         return float(loss.value) if want_loss else None
 
     def ae_wp_evaluate_images(self, vgg, images_u8, xoff, yoff, tokens, enc_tokens=None, body_dropout=None, samples=False):
@@ -572,7 +594,7 @@ class Context:
         return float(loss.value), out
 
     def ae1_wp_step_images(self, vgg, images_u8, xoff, yoff, tokens, enc_tokens=None, enc_state=None, body_dropout=None,
-                           dropout=None, want_loss=True, want_dfeats=False):
+                           dropout=None, want_loss=True, want_dfeats=False, finetune=False):
         """nvqa_ae1_wp_step_images: ae1_wp_step fed by the extractor; returns as ae1_wp_step does (dfeats = d(loss)/d(f^))."""
         d = self.dims
         x, S = _images_u8(images_u8, d.B)
@@ -583,8 +605,11 @@ class Context:
         loss = ctypes.c_float(0)
         bdr = ctypes.byref(body_dropout) if body_dropout is not None else None
         dr = ctypes.byref(dropout) if dropout is not None else None
-        self._check(self.lib.nvqa_ae1_wp_step_images(self._h, vgg._h, _u8(x), S, int(xoff), int(yoff), bdr, _i32(et), _f32(es),
-                                                     _i32(tok), dr, ctypes.byref(loss) if want_loss else None, _f32(df)))
+        fn = self.lib.nvqa_ae1_wp_step_images_finetune if finetune else self.lib.nvqa_ae1_wp_step_images
+        self._check(fn(self._h, vgg._h, _u8(x), S, int(xoff), int(yoff), bdr, _i32(et), _f32(es),
+                       _i32(tok), dr, ctypes.byref(loss) if want_loss else None, _f32(df)))
+        if finetune:
+            vgg._train_n = d.B
         out = float(loss.value) if want_loss else None
         return (out, df) if want_dfeats else out
 
@@ -700,6 +725,7 @@ class Vgg16:
         self.lib = load_library()
         self._h = _vp()
         self.hw = input_hw
+        self.width_div = width_div
         self._check(self.lib.nvqa_vgg16_create(device, width_div, input_hw, max_batch, ctypes.byref(self._h)))
         self.weight_count = int(self.lib.nvqa_vgg16_weight_count(self._h))
         self.feature_dim = int(self.lib.nvqa_vgg16_feature_dim(self._h))
@@ -734,6 +760,67 @@ class Vgg16:
         dr = ctypes.byref(dropout) if dropout is not None else None
         self._check(self.lib.nvqa_vgg16_fc7_raw(self._h, _u8(x), n, S, int(xoff), int(yoff), dr, _f32(out)))
         return out
+
+    # ---- fine-tuning (f32 body only) ----
+    def train_enable(self, on=True):
+        """allocate (True) or free (False) the training state: saved activations, gradients, W', workspace"""
+        self._check(self.lib.nvqa_vgg16_train_enable(self._h, int(bool(on))))
+        if not on:
+            self._train_n = 0  # the saved activations went with the state
+
+    def train_forward_raw(self, images_u8, xoff, yoff, dropout=None, want_feats=True):
+        """fc7_raw's arguments and bits, every layer's output kept for backward(); returns the features, or None"""
+        x, S = _images_u8(images_u8)
+        n = x.shape[0]
+        out = np.empty((n, self.feature_dim), np.float32) if want_feats else None
+        dr = ctypes.byref(dropout) if dropout is not None else None
+        self._check(self.lib.nvqa_vgg16_train_forward_raw(self._h, _u8(x), n, S, int(xoff), int(yoff), dr,
+                                                          _f32(out) if want_feats else None))
+        self._train_n = n
+        return out
+
+    def conv_shape(self, which):
+        """(channels, height) of convolution `which`'s output (0..12); the two tables follow kConvCout / kPoolAfter of
+        csrc/vgg.hip (the ABI has no call that returns a layer's shape)"""
+        cout = [64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512]
+        pools = [0, 1, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 1]
+        return max(1, cout[which] // self.width_div), self.hw >> sum(pools[:which])
+
+    def train_activation(self, which):
+        """saved output of layer 0..12 (convolution, post-ReLU, NCHW), 13 (fc6), 14 (fc7) of the last training forward"""
+        n = getattr(self, "_train_n", 0)
+        if not n:
+            raise NvqaError("train_activation before train_forward_raw")
+        if which >= 13:
+            out = np.empty((n, self.feature_dim), np.float32)
+        else:
+            c, h = self.conv_shape(which)
+            out = np.empty((n, c, h, h), np.float32)
+        self._check(self.lib.nvqa_vgg16_train_activation(self._h, int(which), _f32(out)))
+        return out
+
+    def backward(self, dfeats, through_l2norm=False):
+        """d(loss)/d(features) [n x F] (through_l2norm: d/d(f^) of the row-normalised features) -> the body's gradients"""
+        d = np.ascontiguousarray(dfeats, np.float32)
+        assert d.ndim == 2 and d.shape[1] == self.feature_dim
+        self._check(self.lib.nvqa_vgg16_backward(self._h, _f32(d), d.shape[0], int(bool(through_l2norm))))
+
+    def get_grads(self):
+        out = np.empty(self.weight_count, np.float32)
+        self._check(self.lib.nvqa_vgg16_get_grads(self._h, _f32(out)))
+        return out
+
+    def get_weights(self):
+        out = np.empty(self.weight_count, np.float32)
+        self._check(self.lib.nvqa_vgg16_get_weights(self._h, _f32(out)))
+        return out
+
+    def update(self, rule, lr, alpha=0.9, beta=0.999, eps=1e-8, wd=0.0, clamp=0.0, scale=1.0, want_stats=True):
+        """one -cnn_optim update (OPT_SGD / OPT_SGDM / OPT_ADAM) of every weight of the body; returns (|x|, updates >= 1%)"""
+        st = np.zeros(2, np.float32)
+        self._check(self.lib.nvqa_vgg16_update(self._h, int(rule), lr, alpha, beta, eps, wd, clamp, scale,
+                                               _f32(st) if want_stats else None))
+        return (float(st[0]), float(st[1])) if want_stats else None
 
     def preprocess(self, rgb):
         x = np.ascontiguousarray(rgb, np.float32)

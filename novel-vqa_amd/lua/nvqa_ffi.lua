@@ -59,6 +59,15 @@ int nvqa_vgg16_set_precision(nvqa_vgg *vgg, int bf16);
 int nvqa_vgg16_preprocess(nvqa_vgg *vgg, const float *rgb, int n, int H, int W, float *out);
 int nvqa_vgg16_fc7_raw(nvqa_vgg *vgg, const uint8_t *images, int n, int S, int xoff, int yoff,
                        const nvqa_dropout *body_dropout, float *feats_out);
+int nvqa_vgg16_train_enable(nvqa_vgg *vgg, int on);
+int nvqa_vgg16_train_forward_raw(nvqa_vgg *vgg, const uint8_t *images, int n, int S, int xoff, int yoff,
+                                 const nvqa_dropout *dropout, float *feats_out);
+int nvqa_vgg16_train_activation(nvqa_vgg *vgg, int which, float *out);
+int nvqa_vgg16_backward(nvqa_vgg *vgg, const float *dfeats, int n, int through_l2norm);
+int nvqa_vgg16_get_grads(nvqa_vgg *vgg, float *flat_out);
+int nvqa_vgg16_get_weights(nvqa_vgg *vgg, float *flat_out);
+int nvqa_vgg16_update(nvqa_vgg *vgg, int rule, float lr, float alpha, float beta, float eps, float wd, float clamp,
+                      float scale, float stats_out[2]);
 int nvqa_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const float *images, const int32_t *tokens,
                      const int32_t *lengths, const int32_t *labels, const nvqa_dropout *dropout, float *loss_out);
 int nvqa_ae_step(nvqa_ctx *ctx, const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out);
@@ -111,6 +120,14 @@ int nvqa_ae1_wp_step_images(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_
 int nvqa_ae1_wp_evaluate_images(nvqa_ctx *ctx, nvqa_vgg *vgg, int32_t n, const uint8_t *images_u8, int S, int xoff, int yoff,
                                 const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
                                 float *loss_out, int32_t *samples_out);
+int nvqa_ae_wp_step_dfeats(nvqa_ctx *ctx, const float *feats, const int32_t *enc_tokens, const int32_t *tokens,
+                           const nvqa_dropout *dropout, float *loss_out, float *dfeats_out);
+int nvqa_ae_wp_step_images_finetune(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                    const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const int32_t *tokens,
+                                    const nvqa_dropout *dropout, float *loss_out);
+int nvqa_ae1_wp_step_images_finetune(nvqa_ctx *ctx, nvqa_vgg *vgg, const uint8_t *images_u8, int S, int xoff, int yoff,
+                                     const nvqa_dropout *body_dropout, const int32_t *enc_tokens, const float *enc_state,
+                                     const int32_t *tokens, const nvqa_dropout *dropout, float *loss_out, float *dfeats_out);
 int nvqa_profile_enable(nvqa_ctx *ctx, int enable);
 int nvqa_profile_reset(nvqa_ctx *ctx);
 int nvqa_profile_count(const nvqa_ctx *ctx);

@@ -50,6 +50,13 @@ cmd:option('-optim','adam','what update to use? rmsprop|adagrad|sgd|sgdm|sgdmom|
 cmd:option('-learning_rate',3e-5,'learning rate')
 cmd:option('-learning_rate_decay_start', -1, 'at what iteration to start decaying learning rate? (-1 = dont)')
 cmd:option('-learning_rate_decay_every', 50000, 'every how many iterations thereafter to drop LR by half?')
+cmd:option('-finetune_body', 0, '1: from -finetune_cnn_after on the VGG-16 body learns too (-body_in_loop 1): its backward inside the step, -cnn_optim on all its weights')
+cmd:option('-finetune_cnn_after', -1, 'After what iteration do we start finetuning the CNN body? (-1 = never; read with -finetune_body 1)')
+cmd:option('-cnn_optim','adam','optimization to use for the CNN body: sgd|sgdm|adam')
+cmd:option('-cnn_optim_alpha',0.8,'alpha for momentum / adam of the CNN body')
+cmd:option('-cnn_optim_beta',0.999,'beta for adam of the CNN body')
+cmd:option('-cnn_learning_rate',1e-5,'learning rate for the CNN body')
+cmd:option('-cnn_weight_decay', 0, 'L2 weight decay just for the CNN body')
 cmd:option('-optim_alpha',0.8,'alpha for adagrad/rmsprop/momentum/adam')
 cmd:option('-optim_beta',0.999,'beta used for adam')
 cmd:option('-optim_epsilon',1e-8,'epsilon that goes into denominator for smoothing')
@@ -78,6 +85,7 @@ if opt.body_in_loop == 1 then                        -- the reference's stage: r
   images = {train = h5i:read('/images/train'), val = h5i:read('/images/val')}
   img_size = images.train:dataspaceSize()[3]
   body = nvqa.body_open(opt)
+  if opt.finetune_body == 1 then nvqa.check(nvqa.lib.nvqa_vgg16_train_enable(body, 1)) end
 else
   h5 = hdf5.open(opt.input_feats_h5, 'r')
   feats = {train = h5:read('/feats/train'):all():float(), val = h5:read('/feats/val'):all():float()}
@@ -197,7 +205,7 @@ end
 
 -- main loop (:359-420) ------------------------------------------------------------------------------------------------
 local iter, loss0, best_score = 1, nil, nil
-local loss, stats = ffi.new('float[1]'), ffi.new('float[2]')
+local loss, stats, cnn_stats = ffi.new('float[1]'), ffi.new('float[2]'), ffi.new('float[2]')
 local checkpoint_path = paths.concat(opt.checkpoint_path, 'model_id' .. opt.id)
 while true do
   local batch, fb = getBatch('train', opt.batch_size)
@@ -205,7 +213,13 @@ while true do
   local skip = torch.uniform() <= 0.5                                              -- encoder_skip_flag = 1 (:299-301)
   local enc_tokens, enc_state = nvqa.iptr(batch), nil
   if skip then enc_tokens, enc_state = nil, nvqa.fptr(mean_rows) end
-  if body then                                                                     -- prepro(data.images, true, ...) + cnn:forward
+  local body_learns = body ~= nil and opt.finetune_body == 1 and opt.finetune_cnn_after >= 0 and iter >= opt.finetune_cnn_after
+  if body_learns then                                                              -- ... + cnn:backward(data.imgs, dfeats) (:329)
+    local xoff, yoff = nvqa.crop_origin(img_size, true)
+    nvqa.check(nvqa.lib.nvqa_ae1_wp_step_images_finetune(ctx, body, nvqa.bptr(fb), img_size, xoff, yoff,
+                                                         nvqa.body_dropout(true, opt.seed, iter), enc_tokens, enc_state,
+                                                         nvqa.iptr(batch), dr, loss, nil))
+  elseif body then                                                                 -- prepro(data.images, true, ...) + cnn:forward
     local xoff, yoff = nvqa.crop_origin(img_size, true)
     nvqa.check(nvqa.lib.nvqa_ae1_wp_step_images(ctx, body, nvqa.bptr(fb), img_size, xoff, yoff,
                                                 nvqa.body_dropout(true, opt.seed, iter), enc_tokens, enc_state, nvqa.iptr(batch),
@@ -223,7 +237,18 @@ while true do
   else
     nvqa.optim_update(ctx, opt, learning_rate, stats)
   end
-  print(string.format('iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f', iter, loss[0], stats[1], stats[0]))
+  if body_learns then                                                              -- the cnn vector, scales all 1 (:182, :477-484)
+    local clamp = 0
+    if opt.cnn_weight_decay > 0 then clamp = opt.grad_clip end
+    local cnn_rule = nvqa.CNN_OPT[opt.cnn_optim]
+    if cnn_rule == nil then error('bad option for opt.cnn_optim (sgd | sgdm | adam)') end
+    nvqa.check(nvqa.lib.nvqa_vgg16_update(body, cnn_rule, opt.cnn_learning_rate * learning_rate / opt.learning_rate, opt.cnn_optim_alpha,
+                                          opt.cnn_optim_beta, opt.optim_epsilon, opt.cnn_weight_decay, clamp, 1, cnn_stats))
+    print(string.format('iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f | # cnn updates: %4d | cnnParamsNorm: %.4f',
+                        iter, loss[0], stats[1], stats[0], cnn_stats[1], cnn_stats[0]))
+  else
+    print(string.format('iter %d: loss: %.3f | # updates: %4d | paramsNorm: %.4f', iter, loss[0], stats[1], stats[0]))
+  end
   if iter % opt.save_checkpoint_every == 0 or iter == opt.max_iters then
     local val_loss = eval_split('val')
     print('validation loss: ', val_loss)

@@ -35,6 +35,7 @@ cmd:option('-input_json','data/data.json','path to the json file containing addi
 cmd:option('-start_from_text', '', 'flat-vector table of the arch2 text auto-encoder (AETrainer.export_params)')
 cmd:option('-body_in_loop', 0, '1: run the VGG-16 body inside the step on the raw images /images/<split> of -input_h5 (needs -cnn_weights)')
 cmd:option('-cnn_weights', '', 'flat float32 file of the VGG-16 weights in nvqa_vgg16_set_weights order (-body_in_loop 1)')
+cmd:option('-finetune_body', 0, '1: from -finetune_cnn_after on the VGG-16 body learns too (-body_in_loop 1): its backward inside the step, -cnn_optim on all its weights at scale 0.01')
 cmd:option('-body_dropout_in_eval', 0, '1: drop6 / drop7 stay live in eval_split, as in the reference script (-body_in_loop 1)')
 cmd:option('-rnn_size',512,'size of the rnn in number of hidden nodes in each layer')
 cmd:option('-input_encoding_size',512,'the encoding size of each token in the vocabulary, and the image.')
@@ -82,7 +83,9 @@ if opt.body_in_loop == 1 then                        -- the reference's stage: r
   images = {train = h5i:read('/images/train'), val = h5i:read('/images/val')}
   img_size = images.train:dataspaceSize()[3]
   body = nvqa.body_open(opt)
+  if opt.finetune_body == 1 then nvqa.check(nvqa.lib.nvqa_vgg16_train_enable(body, 1)) end
 else
+  assert(opt.finetune_body ~= 1, '-finetune_body 1 needs -body_in_loop 1')
   h5 = hdf5.open(opt.input_feats_h5, 'r')
   feats = {train = h5:read('/feats/train'):all():float(), val = h5:read('/feats/val'):all():float()}
   h5:close()
@@ -177,7 +180,13 @@ while true do
   local batch, fb = getBatch('train', opt.batch_size)
   local enc = batch
   if torch.uniform() <= opt.rand_val then enc = nil end                          -- the null sentence (:289-295)
-  if body then                                                                   -- prepro(data.images, true, ...) + cnn:forward
+  local body_learns = opt.finetune_body == 1 and opt.finetune_cnn_after >= 0 and iter >= opt.finetune_cnn_after
+  if body_learns then                                                            -- ... + cnn:backward(data.imgs, dfeats) (:307-310)
+    local xoff, yoff = nvqa.crop_origin(img_size, true)
+    nvqa.check(nvqa.lib.nvqa_ae_wp_step_images_finetune(ctx, body, nvqa.bptr(fb), img_size, xoff, yoff,
+                                                        nvqa.body_dropout(true, opt.seed, iter), enc and nvqa.iptr(enc) or nil,
+                                                        nvqa.iptr(batch), nvqa.dropout(1, opt.drop_prob_ae, opt.seed, iter), loss))
+  elseif body then                                                               -- prepro(data.images, true, ...) + cnn:forward
     local xoff, yoff = nvqa.crop_origin(img_size, true)
     nvqa.check(nvqa.lib.nvqa_ae_wp_step_images(ctx, body, nvqa.bptr(fb), img_size, xoff, yoff,
                                                nvqa.body_dropout(true, opt.seed, iter), enc and nvqa.iptr(enc) or nil,
@@ -211,6 +220,10 @@ while true do
                                                        opt.optim_epsilon, opt.cnn_weight_decay, clamp, cnn_stats))
     end
     frozen_stats = nil
+    if body_learns then                                                          -- the whole cnn vector, cnnFinalLearningScales 0.01 (:194, :457-466)
+      nvqa.check(nvqa.lib.nvqa_vgg16_update(body, cnn_rule, cnn_learning_rate, opt.cnn_optim_alpha, opt.cnn_optim_beta,
+                                            opt.optim_epsilon, opt.cnn_weight_decay, clamp, 0.01, nil))
+    end
   else
     if frozen_stats == nil then                                                  -- a zero gradient: the zero entries count
       local w = torch.FloatTensor(E * I + E)

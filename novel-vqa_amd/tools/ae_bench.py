@@ -34,8 +34,14 @@ features stay on the device), "composed" = nvqa_vgg16_fc7_raw to the host and th
 compute the same bits per step and end every step with nvqa_adam_update; a block is timed around a final synchronise.  The
 line carries both arms' ms per step (median over blocks), their block times and spreads and the ratio.
 
+--finetune (--arch 5 | 6): the same shape with the body fine-tuning, in two arms that alternate block by
+block: "frozen" = nvqa_ae*_wp_step_images + nvqa_adam_update, "finetune" = nvqa_ae*_wp_step_images_finetune + nvqa_adam_update
++ nvqa_vgg16_update (adam, scale 0.01 for arch 5 and 1 for arch 6) on a training-enabled extractor of their own each.  A block
+ends with both streams drained (the last update of a block returns its statistics).  The line carries both arms' ms per step,
+block times and spreads, and finetune_over_frozen.
+
     python novel-vqa_amd/tools/ae_bench.py [--arch 1|2|5|6] [--bf16] [--I 4096 --null-share 0.5] [--world N] [--resident] [--optim RULE]
-                                           [--images [--S 256 --body-div 1 --body-hw 224]]
+                                           [--images | --finetune [--S 256 --body-div 1 --body-hw 224]]
                                            [--blocks 5 --steps 10 --warmup 5] [--out FILE]
 """
 import argparse
@@ -117,10 +123,14 @@ def images_main(a, pkg):
         batches.append(tok)
         images.append(rng.integers(0, 256, (B, 3, a.S, a.S), dtype=np.uint8))
     null = np.random.default_rng(1).random(4096) < a.null_share
-    arms = {"in_loop": make_ctx(), "composed": make_ctx()}
+    arms = {"frozen": make_ctx(), "finetune": make_ctx()} if a.finetune else {"in_loop": make_ctx(), "composed": make_ctx()}
     its = {k: 0 for k in arms}
+    if a.finetune:  # the fine-tuning arm moves its body: one extractor per arm
+        tuned = b.Vgg16(0, a.body_div, a.body_hw, max_batch=B)
+        tuned.set_weights(vgg.get_weights())
+        tuned.train_enable(True)
 
-    def one_step(arm, want_loss=False):
+    def one_step(arm, want_loss=False, last=False):
         its[arm] += 1
         it = its[arm]
         ctx, k = arms[arm], it % len(batches)
@@ -131,9 +141,15 @@ def images_main(a, pkg):
             enc = {"enc_tokens": None if skip else batches[k]}
         else:
             enc = {"enc_state": enc_state} if skip else {"enc_tokens": batches[k]}
-        if arm == "in_loop":
+        if arm in ("in_loop", "frozen"):
             step = ctx.ae_wp_step_images if a.arch == 5 else ctx.ae1_wp_step_images
             loss = step(vgg, images[k], xoff, yoff, batches[k], body_dropout=bdr, dropout=dr, want_loss=want_loss, **enc)
+        elif arm == "finetune":
+            step = ctx.ae_wp_step_images if a.arch == 5 else ctx.ae1_wp_step_images
+            loss = step(tuned, images[k], xoff, yoff, batches[k], body_dropout=bdr, dropout=dr, want_loss=want_loss, finetune=True, **enc)
+            ctx.adam_update(lr, 0.8, 0.999, 1e-8, 1e-6, 0.1)
+            tuned.update(b.OPT_ADAM, 1e-5, 0.8, 0.999, 1e-8, 0.0, 0.0, 0.01 if a.arch == 5 else 1.0, want_stats=last)  # last: drains the body's stream
+            return loss
         else:
             feats = vgg.fc7_raw(images[k], xoff, yoff, dropout=bdr)  # to the host and back
             step = ctx.ae_wp_step if a.arch == 5 else ctx.ae1_wp_step
@@ -143,8 +159,8 @@ def images_main(a, pkg):
 
     def timed_block(arm):
         t0 = time.perf_counter()
-        for _ in range(a.steps):
-            one_step(arm)
+        for i in range(a.steps):
+            one_step(arm, last=i == a.steps - 1)
         arms[arm].sync()
         return (time.perf_counter() - t0) * 1e3 / a.steps
 
@@ -156,12 +172,29 @@ def images_main(a, pkg):
     for _ in range(a.blocks):
         for arm in arms:
             blocks[arm].append(timed_block(arm))
-    # both arms have run the same steps: the next one must give the same loss, bit for bit
-    losses = {arm: one_step(arm, want_loss=True) for arm in arms}
+    # both arms have run the same steps: the next one must give the same loss, bit for bit (--finetune: the bodies differ by now)
+    losses = {arm: one_step(arm, want_loss=True, last=True) for arm in arms}
     for c in arms.values():
         c.close()
     vgg.close()
     med = {k: float(np.median(v)) for k, v in blocks.items()}
+    if a.finetune:
+        tuned.close()
+        line = {"workload": "ae_arch%d_weakpaired_finetune" % a.arch, "B": B, "S": a.S, "body_div": a.body_div, "body_hw": a.body_hw,
+                "I": I, "D": a.D, "V": a.V, "E": a.E, "R": a.R, "L": a.L, "null_share": a.null_share, "blocks": a.blocks,
+                "steps_per_block": a.steps, "warmup": a.warmup, "order": list(arms), "loss_frozen": losses["frozen"],
+                "loss_finetune": losses["finetune"]}
+        for k in arms:
+            line["ms_per_step_" + k] = round(med[k], 4)
+            line["block_ms_" + k] = [round(x, 4) for x in blocks[k]]
+            line["block_spread_pct_" + k] = round(100.0 * (max(blocks[k]) - min(blocks[k])) / med[k], 2)
+        line["finetune_over_frozen"] = round(med["finetune"] / med["frozen"], 4)
+        s = json.dumps(line)
+        print(s)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(s + "\n")
+        return
     line = {"workload": "ae_arch%d_weakpaired_images" % a.arch, "B": B, "S": a.S, "body_div": a.body_div, "body_hw": a.body_hw,
             "I": I, "D": a.D, "V": a.V, "E": a.E, "R": a.R, "L": a.L, "null_share": a.null_share,
             "blocks": a.blocks, "steps_per_block": a.steps, "warmup": a.warmup, "order": list(arms),
@@ -199,12 +232,13 @@ def main():
     ap.add_argument("--resident", action="store_true")
     ap.add_argument("--optim", default="adam", choices=("rmsprop", "adagrad", "sgd", "sgdm", "sgdmom", "adam"))
     ap.add_argument("--images", action="store_true")
+    ap.add_argument("--finetune", action="store_true")
     ap.add_argument("--S", type=int, default=256)
     ap.add_argument("--body-div", type=int, default=1)
     ap.add_argument("--body-hw", type=int, default=224)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.images:
+    if a.images or a.finetune:
         if a.arch not in (5, 6) or a.world > 1 or a.resident or a.bf16 or a.optim != "adam":
             ap.error("--images: the body in the loop is for --arch 5 | 6 alone")
         return images_main(a, ge.load_package())
