@@ -921,11 +921,8 @@ static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb,
     const int kslice = ((K + Z - 1) / Z + kq - 1) / kq * kq;
     Z = (K + kslice - 1) / kslice;
     if (a.bf16) {
-        const WgradBf16Args g{A, Bm, A16, B16, Z > 1 ? a.slabs : out, Z > 1 ? (size_t)M * N : 0, lda, ldb, N, M, N, K, kslice};
-        const dim3 grid((M + NVQA_WB_BM - 1) / NVQA_WB_BM, (N + NVQA_WB_BN - 1) / NVQA_WB_BN, Z);
-        if (A16 && B16) hipLaunchKernelGGL((k_wgrad_bf16<true, true>), grid, dim3(256), NVQA_WB_LDS_BYTES, c->s, g);
-        else hipLaunchKernelGGL((k_wgrad_bf16<false, false>), grid, dim3(256), NVQA_WB_LDS_BYTES, c->s, g);
-        NVQA_HIP(hipGetLastError());
+        if (!A16 || !B16) A16 = B16 = nullptr; // both images or neither
+        NVQA_HIP(wgrad_bf16_launch(c->s, WgradBf16Args{A, Bm, A16, B16, Z > 1 ? a.slabs : out, Z > 1 ? (size_t)M * N : 0, lda, ldb, N, M, N, K, kslice}));
     } else {
         GemmArgs g = ae_args(A, lda, Bm, ldb, M, N, K, kslice);
         const EpiStore e{Z > 1 ? a.slabs : out, N, (size_t)M * N};
@@ -2029,8 +2026,6 @@ extern "C" int nvqa_ae_set_precision(nvqa_ctx *c, int bf16)
     AeState &a = *c->ae;
     if (bf16) {
         NVQA_HIP(hipSetDevice(c->device));
-        NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_bf16<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES));
-        NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_bf16<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES));
         if (c->d.R % 8 == 0 && !a.G16) { // the images of the projection group, on first use: an f32-only context never holds them
             const size_t B = c->d.B, R = c->d.R, Vp1 = (size_t)c->d.V + 1, rows = ((size_t)a.D + 1) * B;
             a.ld16 = (int)((Vp1 + 7) / 8 * 8);

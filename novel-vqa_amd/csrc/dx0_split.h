@@ -5,10 +5,10 @@
 //                                      a column are 64 contiguous bytes and one K step of all columns is one contiguous run
 //                                      (with plain [N][K] rows a K step would use half of every 128-byte line it fetches,
 //                                      and the L2 -> CU path, not the matrix pipe, would set the pace)
-// The split is wgrad_split.h's: hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), round to nearest even; of the
-// nine piece products the six that matter go through v_mfma_f32_16x16x32_bf16 into the SAME f32 accumulator.
-// DEFINITION (bit-reproducible results): K runs in ascending steps of 32; within a step the terms of an accumulator are
-//     lo hi, mid mid, hi lo, mid hi, hi mid, hi hi            (piece of A  x  piece of W, smallest first)
+// The three-way split of an f32 value and the six terms that matter are kmajor_bf16.h's; they go through
+// v_mfma_f32_16x16x32_bf16 into the SAME f32 accumulator.
+// DEFINITION (bit-reproducible results): K runs in ascending steps of 32; within a step the terms of an accumulator come in
+// the order of WB_TERM_A / WB_TERM_B (piece of A  x  piece of W, smallest first).
 // There is no split-K and there are no slabs: every accumulator sees this one fixed sequence whatever the grid is.
 //
 // Why this product suits the form better than the weight gradients do:
@@ -21,19 +21,14 @@
 //     embedding launch) and the kernel does no split work for B at all.
 // Workgroup = 256 threads = 4 waves = 64 rows (13 312 rows: 208 workgroups, one round on 256 CUs) x one column block of
 // NT column tiles (NT = 13: N <= 208; NT = 16: N <= 256, or two column blocks for N <= 512).
-// B path (template flag DIRECT):
-//   false  the three images of the step's 32 k x 16 NT columns are staged through LDS: global -> registers (one whole K
-//          step ahead) -> LDS buffer (s + 1) & 1 during step s, ONE barrier per K step.  Rows of 64 bytes (32 k), the 16-byte
-//          chunk c of column n at 64 n + 16 (c ^ f((n >> 2) & 3)), f = 0, 2, 3, 1: conflict-free for the ds_read_b128
-//          fragment read (its lane groups mix lh and lh + 1: MI355X LDS table) and for the contiguous ds_write_b128.
-//          Per wave and K step: 6 NT MFMAs (NT = 13: 1248 matrix-pipe cycles), 3 NT ds_read_b128 (4 waves: half the LDS
-//          array's cycles), ~60 VALU instructions of split.
-//   true   every wave reads its B fragments from the (L2-resident) images itself: no LDS, no barrier, 4 x the L2 reads.
-//          Measured slower (MI355X, the checker's --time mode, profiles/dx0_split_ab.json; us per launch, first pass behind an
-//          evicting memset / steady state): 13312 x 200 x 2048  LDS 89 / 72-82, direct 267 / 168-183 (the f32 MFMA GEMM it
-//          replaces: 130 / 127-139); 14336 x 512 x 2048  LDS 178 / 162-179, direct 389 / 367-402 (f32 GEMM 260 / 259-284).
-//          The library launches the LDS form only; the direct form stays for that measurement and as a second
-//          implementation that the checker holds to the same bits.
+// B path: the three images of the step's 32 k x 16 NT columns are staged through LDS: global -> registers (one whole K
+//   step ahead) -> LDS buffer (s + 1) & 1 during step s, ONE barrier per K step.  Rows of 64 bytes (32 k), the 16-byte
+//   chunk c of column n at 64 n + 16 (c ^ f((n >> 2) & 3)), f = 0, 2, 3, 1: conflict-free for the ds_read_b128
+//   fragment read (its lane groups mix lh and lh + 1: MI355X LDS table) and for the contiguous ds_write_b128.
+//   Per wave and K step: 6 NT MFMAs (NT = 13: 1248 matrix-pipe cycles), 3 NT ds_read_b128 (4 waves: half the LDS
+//   array's cycles), ~60 VALU instructions of split.
+//   (A removed variant had every wave read its B fragments from the L2-resident images itself -- no LDS, no barrier, 4 x
+//   the L2 reads -- and measured 2-3 x slower: DESIGN.md section 4.1, profiles/dx0_split_ab.json.)
 // A fragments travel through a ring of NVQA_DX_PD K steps per lane (2 PD loads in flight).  The buffer descriptor covers
 // exactly the workgroup's rows that exist, so rows past M read as zero without a branch; K % 32 == 0 leaves no K tail.
 // The K loop runs whole rounds of PD steps: where K / 32 is no multiple of PD, the last round multiplies up to PD - 1 steps
@@ -47,9 +42,7 @@
 // segment q = i / S takes that segment's row block (i % S + q) % S: a bijection inside each segment, and the active row
 // blocks rotate over the XCDs from segment to segment.  Which workgroup computes a row block changes no bit of it.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "wgrad_bf16.h"
+#include "kmajor_bf16.h"
 
 namespace nvqa {
 
@@ -70,7 +63,7 @@ struct Dx0SplitArgs {
 // one LDS buffer: 3 images x 256 columns x 64 bytes whatever N is (one staging geometry: every chunk's address is the lane's part
 // plus a constant); two buffers = 96 KB, so a CU holds ONE workgroup -- 208 workgroups spread over 208 CUs by construction
 #define NVQA_DX_PLANE (256 * 64)
-constexpr int dx0_split_lds_bytes(bool direct) { return direct ? 0 : 2 * 3 * NVQA_DX_PLANE; }
+constexpr int dx0_split_lds_bytes() { return 2 * 3 * NVQA_DX_PLANE; }
 // column tiles per column block and column blocks for N
 inline int dx0_split_nt(int N) { return N <= 208 ? 13 : 16; }
 inline int dx0_split_col_blocks(int N) { return N <= 256 ? 1 : 2; }
@@ -83,30 +76,17 @@ inline bool dx0_split_takes(int M, int N, int K, int lda)
     return true;
 }
 
-__device__ __forceinline__ wb_u32x2 dx_cvt(wb_f32x4 v)
-{
-    const wb_f32x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
-    return wb_u32x2{__builtin_bit_cast(unsigned, __builtin_convertvector(lo, wb_bf16x2)),
-                    __builtin_bit_cast(unsigned, __builtin_convertvector(hi, wb_bf16x2))};
-}
-__device__ __forceinline__ wb_f32x4 dx_widen(wb_u32x2 p)
-{
-    return wb_f32x4{__builtin_bit_cast(float, p[0] << 16), __builtin_bit_cast(float, p[0] & 0xffff0000u),
-                    __builtin_bit_cast(float, p[1] << 16), __builtin_bit_cast(float, p[1] & 0xffff0000u)};
-}
 // 8 consecutive k of one row -> the hi, mid and lo fragments
 __device__ __forceinline__ void dx_split8(const wb_u32x4 &u0, const wb_u32x4 &u1, wb_bf16x8 (&p)[3])
 {
-    wb_f32x4 v0 = __builtin_bit_cast(wb_f32x4, u0), v1 = __builtin_bit_cast(wb_f32x4, u1);
+    wb_u32x2 c0[3], c1[3];
+    wb_split4(__builtin_bit_cast(wb_f32x4, u0), c0[0], c0[1], c0[2]);
+    wb_split4(__builtin_bit_cast(wb_f32x4, u1), c1[0], c1[1], c1[2]);
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-        const wb_u32x2 c0 = dx_cvt(v0), c1 = dx_cvt(v1);
-        p[pl] = __builtin_bit_cast(wb_bf16x8, wb_u32x4{c0[0], c0[1], c1[0], c1[1]});
-        if (pl < 2) { v0 -= dx_widen(c0); v1 -= dx_widen(c1); }
-    }
+    for (int pl = 0; pl < 3; ++pl) p[pl] = __builtin_bit_cast(wb_bf16x8, wb_u32x4{c0[pl][0], c0[pl][1], c1[pl][0], c1[pl][1]});
 }
 
-template <int NT, bool DIRECT>
+template <int NT>
 __global__ __launch_bounds__(NVQA_DX_THREADS, 1) void k_dx0_split(Dx0SplitArgs g)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char dx_smem[];
@@ -174,14 +154,8 @@ __global__ __launch_bounds__(NVQA_DX_THREADS, 1) void k_dx0_split(Dx0SplitArgs g
     };
     // fragment of column tile j, image pl: lane (li, lh) holds W^T[16 j + li][8 lh .. 8 lh + 7] of the step
     const unsigned f_loff = (unsigned)(li * 64 + 16 * (lh ^ ((0x78 >> (2 * (li >> 2))) & 3)));
-    const unsigned f_goff = (unsigned)((n0 + li) * 64 + 16 * lh); // (DIRECT)
-    auto frag_b = [&](int buf, int s, int pl, int j) -> wb_bf16x8 {
-        if constexpr (DIRECT) {
-            const unsigned off = n0 + 16 * j + li < g.N ? f_goff + (unsigned)(j * 1024) : NVQA_DX_OOB;
-            return __builtin_bit_cast(wb_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r_w, off, pl * img_bytes + s * g.N * 64, 0));
-        } else {
-            return __builtin_bit_cast(wb_bf16x8, *reinterpret_cast<const wb_u32x4 *>(dx_smem + buf * STAGE + pl * PLANE + j * 1024 + f_loff));
-        }
+    auto frag_b = [&](int buf, int pl, int j) -> wb_bf16x8 {
+        return __builtin_bit_cast(wb_bf16x8, *reinterpret_cast<const wb_u32x4 *>(dx_smem + buf * STAGE + pl * PLANE + j * 1024 + f_loff));
     };
 
     wb_f32x4 acc[NT];
@@ -195,19 +169,17 @@ __global__ __launch_bounds__(NVQA_DX_THREADS, 1) void k_dx0_split(Dx0SplitArgs g
 #pragma unroll
     for (int p = 0; p < PD; ++p) load_a(p, p);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!DIRECT) {
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) load_b(0, i, 0);
+    for (int i = 0; i < NLD; ++i) load_b(0, i, 0);
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) store_b(0, i, 0);
-        __builtin_amdgcn_sched_barrier(0);
+    for (int i = 0; i < NLD; ++i) store_b(0, i, 0);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) load_b(1, i, 1);
-        __builtin_amdgcn_sched_barrier(0);
+    for (int i = 0; i < NLD; ++i) load_b(1, i, 1);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) load_b(0, i, 2);
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    for (int i = 0; i < NLD; ++i) load_b(0, i, 2);
+    __builtin_amdgcn_sched_barrier(0);
     wb_bf16x8 a[3];
     dx_split8(ring[0][0], ring[0][1], a);
 
@@ -221,50 +193,47 @@ __global__ __launch_bounds__(NVQA_DX_THREADS, 1) void k_dx0_split(Dx0SplitArgs g
     // Vector memory loads return in order and are waited for counting from the youngest.  Every K step issues the same loads
     // in the same order on every path (a wave whose tile is skipped multiplies zeros: no branch in the loop), so each wait
     // leaves a constant number of younger loads in flight: a stage chunk has two steps to arrive, an A fragment PD - 1.
-    constexpr int TA[6] = {2, 1, 0, 1, 0, 0}, TB[6] = {0, 1, 2, 0, 1, 0}; // lo hi, mid mid, hi lo, mid hi, hi mid, hi hi
-    auto frags = [&](int buf, int s, int ch, wb_bf16x8 (&b)[3][2]) {
+    auto frags = [&](int buf, int ch, wb_bf16x8 (&b)[3][2]) {
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-            for (int j = ch * NT / NCH; j < (ch + 1) * NT / NCH; ++j) b[pl][j - ch * NT / NCH] = frag_b(buf, s, pl, j);
+            for (int j = ch * NT / NCH; j < (ch + 1) * NT / NCH; ++j) b[pl][j - ch * NT / NCH] = frag_b(buf, pl, j);
     };
     for (int s0 = 0; s0 < nk; s0 += PD) {
 #pragma unroll
         for (int p = 0; p < PD; ++p) {
             const int s = s0 + p; // (s >= nk in the last round: zeros from A)
             wb_bf16x8 b[2][3][2], an[3];
-            if constexpr (!DIRECT) __syncthreads(); // buffer s & 1 is complete; nobody reads buffer (s + 1) & 1 any more
-            frags(p & 1, s, 0, b[0]);
+            __syncthreads(); // buffer s & 1 is complete; nobody reads buffer (s + 1) & 1 any more
+            frags(p & 1, 0, b[0]);
             __builtin_amdgcn_sched_barrier(0);
             wb_f32x4 v0 = __builtin_bit_cast(wb_f32x4, ring[(p + 1) % PD][0]), v1 = __builtin_bit_cast(wb_f32x4, ring[(p + 1) % PD][1]);
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) {
-                if (ch + 1 < NCH) frags(p & 1, s, ch + 1, b[(ch + 1) & 1]);
+                if (ch + 1 < NCH) frags(p & 1, ch + 1, b[(ch + 1) & 1]);
 #pragma unroll
                 for (int t = 0; t < 6; ++t)
 #pragma unroll
                     for (int j = ch * NT / NCH; j < (ch + 1) * NT / NCH; ++j)
-                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[TA[t]], b[ch & 1][TB[t]][j - ch * NT / NCH], acc[j], 0, 0, 0);
-                if (ch < 3) { // piece ch of the next step's A fragments
-                    const wb_u32x2 c0 = dx_cvt(v0), c1 = dx_cvt(v1);
+                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[WB_TERM_A[t]], b[ch & 1][WB_TERM_B[t]][j - ch * NT / NCH], acc[j], 0, 0, 0);
+                if (ch < 3) { // piece ch of the next step's A fragments: one step of wb_split4() per group, the two vectors side by side
+                    const wb_u32x2 c0 = wb_pack(v0), c1 = wb_pack(v1);
                     an[ch] = __builtin_bit_cast(wb_bf16x8, wb_u32x4{c0[0], c0[1], c1[0], c1[1]});
-                    if (ch < 2) { v0 -= dx_widen(c0); v1 -= dx_widen(c1); }
+                    if (ch < 2) { v0 -= wb_widen(c0); v1 -= wb_widen(c1); }
                 }
                 if (ch == 0) load_a(p, s + PD); // slot p held step s, split during step s - 1
-                if constexpr (!DIRECT) {
 #pragma unroll
-                    for (int i = ch * NLD / NCH; i < (ch + 1) * NLD / NCH; ++i) {
-                        store_b((p + 1) & 1, i, (p + 1) & 1);
-                        load_b((p + 1) & 1, i, s + 3);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+                for (int i = ch * NLD / NCH; i < (ch + 1) * NLD / NCH; ++i) {
+                    store_b((p + 1) & 1, i, (p + 1) & 1);
+                    load_b((p + 1) & 1, i, s + 3);
+                }
+                __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
 #pragma unroll
-                    for (int x = 0; x < 12; ++x) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                        if (x % 4 == 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                        if (x % 4 == 3) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
+                for (int x = 0; x < 12; ++x) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+                    if (x % 4 == 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+                    if (x % 4 == 3) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -287,25 +256,24 @@ __global__ __launch_bounds__(NVQA_DX_THREADS, 1) void k_dx0_split(Dx0SplitArgs g
     }
 }
 
-// one launch on stream st; direct: the B fragments straight from the images (the slower form, figures in the header; the library stages through LDS)
-template <int NT, bool DIRECT>
+// one launch on stream st
+template <int NT>
 inline hipError_t dx0_split_launch_nt(hipStream_t st, const Dx0SplitArgs &g)
 {
     static bool attr = false;
-    constexpr int lds = dx0_split_lds_bytes(DIRECT);
-    if (!attr && lds > 0) {
-        const hipError_t e = hipFuncSetAttribute((const void *)k_dx0_split<NT, DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    constexpr int lds = dx0_split_lds_bytes();
+    if (!attr) {
+        const hipError_t e = hipFuncSetAttribute((const void *)k_dx0_split<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
         attr = true;
     }
     const dim3 grid((g.M + NVQA_DX_ROWS - 1) / NVQA_DX_ROWS, dx0_split_col_blocks(g.N));
-    hipLaunchKernelGGL((k_dx0_split<NT, DIRECT>), grid, dim3(NVQA_DX_THREADS), lds, st, g);
+    hipLaunchKernelGGL((k_dx0_split<NT>), grid, dim3(NVQA_DX_THREADS), lds, st, g);
     return hipGetLastError();
 }
-inline hipError_t dx0_split_launch(hipStream_t st, const Dx0SplitArgs &g, bool direct = false)
+inline hipError_t dx0_split_launch(hipStream_t st, const Dx0SplitArgs &g)
 {
-    if (dx0_split_nt(g.N) == 13) return direct ? dx0_split_launch_nt<13, true>(st, g) : dx0_split_launch_nt<13, false>(st, g);
-    return direct ? dx0_split_launch_nt<16, true>(st, g) : dx0_split_launch_nt<16, false>(st, g);
+    return dx0_split_nt(g.N) == 13 ? dx0_split_launch_nt<13>(st, g) : dx0_split_launch_nt<16>(st, g);
 }
 
 } // namespace nvqa

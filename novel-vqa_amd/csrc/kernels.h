@@ -8,6 +8,7 @@
 #include "../../include/nvqa_layout.h"
 #include "epilogues.h"
 #include "gemm_f32.h"
+#include "kmajor_bf16.h"
 #include "latch.h"
 
 namespace nvqa {
@@ -45,7 +46,7 @@ struct TransposeJob {
     const float *W = nullptr; // nullptr: no job
     unsigned short *out = nullptr;
     int rows = 0, cols = 0, first_block = 0, nblocks = 0;
-    // f32 mode (dx0_split.h): `out` takes hi = bf16(w) and these two mid = bf16(w - hi) and lo = bf16(w - hi - mid), all three in
+    // f32 mode (dx0_split.h): `out` takes hi and these two the mid and lo pieces of w (kmajor_bf16.h: wb_split1()), all three in
     // blocks of 32 rows of W, [rows / 32][cols][32] (rows % 32 == 0), instead of [cols][rows]; nullptr: the one [cols][rows] image
     unsigned short *out_mid = nullptr, *out_lo = nullptr;
 };
@@ -62,14 +63,12 @@ __device__ __forceinline__ void transpose_to_bf16_block(const TransposeJob &j, i
         const int cc = c0 + i, r = r0 + tx;
         if (cc < j.cols && r < j.rows) {
             const size_t o = j.out_mid ? ((size_t)(r0 / 32) * j.cols + cc) * 32 + tx : (size_t)cc * j.rows + r;
-            const float w = t[tx][i];
-            const __bf16 hi = (__bf16)w;
+            __bf16 hi, mid, lo;
+            wb_split1(t[tx][i], hi, mid, lo);
             reinterpret_cast<__bf16 *>(j.out)[o] = hi;
             if (j.out_mid) {
-                const float r1 = w - (float)hi;
-                const __bf16 mid = (__bf16)r1;
                 reinterpret_cast<__bf16 *>(j.out_mid)[o] = mid;
-                reinterpret_cast<__bf16 *>(j.out_lo)[o] = (__bf16)(r1 - (float)mid);
+                reinterpret_cast<__bf16 *>(j.out_lo)[o] = lo;
             }
         }
     }

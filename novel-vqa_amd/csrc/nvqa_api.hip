@@ -772,36 +772,21 @@ static int colsum(nvqa_ctx *c, const float *X, int M, int N, int ld, float *out,
     return 0;
 }
 
-// bf16 operand mode: the gfx950 k-major kernel (wgrad_bf16.h); A16 / B16: bf16 images of the operands where this step's
-// persistent kernels wrote them (NULL: rounded from the f32 rows on the way into LDS -- the same values either way)
-static int wgrad_bf16(nvqa_ctx *c, const float *A, const unsigned short *A16, int lda, const float *Bm, const unsigned short *B16, int ldb,
-                      int M, int N, int K, float *dW, float *slabs, hipStream_t st)
+// split-K of a weight gradient over tiles of tile_m x tile_n: how many K slices (slabs) -- enough to fill the machine, each
+// at least 256 K rows, and no more than the slab buffer holds.  tools/kbench11, 2048 x 200 x 13312: 16 slices 115 us, 8 slices
+// 129 us; measured again for the k-major kernels (round 2): 2048 x 512: 8 slices, 2048 x 200: 16
+static int wgrad_slices(const nvqa_ctx *c, int tile_m, int tile_n, int M, int N, int K)
 {
-    const int tiles = ((M + NVQA_WB_BM - 1) / NVQA_WB_BM) * ((N + NVQA_WB_BN - 1) / NVQA_WB_BN);
+    const int tiles = ((M + tile_m - 1) / tile_m) * ((N + tile_n - 1) / tile_n);
     int ks = 1;
-    while (ks < 16 && tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2; // measured (round 2): 2048 x 512: 8 slices, 2048 x 200: 16
+    while (ks < 16 && tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2;
     if ((size_t)ks * M * N > c->slab_floats) ks = std::max<int>(1, (int)(c->slab_floats / ((size_t)M * N)));
-    int kslice = ((K + ks - 1) / ks + NVQA_WB_BK - 1) / NVQA_WB_BK * NVQA_WB_BK;
-    ks = (K + kslice - 1) / kslice;
-    if (M % 8 || lda % 8) A16 = nullptr;
-    if (N % 8 || ldb % 8) B16 = nullptr;
-    {
-        ProfScope ps(c, PF_GEMM_WGRAD, 2.0 * M * N * K, ((double)K * (M + N) * (A16 ? 2 : 4) + (double)ks * M * N * 4), st);
-        WgradBf16Args g{A, Bm, A16, B16, ks == 1 ? dW : slabs, ks == 1 ? 0 : (size_t)M * N, lda, ldb, N, M, N, K, kslice};
-        const dim3 grid((M + NVQA_WB_BM - 1) / NVQA_WB_BM, (N + NVQA_WB_BN - 1) / NVQA_WB_BN, ks);
-        static bool attr = false;
-        if (!attr) {
-            NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_bf16<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES));
-            NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_bf16<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES));
-            NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_bf16<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES));
-            attr = true;
-        }
-        if (A16 && B16) hipLaunchKernelGGL((k_wgrad_bf16<true, true>), grid, dim3(256), NVQA_WB_LDS_BYTES, st, g);
-        else if (A16) hipLaunchKernelGGL((k_wgrad_bf16<true, false>), grid, dim3(256), NVQA_WB_LDS_BYTES, st, g);
-        else hipLaunchKernelGGL((k_wgrad_bf16<false, false>), grid, dim3(256), NVQA_WB_LDS_BYTES, st, g);
-        NVQA_HIP(hipGetLastError());
-    }
-    if (ks == 1) return 0;
+    return ks;
+}
+
+// dW = the ks slabs summed in z order (deterministic)
+static int reduce_slabs(nvqa_ctx *c, const float *slabs, int ks, int M, int N, float *dW, hipStream_t st)
+{
     ProfScope ps(c, PF_REDUCE, 0, (double)(ks + 1) * M * N * 4, st);
     const size_t n4 = (size_t)M * N / 4;
     hipLaunchKernelGGL(k_reduce_slabs, dim3((n4 + 255) / 256), dim3(256), 0, st, slabs, ks, n4, reinterpret_cast<float4 *>(dW));
@@ -809,49 +794,46 @@ static int wgrad_bf16(nvqa_ctx *c, const float *A, const unsigned short *A16, in
     return 0;
 }
 
+// bf16 operand mode: the gfx950 k-major kernel (wgrad_bf16.h); A16 / B16: bf16 images of the operands where this step's
+// persistent kernels wrote them (NULL: rounded from the f32 rows on the way into LDS -- the same values either way)
+static int wgrad_bf16(nvqa_ctx *c, const float *A, const unsigned short *A16, int lda, const float *Bm, const unsigned short *B16, int ldb,
+                      int M, int N, int K, float *dW, float *slabs, hipStream_t st)
+{
+    int ks = wgrad_slices(c, NVQA_WB_BM, NVQA_WB_BN, M, N, K);
+    const int kslice = ((K + ks - 1) / ks + NVQA_WB_BK - 1) / NVQA_WB_BK * NVQA_WB_BK;
+    ks = (K + kslice - 1) / kslice;
+    if (M % 8 || lda % 8) A16 = nullptr;
+    if (N % 8 || ldb % 8) B16 = nullptr;
+    {
+        ProfScope ps(c, PF_GEMM_WGRAD, 2.0 * M * N * K, ((double)K * (M + N) * (A16 ? 2 : 4) + (double)ks * M * N * 4), st);
+        NVQA_HIP(wgrad_bf16_launch(st, WgradBf16Args{A, Bm, A16, B16, ks == 1 ? dW : slabs, ks == 1 ? 0 : (size_t)M * N, lda, ldb, N, M, N, K, kslice}));
+    }
+    return ks == 1 ? 0 : reduce_slabs(c, slabs, ks, M, N, dW, st);
+}
+
 // f32 mode: each f32 product as six bf16 MFMA terms (wgrad_split.h); the K stages that hold active rows are dealt
 // round-robin to the ks slices inside the kernel, so ks is all the host chooses
 static int wgrad_split(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb, int M, int N, int K,
                        float *dW, float *slabs, hipStream_t st)
 {
-    const int tiles = ((M + NVQA_WS_BM - 1) / NVQA_WS_BM) * ((N + NVQA_WS_BN - 1) / NVQA_WS_BN);
-    int ks = 1;
-    while (ks < 16 && tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2; // 2048 x 512: 8 slices, 2048 x 200: 16
-    if ((size_t)ks * M * N > c->slab_floats) ks = std::max<int>(1, (int)(c->slab_floats / ((size_t)M * N)));
+    const int ks = wgrad_slices(c, NVQA_WS_BM, NVQA_WS_BN, M, N, K);
     {
         // bytes: the compulsory traffic -- each operand row once (the filled share of the K rows where the kernel can skip
         // padding stages, seg_rows % 32 == 0; all K rows otherwise) and the slabs -- not the re-reads of a dG row tile per
         // column tile and of a column tile per row tile, which L2 serves in part (profiles/wgrad_split_ab.json: 249 MB fetched)
         const double kfrac = c->d.B % NVQA_WS_BK == 0 ? c->batch_len_frac : 1.0;
         ProfScope ps(c, PF_GEMM_WGRAD, 2.0 * M * N * K, ((double)K * (M + N) * kfrac + (double)ks * M * N) * 4, st);
-        WgradSplitArgs g{A, Bm, ks == 1 ? dW : slabs, ks == 1 ? 0 : (size_t)M * N, c->nrows, c->d.B, lda, ldb, N, M, N, K};
+        const WgradSplitArgs g{A, Bm, ks == 1 ? dW : slabs, ks == 1 ? 0 : (size_t)M * N, c->nrows, c->d.B, lda, ldb, N, M, N, K};
         if (c->wgrad_kernel == 2 && wgrad_split2_takes(M, N, K, lda, ldb, c->d.B)) {
             // the same slabs, bit for bit, from 256 x 128 tiles with a pipelined K loop (wgrad_split2.h); ks stays as chosen above
-            static bool attr2 = false;
-            if (!attr2) {
-                NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_split2, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS2_LDS_BYTES));
-                attr2 = true;
-            }
-            hipLaunchKernelGGL(k_wgrad_split2, dim3(wgrad_split2_blocks(M, N, ks)), dim3(NVQA_WS2_THREADS), NVQA_WS2_LDS_BYTES, st, g, ks);
+            NVQA_HIP(wgrad_split2_launch(st, g, ks));
             c->wgrad_launches[2] += 1;
         } else {
-            const dim3 grid((M + NVQA_WS_BM - 1) / NVQA_WS_BM, (N + NVQA_WS_BN - 1) / NVQA_WS_BN, ks);
-            static bool attr = false;
-            if (!attr) {
-                NVQA_HIP(hipFuncSetAttribute((const void *)k_wgrad_split, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS_LDS_BYTES));
-                attr = true;
-            }
-            hipLaunchKernelGGL(k_wgrad_split, grid, dim3(256), NVQA_WS_LDS_BYTES, st, g);
+            NVQA_HIP(wgrad_split_launch(st, g, ks));
             c->wgrad_launches[1] += 1;
         }
-        NVQA_HIP(hipGetLastError());
     }
-    if (ks == 1) return 0;
-    ProfScope ps(c, PF_REDUCE, 0, (double)(ks + 1) * M * N * 4, st);
-    const size_t n4 = (size_t)M * N / 4;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((n4 + 255) / 256), dim3(256), 0, st, slabs, ks, n4, reinterpret_cast<float4 *>(dW));
-    NVQA_HIP(hipGetLastError());
-    return 0;
+    return ks == 1 ? 0 : reduce_slabs(c, slabs, ks, M, N, dW, st);
 }
 
 // dW[M x N] = A^T B with A stored [K][M], B stored [K][N]; K = TS*B is long, the output
@@ -862,10 +844,7 @@ static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb,
     if (c->bf16 && M % 4 == 0 && N % 4 == 0) return wgrad_bf16(c, A, A16, lda, Bm, B16, ldb, M, N, K, dW, slabs, st);
     if (!c->bf16 && c->wgrad_split_on && wgrad_split_takes(M, N, K, lda, ldb, c->d.B)) return wgrad_split(c, A, lda, Bm, ldb, M, N, K, dW, slabs, st);
     if (!c->bf16) c->wgrad_launches[0] += 1; // (bf16 mode lands here only where M or N is no multiple of 4: not an f32-mode product)
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    int ks = 1;
-    while (ks < 16 && tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2; // tools/kbench11: 2048 x 200 x 13312: 16 slices 115 us, 8 slices 129 us
-    if ((size_t)ks * M * N > c->slab_floats) ks = std::max<int>(1, (int)(c->slab_floats / ((size_t)M * N)));
+    int ks = wgrad_slices(c, 128, 128, M, N, K);
     int kslice = (K + ks - 1) / ks;
     kslice = (kslice + 31) / 32 * 32;
     ks = (K + kslice - 1) / kslice;
@@ -879,12 +858,7 @@ static int wgrad(nvqa_ctx *c, const float *A, int lda, const float *Bm, int ldb,
         }
         NVQA_TRY((gemm_big<A_MC, B_NC, EpiStore, true>(c, g, EpiStore{slabs, N, (size_t)M * N}, st)));
     }
-    ProfScope ps(c, PF_REDUCE, 0, (double)(ks + 1) * M * N * 4, st);
-    const size_t n4 = (size_t)M * N / 4;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((n4 + 255) / 256), dim3(256), 0, st, slabs, ks, n4,
-                       reinterpret_cast<float4 *>(dW));
-    NVQA_HIP(hipGetLastError());
-    return 0;
+    return reduce_slabs(c, slabs, ks, M, N, dW, st);
 }
 
 // ------------------------------------------------------------------------------------

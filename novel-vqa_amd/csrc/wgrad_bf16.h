@@ -1,34 +1,22 @@
 // wgrad_bf16.h -- the time-batched weight gradients of the bf16 operand mode (nvqa_set_precision(1)) as a gfx950 kernel:
 //     dW[M x N] = A^T B,   A = dG stored [K][lda] (K = steps x rows, M gate pre-activations contiguous),
 //                          B = the layer's input / previous hidden state stored [K][ldb] (N contiguous)
-// Both operands are K-MAJOR: the reduction index is the slow one, so a lane's MFMA fragment (8 consecutive k of one m)
-// is a COLUMN of the tile.  gemm_f32.h's BF mode reads it with 4 ds_read_b32 per 4 k from an f32 image and converts per
-// MFMA (v_mfma_f32_32x32x8_bf16_1k): 0.38 ms per step, LDS- and VALU-bound, the matrix pipe 10 % busy.  Here:
-//   * the f32 rows are rounded to bf16 ONCE on their way into LDS (v_cvt_pk_bf16_f32, round-to-nearest-even -- the same
-//     rounding of the same values as before: bit-identical products), the image is [k][128 m] bf16, half the bytes;
-//   * fragments come out of that k-major image with ds_read_b64_tr_b16, the hardware transpose read (4 k x 16 m block per
-//     16-lane group, delivered column-major): two reads = the 8 k of one v_mfma_f32_16x16x32_bf16 operand;
-//   * image layout (b) of cdna_hip_programming.md T10: 256-byte rows, 16-byte chunk ch of row k at
-//     256 k + 16 (ch ^ (((k & 3) << 2) | ((k >> 2) & 3))): conflict-free for these reads.
+// Both operands are K-MAJOR (kmajor_bf16.h: image layout, transposed fragment read, accumulator tile).  gemm_f32.h's BF mode
+// reads a fragment with 4 ds_read_b32 per 4 k from an f32 image and converts per MFMA (v_mfma_f32_32x32x8_bf16_1k): 0.38 ms
+// per step, LDS- and VALU-bound, the matrix pipe 10 % busy.  Here:
+//   * the f32 rows are rounded to bf16 ONCE on their way into LDS (wb_pack(): the same rounding of the same values as
+//     before, bit-identical products), the image is [k][128 m] bf16, half the bytes;
+//   * two transposed reads out of that image = the 8 k of one v_mfma_f32_16x16x32_bf16 operand.
 // Where the step's persistent bf16 kernels have left bf16 IMAGES of an operand (dG: lstm_persist_bwd2.h's Gb; h and
 // Dropout(h): lstm_persist.h's Hb / Ub -- the same values, rounded the same way) the operand is staged from the image
 // instead (template flags ABF / BBF): half the L2 -> LDS bytes, which bound the f32-sourced form (32 flop per byte at
 // this tile size), and no conversion.
 // Tile 128 x 128 x 64 per stage, 4 waves as 2 x 2 (64 x 64 each = 4 x 4 MFMA tiles), register-prefetched global loads,
-// double-buffered LDS, split-K over blockIdx.z into f32 slabs that k_reduce_slabs sums in z order (deterministic).
+// double-buffered LDS, split-K over blockIdx.z into f32 slabs that the caller sums in z order (deterministic).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "kmajor_bf16.h"
 
 namespace nvqa {
-
-typedef float wb_f32x4 __attribute__((ext_vector_type(4)));
-typedef float wb_f32x2 __attribute__((ext_vector_type(2)));
-typedef short wb_s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 wb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned wb_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned wb_u32x4 __attribute__((ext_vector_type(4)));
 
 struct WgradBf16Args {
     const float *A, *B; // [K][lda], [K][ldb]
@@ -43,8 +31,6 @@ struct WgradBf16Args {
 #define NVQA_WB_BK 64
 #define NVQA_WB_STAGE_BYTES (2 * NVQA_WB_BK * 256) // A image + B image
 #define NVQA_WB_LDS_BYTES (2 * NVQA_WB_STAGE_BYTES)
-
-__device__ __forceinline__ unsigned wb_off(int row, int ch) { return 256u * row + 16u * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 
 template <bool ABF, bool BBF>
 __global__ __launch_bounds__(256) void k_wgrad_bf16(WgradBf16Args g)
@@ -84,12 +70,6 @@ __global__ __launch_bounds__(256) void k_wgrad_bf16(WgradBf16Args g)
                 rb[i] = b_in && k0 + srow + 8 * i < kend ? *reinterpret_cast<const wb_u32x4 *>(pb + (size_t)(k0 - kbeg + 8 * i) * g.ldb) : wb_u32x4{0, 0, 0, 0};
         }
     };
-    auto pack = [](const wb_u32x4 &u) {
-        const wb_f32x4 v = __builtin_bit_cast(wb_f32x4, u);
-        const wb_f32x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
-        return wb_u32x2{__builtin_bit_cast(unsigned, __builtin_convertvector(lo, wb_bf16x2)),
-                        __builtin_bit_cast(unsigned, __builtin_convertvector(hi, wb_bf16x2))};
-    };
     auto store_stage = [&](int buf) {
         unsigned char *As = wb_smem + buf * NVQA_WB_STAGE_BYTES, *Bs = As + NVQA_WB_BK * 256;
         if constexpr (ABF) {
@@ -97,37 +77,26 @@ __global__ __launch_bounds__(256) void k_wgrad_bf16(WgradBf16Args g)
             for (int i = 0; i < 4; ++i) *reinterpret_cast<wb_u32x4 *>(As + wb_off(irow + 16 * i, ic8)) = ra[i];
         } else {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) *reinterpret_cast<wb_u32x2 *>(As + wb_off(srow + 8 * i, sc4 >> 1) + 8u * (sc4 & 1)) = pack(ra[i]);
+            for (int i = 0; i < 8; ++i) *reinterpret_cast<wb_u32x2 *>(As + wb_off(srow + 8 * i, sc4 >> 1) + 8u * (sc4 & 1)) = wb_pack(__builtin_bit_cast(wb_f32x4, ra[i]));
         }
         if constexpr (BBF) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) *reinterpret_cast<wb_u32x4 *>(Bs + wb_off(irow + 16 * i, ic8)) = rb[i];
         } else {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) *reinterpret_cast<wb_u32x2 *>(Bs + wb_off(srow + 8 * i, sc4 >> 1) + 8u * (sc4 & 1)) = pack(rb[i]);
+            for (int i = 0; i < 8; ++i) *reinterpret_cast<wb_u32x2 *>(Bs + wb_off(srow + 8 * i, sc4 >> 1) + 8u * (sc4 & 1)) = wb_pack(__builtin_bit_cast(wb_f32x4, rb[i]));
         }
     };
-    // fragment of the 16 columns starting at c16 (tile-local), k rows kk .. kk+31: lane (li, lh) needs k = kk + 8 lh + j.
-    // One transposed read covers a 4 (k) x 16 (columns) block per 16-lane group: lane 4q + p of the group supplies the
-    // address of row q, columns 4p .. 4p+3 and receives column (4q + p) of the 4 rows.
+    // fragment of the 16 columns starting at c16 (tile-local), k rows kk .. kk+31 (kmajor_bf16.h)
     const int q = li >> 2, p = li & 3;
     auto frag = [&](const unsigned char *img, int c16, int kk) -> wb_bf16x8 {
         const int r0 = kk + 8 * lh + q;
         const int ch = (c16 >> 3) + (p >> 1);
-        const wb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) wb_s16x4 *)(img + wb_off(r0, ch) + 8u * (p & 1)));
-        const wb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) wb_s16x4 *)(img + wb_off(r0 + 4, ch) + 8u * (p & 1)));
-        typedef short s16x8_t __attribute__((ext_vector_type(8)));
-        const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(wb_bf16x8, v);
+        return wb_frag((wb_lds_s16x4)(img + wb_off(r0, ch) + 8u * (p & 1)), (wb_lds_s16x4)(img + wb_off(r0 + 4, ch) + 8u * (p & 1)));
     };
 
     wb_f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = wb_f32x4{0.f, 0.f, 0.f, 0.f};
+    wb_zero_tile(acc);
 
     const int nst = (kend - kbeg + NVQA_WB_BK - 1) / NVQA_WB_BK;
     if (nst > 0) {
@@ -154,19 +123,28 @@ __global__ __launch_bounds__(256) void k_wgrad_bf16(WgradBf16Args g)
             __syncthreads();
         }
     }
-    // D[row = 4 lh + r][col = li] of tile (i, j): row = m (A's columns), col = n
-    float *out = g.out + (size_t)blockIdx.z * g.slab_stride;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + 16 * j + li;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm * 64 + 16 * i + 4 * lh + r;
-                if (m < g.M && n < g.N) out[(size_t)m * g.ldo + n] = acc[i][j][r];
-            }
-        }
+    wb_store_tile(g.out + (size_t)blockIdx.z * g.slab_stride, g.ldo, g.M, g.N, m0 + wm * 64, n0 + wn * 64, li, lh, acc);
+}
+
+// one launch on stream st: the instance follows the images given (A16 and B16, A16 alone, or neither), the grid's z the K slices
+template <bool ABF, bool BBF>
+inline hipError_t wgrad_bf16_launch_inst(hipStream_t st, const WgradBf16Args &g)
+{
+    static bool attr = false;
+    if (!attr) {
+        const hipError_t e = hipFuncSetAttribute((const void *)k_wgrad_bf16<ABF, BBF>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES);
+        if (e != hipSuccess) return e;
+        attr = true;
+    }
+    const dim3 grid((g.M + NVQA_WB_BM - 1) / NVQA_WB_BM, (g.N + NVQA_WB_BN - 1) / NVQA_WB_BN, (g.K + g.kslice - 1) / g.kslice);
+    hipLaunchKernelGGL((k_wgrad_bf16<ABF, BBF>), grid, dim3(256), NVQA_WB_LDS_BYTES, st, g);
+    return hipGetLastError();
+}
+inline hipError_t wgrad_bf16_launch(hipStream_t st, const WgradBf16Args &g)
+{
+    if (g.A16 && g.B16) return wgrad_bf16_launch_inst<true, true>(st, g);
+    if (g.A16) return wgrad_bf16_launch_inst<true, false>(st, g);
+    return wgrad_bf16_launch_inst<false, false>(st, g);
 }
 
 } // namespace nvqa

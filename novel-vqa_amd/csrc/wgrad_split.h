@@ -1,16 +1,9 @@
 // wgrad_split.h -- the time-batched weight gradients of the f32 mode as SIX bf16 MFMA terms per f32 product:
 //     dW[M x N] = A^T B,   A = dG stored [K][lda] (K = steps x rows, M gate pre-activations contiguous),
 //                          B = the layer's input / previous hidden state stored [K][ldb] (N contiguous)
-// An f32 value is exactly the sum of three bf16 values (3 x 8 significand bits): hi = bf16(x), mid = bf16(x - hi),
-// lo = bf16(x - hi - mid), round-to-nearest-even, the subtractions exact in f32.  A product a b is then the sum of nine
-// bf16 x bf16 products, each exact in f32; mid lo, lo mid and lo lo lie at or below 2^-24 of the product -- under what one
-// f32 rounding of the product loses anyway -- and are dropped.  The other six go through v_mfma_f32_16x16x32_bf16 into the
-// SAME f32 accumulator, smallest first:
-//     lo hi, mid mid, hi lo, mid hi, hi mid, hi hi
-// The order is part of the kernel's definition (bit-reproducible results).  Six MFMAs of K = 32 take 96 matrix-pipe
-// cycles where v_mfma_f32_16x16x4_f32 needs 256 for the same K.
-//   * The split happens ONCE per value, on its way into LDS: three k-major bf16 images per operand in the layout of
-//     wgrad_bf16.h (wb_off(): conflict-free for ds_read_b64_tr_b16), fragments by the transposed read as there.
+// The three-way split of an f32 value, the six terms and their order, the k-major LDS image and the transposed fragment
+// read are kmajor_bf16.h's.  What is this kernel's own:
+//   * The split happens ONCE per value, on its way into LDS: three k-major bf16 images per operand.
 //   * One LDS stage (6 images x 32 k x 256 B = 48 KB; with the stage list's tables the launch asks for 55 328 bytes)
 //     and <= 256 registers: two workgroups share a CU, so one workgroup's fragment reads and barriers run under the
 //     other's MFMAs.  Within a workgroup a K stage is
@@ -18,18 +11,15 @@
 //         96 MFMAs of stage s, with the split arithmetic and the LDS stores of stage s+1 in their gaps | barrier
 //     (sched_group_barrier: 16 MFMAs alone while the loads land, then per MFMA three VALU instructions and per three
 //     MFMAs one LDS store).  Loading two stages ahead (a second register set, 256 VGPRs) measured the same.
-//   * Split-K over blockIdx.z into f32 slabs that k_reduce_slabs sums in z order.  The K stages that hold active rows
+//   * Split-K over the slices into f32 slabs that the caller sums in z order.  The K stages that hold active rows
 //     (ragged batches: rows >= nrows[step] of a step are zero padding; such stages are skipped when seg_rows % 32 == 0)
-//     form one list, dealt to the slices round-robin: stage i of the list goes to slice i % gridDim.z, so a ragged
-//     batch loads every slice alike.  Rows between nrows[step] and the end of their 32-row stage ARE multiplied: they
-//     must be zero in one operand and finite in the other, as for gemm_big's K tiles.  Every workgroup builds its own
-//     list (a prefix sum over the steps and a search per stage, three barriers): small beside the K loop.
-// Non-finite operands: x = +-inf or NaN gives NaN pieces, so a non-finite dG still gives a non-finite dW (NaN where the
-// f32 chain may have said inf); |x| >= 2^127 can round hi to inf.  Neither occurs in a step that is not already lost.
+//     form one list, dealt to the slices round-robin: stage i of the list goes to slice i % (number of slices), so a
+//     ragged batch loads every slice alike (ws_stage_list(), shared with k_wgrad_split2).  Rows between nrows[step] and
+//     the end of their 32-row stage ARE multiplied: they must be zero in one operand and finite in the other, as for
+//     gemm_big's K tiles.  Every workgroup builds its own list (a prefix sum over the steps and a search per stage, three
+//     barriers): small beside the K loop.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "wgrad_bf16.h"
+#include "kmajor_bf16.h"
 
 namespace nvqa {
 
@@ -59,6 +49,40 @@ inline bool wgrad_split_takes(int M, int N, int K, int lda, int ldb, int seg_row
     return true;
 }
 
+// the K stages of slice z of ks: entry idx of the slice's list = stage z + idx ks of the list of active stages, its first
+// K row in stage_k0[idx].  Returns the slice's number of stages.  Called by all THREADS threads of the workgroup; the
+// tables (seg_cnt, seg_base: NVQA_WS_MAX_SEGS + 4 ints each, stage_k0: NVQA_WS_MAX_STAGES) are whole behind its last barrier.
+template <int THREADS>
+__device__ __forceinline__ int ws_stage_list(const WgradSplitArgs &g, int z, int ks, int *seg_cnt, int *seg_base, int *stage_k0)
+{
+    const int tid = threadIdx.x;
+    const bool skip = g.nrows != nullptr && g.seg_rows > 0 && g.seg_rows % NVQA_WS_BK == 0;
+    const int seg_rows = skip ? g.seg_rows : g.K, nseg = (g.K + seg_rows - 1) / seg_rows;
+    // (strided over the block: nseg may equal the block size, and seg_base has nseg + 1 entries)
+    for (int t = tid; t < nseg; t += THREADS) {
+        int lim = min(seg_rows, g.K - t * seg_rows);
+        if (skip) lim = min(lim, g.nrows[t]);
+        seg_cnt[t] = lim > 0 ? (lim + NVQA_WS_BK - 1) / NVQA_WS_BK : 0;
+    }
+    __syncthreads();
+    for (int t = tid; t <= nseg; t += THREADS) {
+        int b = 0;
+        for (int s = 0; s < t; ++s) b += seg_cnt[s];
+        seg_base[t] = b;
+    }
+    __syncthreads();
+    const int total = seg_base[nseg];
+    const int nst = total > z ? (total - z + ks - 1) / ks : 0;
+    for (int idx = tid; idx < nst; idx += THREADS) {
+        const int i = z + idx * ks;
+        int s = 0;
+        while (seg_base[s + 1] <= i) ++s; // i < total = seg_base[nseg]
+        stage_k0[idx] = s * seg_rows + NVQA_WS_BK * (i - seg_base[s]);
+    }
+    __syncthreads();
+    return nst;
+}
+
 __global__ __launch_bounds__(256, 2) void k_wgrad_split(WgradSplitArgs g)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char ws_smem[];
@@ -70,31 +94,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_split(WgradSplitArgs g)
     int *seg_cnt = reinterpret_cast<int *>(ws_smem + 6 * NVQA_WS_PLANE), *seg_base = seg_cnt + NVQA_WS_MAX_SEGS + 4;
     int *stage_k0 = seg_base + NVQA_WS_MAX_SEGS + 4;
 
-    // my K stages: entry idx of the slice's list = stage z + idx kz of the list of active stages
-    const bool skip = g.nrows != nullptr && g.seg_rows > 0 && g.seg_rows % NVQA_WS_BK == 0;
-    const int seg_rows = skip ? g.seg_rows : g.K, nseg = (g.K + seg_rows - 1) / seg_rows;
-    // (strided over the block: nseg may equal the block size, and seg_base has nseg + 1 entries)
-    for (int t = tid; t < nseg; t += 256) {
-        int lim = min(seg_rows, g.K - t * seg_rows);
-        if (skip) lim = min(lim, g.nrows[t]);
-        seg_cnt[t] = lim > 0 ? (lim + NVQA_WS_BK - 1) / NVQA_WS_BK : 0;
-    }
-    __syncthreads();
-    for (int t = tid; t <= nseg; t += 256) {
-        int b = 0;
-        for (int s = 0; s < t; ++s) b += seg_cnt[s];
-        seg_base[t] = b;
-    }
-    __syncthreads();
-    const int total = seg_base[nseg];
-    const int nst = total > z ? (total - z + kz - 1) / kz : 0;
-    for (int idx = tid; idx < nst; idx += 256) {
-        const int i = z + idx * kz;
-        int s = 0;
-        while (seg_base[s + 1] <= i) ++s; // i < total = seg_base[nseg]
-        stage_k0[idx] = s * seg_rows + NVQA_WS_BK * (i - seg_base[s]);
-    }
-    __syncthreads();
+    const int nst = ws_stage_list<256>(g, z, kz, seg_cnt, seg_base, stage_k0);
 
     // staging: thread -> (row = tid / 32 + 8 i, 4 columns 4 (tid % 32) ..), i = 0 .. 3
     const int srow = tid >> 5, sc4 = tid & 31;
@@ -110,23 +110,10 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_split(WgradSplitArgs g)
             rb[i] = b_in && in ? *reinterpret_cast<const wb_u32x4 *>(pb + (size_t)(k0 + 8 * i) * g.ldb) : wb_u32x4{0, 0, 0, 0};
         }
     };
-    auto cvt = [](wb_f32x4 v) {
-        const wb_f32x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
-        return wb_u32x2{__builtin_bit_cast(unsigned, __builtin_convertvector(lo, wb_bf16x2)),
-                        __builtin_bit_cast(unsigned, __builtin_convertvector(hi, wb_bf16x2))};
-    };
-    auto widen = [](wb_u32x2 p) {
-        return wb_f32x4{__builtin_bit_cast(float, p[0] << 16), __builtin_bit_cast(float, p[0] & 0xffff0000u),
-                        __builtin_bit_cast(float, p[1] << 16), __builtin_bit_cast(float, p[1] & 0xffff0000u)};
-    };
     auto put = [&](unsigned char *img, int row, const wb_u32x4 &u) { // hi / mid / lo images of 4 values of one k row
-        wb_f32x4 v = __builtin_bit_cast(wb_f32x4, u);
         const unsigned o = wb_off(row, sc4 >> 1) + 8u * (sc4 & 1);
-        const wb_u32x2 h = cvt(v);
-        v -= widen(h);
-        const wb_u32x2 m = cvt(v);
-        v -= widen(m);
-        const wb_u32x2 l = cvt(v);
+        wb_u32x2 h, m, l;
+        wb_split4(__builtin_bit_cast(wb_f32x4, u), h, m, l);
         *reinterpret_cast<wb_u32x2 *>(img + o) = h;
         *reinterpret_cast<wb_u32x2 *>(img + NVQA_WS_PLANE + o) = m;
         *reinterpret_cast<wb_u32x2 *>(img + 2 * NVQA_WS_PLANE + o) = l;
@@ -138,26 +125,16 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_split(WgradSplitArgs g)
             put(Bs, srow + 8 * i, rb[i]);
         }
     };
-    // fragment of the 16 columns starting at c16 (tile-local), the stage's 32 k rows: lane (li, lh) needs k = 8 lh + j
-    // (wgrad_bf16.h: one transposed read covers a 4 (k) x 16 (columns) block per 16-lane group)
+    // fragment of the 16 columns starting at c16 (tile-local), the stage's 32 k rows (kmajor_bf16.h)
     const int q = li >> 2, p = li & 3;
     auto frag = [&](const unsigned char *img, int c16) -> wb_bf16x8 {
         const int r0 = 8 * lh + q;
         const int ch = (c16 >> 3) + (p >> 1);
-        const wb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) wb_s16x4 *)(img + wb_off(r0, ch) + 8u * (p & 1)));
-        const wb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) wb_s16x4 *)(img + wb_off(r0 + 4, ch) + 8u * (p & 1)));
-        typedef short s16x8_t __attribute__((ext_vector_type(8)));
-        const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(wb_bf16x8, v);
+        return wb_frag((wb_lds_s16x4)(img + wb_off(r0, ch) + 8u * (p & 1)), (wb_lds_s16x4)(img + wb_off(r0 + 4, ch) + 8u * (p & 1)));
     };
 
     wb_f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = wb_f32x4{0.f, 0.f, 0.f, 0.f};
+    wb_zero_tile(acc);
 
     if (nst > 0) {
         load_stage(stage_k0[0]);
@@ -176,15 +153,14 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_split(WgradSplitArgs g)
             __syncthreads(); // every wave holds its fragments: the images may be overwritten
             // (nothing moves across: the split must not start -- and wait for the loads just issued -- above the fragment reads)
             __builtin_amdgcn_sched_barrier(0);
-            // smallest terms first: lo hi, mid mid, hi lo, mid hi, hi mid, hi hi
-            constexpr int TA[6] = {2, 1, 0, 1, 0, 0}, TB[6] = {0, 1, 2, 0, 1, 0};
+            // the six terms, smallest first (kmajor_bf16.h)
 #pragma unroll
             for (int t = 0; t < 6; ++t)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[TA[t]][i], b[TB[t]][j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[WB_TERM_A[t]][i], b[WB_TERM_B[t]][j], acc[i][j], 0, 0, 0);
             store_stage(); // the next stage's images (after the last stage: zeros nobody reads)
             // the split and the stores in the gaps of the MFMAs; the first 16 MFMAs alone: the loads are still landing
             __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
@@ -197,19 +173,21 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_split(WgradSplitArgs g)
             __syncthreads();
         }
     }
-    // D[row = 4 lh + r][col = li] of tile (i, j): row = m (A's columns), col = n
-    float *out = g.out + (size_t)blockIdx.z * g.slab_stride;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + 16 * j + li;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm * 64 + 16 * i + 4 * lh + r;
-                if (m < g.M && n < g.N) out[(size_t)m * g.ldo + n] = acc[i][j][r];
-            }
-        }
+    wb_store_tile(g.out + (size_t)blockIdx.z * g.slab_stride, g.ldo, g.M, g.N, m0 + wm * 64, n0 + wn * 64, li, lh, acc);
+}
+
+// one launch on stream st: ks slices, slab z at g.out + z * g.slab_stride
+inline hipError_t wgrad_split_launch(hipStream_t st, const WgradSplitArgs &g, int ks)
+{
+    static bool attr = false;
+    if (!attr) {
+        const hipError_t e = hipFuncSetAttribute((const void *)k_wgrad_split, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS_LDS_BYTES);
+        if (e != hipSuccess) return e;
+        attr = true;
+    }
+    const dim3 grid((g.M + NVQA_WS_BM - 1) / NVQA_WS_BM, (g.N + NVQA_WS_BN - 1) / NVQA_WS_BN, ks);
+    hipLaunchKernelGGL(k_wgrad_split, grid, dim3(256), NVQA_WS_LDS_BYTES, st, g);
+    return hipGetLastError();
 }
 
 } // namespace nvqa

@@ -4,7 +4,7 @@
 //     k_wgrad_split (same fragments, same MFMAs, same epilogue).  The X / H tile is split once for twice the dG rows:
 //     24 values per thread and stage instead of 32.  One workgroup per CU, two waves per SIMD, <= 256 registers.
 //   * TWO LDS buffers of nine 8 KB images (dG: hi / mid / lo x two 128-column halves, X / H: hi / mid / lo; the image
-//     layout is wgrad_bf16.h's wb_off()), 72 KB each, and ONE barrier per stage.  A stage is six phases of 16 MFMAs,
+//     layout is kmajor_bf16.h's wb_off()), 72 KB each, and ONE barrier per stage.  A stage is six phases of 16 MFMAs,
 //     one per term; what else a phase does rides in the gaps of its MFMAs:
 //         term 0  lo  hi   | fragments mid / mid of this stage; split + store rows 0, 1 of stage s+1, reload for s+2
 //         term 1  mid mid  | fragments hi / lo of this stage;   split + store rows 2, 3 of stage s+1, reload for s+2
@@ -45,7 +45,7 @@ inline bool wgrad_split2_takes(int M, int N, int K, int lda, int ldb, int seg_ro
 
 inline int wgrad_split2_blocks(int M, int N, int ks) { return ((M + NVQA_WS2_BM - 1) / NVQA_WS2_BM) * ((N + NVQA_WS2_BN - 1) / NVQA_WS2_BN) * ks; }
 
-// grid: wgrad_split2_blocks(M, N, ks) x 1 x 1; slab z of the ks slabs at g.out + z * g.slab_stride
+// grid: wgrad_split2_blocks(M, N, ks) x 1 x 1 (wgrad_split2_launch); slab z of the ks slabs at g.out + z * g.slab_stride
 __global__ __launch_bounds__(NVQA_WS2_THREADS) void k_wgrad_split2(WgradSplitArgs g, int ks)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char ws2_smem[];
@@ -67,30 +67,7 @@ __global__ __launch_bounds__(NVQA_WS2_THREADS) void k_wgrad_split2(WgradSplitArg
     }
     const int m0 = (tile % tiles_m) * NVQA_WS2_BM, n0 = (tile / tiles_m) * NVQA_WS2_BN;
 
-    // my K stages, as k_wgrad_split builds them: entry idx of the slice's list = stage z + idx ks of the active stages
-    const bool skip = g.nrows != nullptr && g.seg_rows > 0 && g.seg_rows % NVQA_WS_BK == 0;
-    const int seg_rows = skip ? g.seg_rows : g.K, nseg = (g.K + seg_rows - 1) / seg_rows;
-    for (int t = tid; t < nseg; t += NVQA_WS2_THREADS) {
-        int lim = min(seg_rows, g.K - t * seg_rows);
-        if (skip) lim = min(lim, g.nrows[t]);
-        seg_cnt[t] = lim > 0 ? (lim + NVQA_WS_BK - 1) / NVQA_WS_BK : 0;
-    }
-    __syncthreads();
-    for (int t = tid; t <= nseg; t += NVQA_WS2_THREADS) {
-        int b = 0;
-        for (int s = 0; s < t; ++s) b += seg_cnt[s];
-        seg_base[t] = b;
-    }
-    __syncthreads();
-    const int total = seg_base[nseg];
-    const int nst = total > z ? (total - z + ks - 1) / ks : 0;
-    for (int idx = tid; idx < nst; idx += NVQA_WS2_THREADS) {
-        const int i = z + idx * ks;
-        int s = 0;
-        while (seg_base[s + 1] <= i) ++s; // i < total = seg_base[nseg]
-        stage_k0[idx] = s * seg_rows + NVQA_WS_BK * (i - seg_base[s]);
-    }
-    __syncthreads();
+    const int nst = ws_stage_list<NVQA_WS2_THREADS>(g, z, ks, seg_cnt, seg_base, stage_k0); // as k_wgrad_split builds it
 
     // staging: dG  thread -> (row = tid / 64 + 8 i, 4 columns 4 (tid % 64) ..), i = 0 .. 3
     //          X/H thread -> (row = tid / 32 + 16 i, 4 columns 4 (tid % 32) ..), i = 0, 1
@@ -109,24 +86,11 @@ __global__ __launch_bounds__(NVQA_WS2_THREADS) void k_wgrad_split2(WgradSplitArg
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base + (size_t)k0 * ld), 0, rows * ld * 4, 0x00020000);
     };
     auto ldg = [](const __amdgpu_buffer_rsrc_t &r, unsigned off) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); };
-    auto cvt = [](wb_f32x4 v) {
-        const wb_f32x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
-        return wb_u32x2{__builtin_bit_cast(unsigned, __builtin_convertvector(lo, wb_bf16x2)),
-                        __builtin_bit_cast(unsigned, __builtin_convertvector(hi, wb_bf16x2))};
-    };
-    auto widen = [](wb_u32x2 p) {
-        return wb_f32x4{__builtin_bit_cast(float, p[0] << 16), __builtin_bit_cast(float, p[0] & 0xffff0000u),
-                        __builtin_bit_cast(float, p[1] << 16), __builtin_bit_cast(float, p[1] & 0xffff0000u)};
-    };
     typedef __attribute__((address_space(3))) unsigned char *lds_t;
-    // hi / mid / lo images (stride bytes apart) of 4 values of one k row: the split of wgrad_split.h
+    // hi / mid / lo images (stride bytes apart) of 4 values of one k row
     auto put = [&](lds_t at, unsigned stride, const wb_u32x4 &u) {
-        wb_f32x4 v = __builtin_bit_cast(wb_f32x4, u);
-        const wb_u32x2 h = cvt(v);
-        v -= widen(h);
-        const wb_u32x2 m = cvt(v);
-        v -= widen(m);
-        const wb_u32x2 l = cvt(v);
+        wb_u32x2 h, m, l;
+        wb_split4(__builtin_bit_cast(wb_f32x4, u), h, m, l);
         *reinterpret_cast<__attribute__((address_space(3))) wb_u32x2 *>(at) = h;
         *reinterpret_cast<__attribute__((address_space(3))) wb_u32x2 *>(at + stride) = m;
         *reinterpret_cast<__attribute__((address_space(3))) wb_u32x2 *>(at + 2 * stride) = l;
@@ -154,13 +118,7 @@ __global__ __launch_bounds__(NVQA_WS2_THREADS) void k_wgrad_split2(WgradSplitArg
             fb[i][h] = smem + 6 * NVQA_WS_PLANE + wb_off(r0, ((wn * 64 + 16 * i) >> 3) + (p >> 1)) + 8u * (p & 1);
         }
     struct Frag4 { wb_bf16x8 f[4]; };
-    auto frag = [&](lds_t p0, lds_t p1, unsigned off) -> wb_bf16x8 {
-        const wb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wb_s16x4 *)(p0 + off));
-        const wb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wb_s16x4 *)(p1 + off));
-        typedef short s16x8_t __attribute__((ext_vector_type(8)));
-        const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(wb_bf16x8, v);
-    };
+    auto frag = [&](lds_t p0, lds_t p1, unsigned off) { return wb_frag((wb_lds_s16x4)(p0 + off), (wb_lds_s16x4)(p1 + off)); };
     auto frags_a = [&](int pl) {
         Frag4 r;
 #pragma unroll
@@ -182,6 +140,7 @@ __global__ __launch_bounds__(NVQA_WS2_THREADS) void k_wgrad_split2(WgradSplitArg
     };
 
     wb_f32x4 acc[4][4];
+    // (spelled out, not wb_zero_tile(): through the helper this kernel compiles to 220 registers instead of 216 -- profiles/kmajor_shared_ab.json)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -208,6 +167,10 @@ __global__ __launch_bounds__(NVQA_WS2_THREADS) void k_wgrad_split2(WgradSplitArg
     };
     typedef std::integral_constant<bool, true> yes_t;
     typedef std::integral_constant<bool, false> no_t;
+    // the phases below are hand-laid: term t multiplies piece WB_TERM_A[t] of dG by piece WB_TERM_B[t] of X / H (0 hi, 1 mid, 2 lo)
+    static_assert(WB_TERM_A[0] == 2 && WB_TERM_B[0] == 0 && WB_TERM_A[1] == 1 && WB_TERM_B[1] == 1 && WB_TERM_A[2] == 0 && WB_TERM_B[2] == 2 &&
+                      WB_TERM_A[3] == 1 && WB_TERM_B[3] == 0 && WB_TERM_A[4] == 0 && WB_TERM_B[4] == 1 && WB_TERM_A[5] == 0 && WB_TERM_B[5] == 0,
+                  "k_wgrad_split2's phases run lo hi, mid mid, hi lo, mid hi, hi mid, hi hi");
 
     if (nst > 0) {
         {   // stage 0 into buffer 0, stage 1 on its way
@@ -267,19 +230,20 @@ __global__ __launch_bounds__(NVQA_WS2_THREADS) void k_wgrad_split2(WgradSplitArg
             b_hi = nb_hi;
         }
     }
-    // D[row = 4 lh + r][col = li] of tile (i, j): row = m (A's columns), col = n
-    float *out = g.out + (size_t)z * g.slab_stride;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + 16 * j + li;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm * 64 + 16 * i + 4 * lh + r;
-                if (m < g.M && n < g.N) out[(size_t)m * g.ldo + n] = acc[i][j][r];
-            }
-        }
+    wb_store_tile(g.out + (size_t)z * g.slab_stride, g.ldo, g.M, g.N, m0 + wm * 64, n0 + wn * 64, li, lh, acc);
+}
+
+// one launch on stream st: ks slices, slab z at g.out + z * g.slab_stride
+inline hipError_t wgrad_split2_launch(hipStream_t st, const WgradSplitArgs &g, int ks)
+{
+    static bool attr = false;
+    if (!attr) {
+        const hipError_t e = hipFuncSetAttribute((const void *)k_wgrad_split2, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS2_LDS_BYTES);
+        if (e != hipSuccess) return e;
+        attr = true;
+    }
+    hipLaunchKernelGGL(k_wgrad_split2, dim3(wgrad_split2_blocks(g.M, g.N, ks)), dim3(NVQA_WS2_THREADS), NVQA_WS2_LDS_BYTES, st, g, ks);
+    return hipGetLastError();
 }
 
 } // namespace nvqa

@@ -4,29 +4,17 @@
 // W^T made by the library's own TransposeJob code), and is held against the f64 product of the UNROUNDED operands beside an
 // f32 fmaf chain on the same operands: L2-relative error within 1.5 x and max-relative error within 4 x of the chain's
 // (tests/test_dx0_split_numerics.py).  Every element of a row that must be written has to be written, every row of a skipped
-// 16-row tile must still be NaN, and a second run must repeat the bits.  Both B paths run: "lds" (the library's) and "direct".
-// One line per case and path; exit status 1 on a miss.  With --time: microseconds per launch of the old f32 MFMA GEMM, of
-// the kernel and of its direct variant at the step's two shapes, the three taking turns -- steady state (five rounds of 10
+// 16-row tile must still be NaN, and a second run must repeat the bits.
+// One line per case (bits=: kmajor_check_common.h); exit status 1 on a miss.  With --time: microseconds per launch of the old
+// f32 MFMA GEMM and of the kernel at the step's two shapes, the two taking turns -- steady state (five rounds of 10
 // launches back to back per kernel: dG, 109 MB, may sit in the 256 MB Infinity Cache) and first pass (five rounds of one
 // launch behind a 1 GiB memset that evicts dG: what the step sees).  Built by the tests, or by hand:
 //     hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../include -o dx0_split_check dx0_split_check.hip
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <algorithm>
-#include <random>
-#include <vector>
+#include "kmajor_check_common.h"
 #include "../../novel-vqa_amd/csrc/kernels.h"
 #include "../../novel-vqa_amd/csrc/dx0_split.h"
 using namespace nvqa;
-
-#define CK(x)                                                                                 \
-    do {                                                                                      \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 3; }    \
-    } while (0)
 
 typedef Cfg<16, 64, 32, 64, 4, 2, 1, 1> CfgNarrow; // the old route's configurations (nvqa_api.hip)
 typedef Cfg<16, 128, 128, 32, 4, 2, 1, 1> CfgBig16;
@@ -79,8 +67,8 @@ int main(int argc, char **argv)
         std::vector<float> hA((size_t)M * lda), hW((size_t)K * N);
         for (int m = 0; m < M; ++m)
             for (int k = 0; k < lda; ++k) {
-                const float a = nd(rng), b = nd(rng);
-                hA[(size_t)m * lda + k] = k < K ? a * expf(b) * 1e-3f : nanf(""); // the padding between rows is never read
+                const float v = kc_lognormal(rng, nd);
+                hA[(size_t)m * lda + k] = k < K ? v : nanf(""); // the padding between rows is never read
             }
         for (auto &v : hW) v = ud(rng);
         float *dA, *dW, *dO[2];
@@ -112,18 +100,18 @@ int main(int argc, char **argv)
                     if (N <= 256) return launch_gemm<CfgNarrow, A_KC, B_NC, false, EpiStore>(0, og, EpiStore{dO[1], N, 0});
                     return launch_gemm<CfgBig16, A_KC, B_NC, false, EpiStore>(0, og, EpiStore{dO[1], N, 0});
                 }
-                return dx0_split_launch(0, g, which == 2);
+                return dx0_split_launch(0, g);
             };
             void *evict;
             const size_t evict_bytes = (size_t)1 << 30;
             CK(hipMalloc(&evict, evict_bytes));
-            // steady state: 5 rounds, each taking the three kernels in turn, 10 launches back to back per turn (min - max of the
+            // steady state: 5 rounds, each taking the two kernels in turn, 10 launches back to back per turn (min - max of the
             // rounds); first pass: 5 rounds in turn, one launch behind the evicting memset (median)
-            float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {0.f, 0.f, 0.f}, fp[3][5], first[3];
-            for (int which = 0; which < 3; ++which)
+            float lo[2] = {1e30f, 1e30f}, hi[2] = {0.f, 0.f}, fp[2][5], first[2];
+            for (int which = 0; which < 2; ++which)
                 for (int i = 0; i < 3; ++i) CK(launch(which));
             for (int round = 0; round < 5; ++round)
-                for (int which = 0; which < 3; ++which) {
+                for (int which = 0; which < 2; ++which) {
                     CK(hipEventRecord(e0, 0));
                     for (int i = 0; i < 10; ++i) CK(launch(which));
                     CK(hipEventRecord(e1, 0));
@@ -133,7 +121,7 @@ int main(int argc, char **argv)
                     lo[which] = std::min(lo[which], ms * 100.f); hi[which] = std::max(hi[which], ms * 100.f);
                 }
             for (int rep = 0; rep < 5; ++rep)
-                for (int which = 0; which < 3; ++which) {
+                for (int which = 0; which < 2; ++which) {
                     CK(hipMemsetAsync(evict, rep, evict_bytes, 0));
                     CK(hipEventRecord(e0, 0));
                     CK(launch(which));
@@ -141,14 +129,13 @@ int main(int argc, char **argv)
                     CK(hipEventSynchronize(e1));
                     CK(hipEventElapsedTime(&fp[which][rep], e0, e1));
                 }
-            for (int which = 0; which < 3; ++which) {
+            for (int which = 0; which < 2; ++which) {
                 std::sort(fp[which], fp[which] + 5);
                 first[which] = fp[which][2] * 1000.f; // median
             }
             CK(hipFree(evict));
-            printf("time M=%d N=%d K=%d: steady state (5 alternated rounds of 10 launches, min-max) old f32 GEMM %.1f-%.1f us, k_dx0_split %.1f-%.1f us, "
-                   "direct variant %.1f-%.1f us; first pass (median of 5) old %.1f us, k_dx0_split %.1f us, direct %.1f us\n", M, N, K, lo[0], hi[0],
-                   lo[1], hi[1], lo[2], hi[2], first[0], first[1], first[2]);
+            printf("time M=%d N=%d K=%d: steady state (5 alternated rounds of 10 launches, min-max) old f32 GEMM %.1f-%.1f us, k_dx0_split %.1f-%.1f us; "
+                   "first pass (median of 5) old %.1f us, k_dx0_split %.1f us\n", M, N, K, lo[0], hi[0], lo[1], hi[1], first[0], first[1]);
         } else {
             // which rows must be written, which must have been skipped (a whole 16-row tile at or beyond its segment's limit)
             const bool skip = dNr && cs.seg_rows > 0 && cs.seg_rows % 16 == 0;
@@ -173,38 +160,36 @@ int main(int argc, char **argv)
                     ref[(size_t)m * N + n] = s;
                     chain[(size_t)m * N + n] = c;
                 }
-            for (int direct = 0; direct < 2; ++direct) {
-                std::vector<float> h[2] = {std::vector<float>(mn), std::vector<float>(mn)};
-                for (int run = 0; run < 2; ++run) {
-                    CK(hipMemset(dO[run], 0xff, mn * 4)); // NaNs
-                    g.out = dO[run];
-                    CK(dx0_split_launch(0, g, direct != 0));
-                    CK(hipDeviceSynchronize());
-                    CK(hipMemcpy(h[run].data(), dO[run], mn * 4, hipMemcpyDeviceToHost));
-                }
-                size_t unwritten = 0, touched = 0, rerun = 0;
-                double refmax = 0, d6max = 0, d32max = 0, d6sq = 0, d32sq = 0, refsq = 0;
-                for (int m = 0; m < M; ++m)
-                    for (int n = 0; n < N; ++n) {
-                        const size_t i = (size_t)m * N + n;
-                        unsigned b0, b1;
-                        memcpy(&b0, &h[0][i], 4); memcpy(&b1, &h[1][i], 4);
-                        rerun += b0 != b1;
-                        if (skipped[m]) touched += b0 != 0xffffffffu;
-                        if (!must[m]) continue;
-                        if (b0 == 0xffffffffu) { ++unwritten; continue; }
-                        const double d6 = (double)h[0][i] - ref[i], d32 = (double)chain[i] - ref[i];
-                        refmax = std::max(refmax, fabs(ref[i])); d6max = std::max(d6max, fabs(d6)); d32max = std::max(d32max, fabs(d32));
-                        d6sq += d6 * d6; d32sq += d32 * d32; refsq += ref[i] * ref[i];
-                    }
-                const double m6 = d6max / refmax, m32 = d32max / refmax, l6 = sqrt(d6sq / refsq), l32 = sqrt(d32sq / refsq);
-                const bool ok = unwritten == 0 && touched == 0 && rerun == 0 && l6 <= 1.5 * l32 && m6 <= 4.0 * m32;
-                bad += ok ? 0 : 1;
-                printf("M=%d N=%d K=%d lda=%d seg_rows=%d nrows=%s %s (%s): six terms max %.3g L2 %.3g, f32 chain max %.3g L2 %.3g (%.2f x, %.2f x), "
-                       "unwritten %zu, skipped rows touched %zu, rerun %s %s\n", M, N, K, lda, cs.seg_rows, dNr ? "given" : "none",
-                       direct ? "direct" : "lds", cs.what, m6, l6, m32, l32, m6 / m32, l6 / l32, unwritten, touched,
-                       rerun ? "DIFFERS" : "identical", ok ? "OK" : "MISS");
+            std::vector<float> h[2] = {std::vector<float>(mn), std::vector<float>(mn)};
+            for (int run = 0; run < 2; ++run) {
+                CK(hipMemset(dO[run], 0xff, mn * 4)); // NaNs
+                g.out = dO[run];
+                CK(dx0_split_launch(0, g));
+                CK(hipDeviceSynchronize());
+                CK(hipMemcpy(h[run].data(), dO[run], mn * 4, hipMemcpyDeviceToHost));
             }
+            size_t unwritten = 0, touched = 0, rerun = 0;
+            double refmax = 0, d6max = 0, d32max = 0, d6sq = 0, d32sq = 0, refsq = 0;
+            for (int m = 0; m < M; ++m)
+                for (int n = 0; n < N; ++n) {
+                    const size_t i = (size_t)m * N + n;
+                    unsigned b0, b1;
+                    memcpy(&b0, &h[0][i], 4); memcpy(&b1, &h[1][i], 4);
+                    rerun += b0 != b1;
+                    if (skipped[m]) touched += b0 != 0xffffffffu;
+                    if (!must[m]) continue;
+                    if (b0 == 0xffffffffu) { ++unwritten; continue; }
+                    const double d6 = (double)h[0][i] - ref[i], d32 = (double)chain[i] - ref[i];
+                    refmax = std::max(refmax, fabs(ref[i])); d6max = std::max(d6max, fabs(d6)); d32max = std::max(d32max, fabs(d32));
+                    d6sq += d6 * d6; d32sq += d32 * d32; refsq += ref[i] * ref[i];
+                }
+            const double m6 = d6max / refmax, m32 = d32max / refmax, l6 = sqrt(d6sq / refsq), l32 = sqrt(d32sq / refsq);
+            const bool ok = unwritten == 0 && touched == 0 && rerun == 0 && l6 <= 1.5 * l32 && m6 <= 4.0 * m32;
+            bad += ok ? 0 : 1;
+            printf("M=%d N=%d K=%d lda=%d seg_rows=%d nrows=%s %s (%s): six terms max %.3g L2 %.3g, f32 chain max %.3g L2 %.3g (%.2f x, %.2f x), "
+                   "unwritten %zu, skipped rows touched %zu, rerun %s bits=%016llx %s\n", M, N, K, lda, cs.seg_rows, dNr ? "given" : "none",
+                   "lds", cs.what, m6, l6, m32, l32, m6 / m32, l6 / l32, unwritten, touched,
+                   rerun ? "DIFFERS" : "identical", (unsigned long long)kc_fnv1a(h[0].data(), mn), ok ? "OK" : "MISS");
         }
         fflush(stdout);
         CK(hipFree(dA)); CK(hipFree(dW)); CK(hipFree(dW3)); CK(hipFree(dO[0])); CK(hipFree(dO[1]));

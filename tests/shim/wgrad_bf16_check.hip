@@ -3,14 +3,9 @@
 // step -- dW[2048 x N] = dG^T X, K = 14336, N = 512 / 200, operands as f32 rows or as the persistent kernels' bf16 images,
 // split-K 8 and 16 -- against a DOUBLE-PRECISION sum of the bf16-rounded operands on the host (its own statement of the
 // product: round-to-nearest-even to bf16, exact products, f64 accumulation).  Every output element of a sample of rows and
-// ALL their columns is checked; prints one line per configuration and exits non-zero on a mismatch.
+// ALL their columns is checked; prints one line per configuration (bits=: kmajor_check_common.h) and exits non-zero on a mismatch.
 // (Promoted from tools/kbench15, which only timed the kernel and sampled 200 outputs.)
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
+#include "kmajor_check_common.h"
 #include "../../novel-vqa_amd/csrc/wgrad_bf16.h"
 using namespace nvqa;
 
@@ -21,15 +16,6 @@ static float bf16r(float x)
     u &= 0xffff0000u;
     float y; memcpy(&y, &u, 4);
     return y;
-}
-
-__global__ void k_sum_slabs(const float *slabs, int ks, size_t n, float *out)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
-    for (int z = 0; z < ks; ++z) s += slabs[(size_t)z * n + i];
-    out[i] = s;
 }
 
 int main()
@@ -45,9 +31,6 @@ int main()
     (void)hipMalloc(&dS, (size_t)16 * M * 512 * 4); (void)hipMalloc(&dO, (size_t)M * 512 * 4);
     (void)hipMemcpy(dA, hA.data(), hA.size() * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(dB, hB.data(), hB.size() * 4, hipMemcpyHostToDevice);
-    (void)hipFuncSetAttribute((const void *)k_wgrad_bf16<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES);
-    (void)hipFuncSetAttribute((const void *)k_wgrad_bf16<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES);
-    (void)hipFuncSetAttribute((const void *)k_wgrad_bf16<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WB_LDS_BYTES);
     std::vector<unsigned short> hA16(hA.size()), hB16(hB.size());
     std::vector<float> rA(hA.size()), rB(hB.size()); // the rounded operands, as f32
     for (size_t i = 0; i < hA.size(); ++i) { rA[i] = bf16r(hA[i]); unsigned u; memcpy(&u, &rA[i], 4); hA16[i] = (unsigned short)(u >> 16); }
@@ -83,12 +66,10 @@ int main()
             for (int ks : {8, 16}) {
                 const int kslice = ((K + ks - 1) / ks + 63) / 64 * 64;
                 const int kz = (K + kslice - 1) / kslice;
-                WgradBf16Args g{dA, dB, dA16, dB16, dS, (size_t)M * N, lda, ldb, N, M, N, K, kslice};
-                const dim3 grid((M + 127) / 128, (N + 127) / 128, kz);
+                // mode 0: both operands as f32 rows, 1: dG as its image, 2: both as images (the launch follows the images given)
+                WgradBf16Args g{dA, dB, mode >= 1 ? dA16 : nullptr, mode == 2 ? dB16 : nullptr, dS, (size_t)M * N, lda, ldb, N, M, N, K, kslice};
                 (void)hipMemset(dS, 0xff, (size_t)16 * M * 512 * 4); // NaNs: an unwritten slab element shows
-                if (mode == 0) hipLaunchKernelGGL((k_wgrad_bf16<false, false>), grid, dim3(256), NVQA_WB_LDS_BYTES, 0, g);
-                else if (mode == 1) hipLaunchKernelGGL((k_wgrad_bf16<true, false>), grid, dim3(256), NVQA_WB_LDS_BYTES, 0, g);
-                else hipLaunchKernelGGL((k_wgrad_bf16<true, true>), grid, dim3(256), NVQA_WB_LDS_BYTES, 0, g);
+                if (wgrad_bf16_launch(0, g) != hipSuccess) { printf("launch failed\n"); return 3; }
                 hipLaunchKernelGGL(k_sum_slabs, dim3(((size_t)M * N + 255) / 256), dim3(256), 0, 0, dS, kz, (size_t)M * N, dO);
                 std::vector<float> hO((size_t)M * N);
                 if (hipMemcpy(hO.data(), dO, hO.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { printf("kernel failed\n"); return 3; }
@@ -100,8 +81,8 @@ int main()
                     }
                 const bool ok = worst <= 2e-5 * scale; // f32 accumulation of 14336 exact products, split-K 8 / 16: measured 2-4e-6
                 bad += ok ? 0 : 1;
-                printf("A %s B %s N=%d splitK=%d: max err %.3g of %.3g (%.2g relative) %s\n", mode ? "image" : "f32", mode == 2 ? "image" : "f32", N, kz,
-                       worst, scale, worst / scale, ok ? "OK" : "MISMATCH");
+                printf("A %s B %s N=%d splitK=%d: max err %.3g of %.3g (%.2g relative) bits=%016llx %s\n", mode ? "image" : "f32", mode == 2 ? "image" : "f32", N, kz,
+                       worst, scale, worst / scale, (unsigned long long)kc_fnv1a(hO.data(), hO.size()), ok ? "OK" : "MISMATCH");
             }
     }
     return bad ? 1 : 0;

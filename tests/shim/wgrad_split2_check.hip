@@ -5,37 +5,12 @@
 // kernel must repeat its bits.  No tolerance: the old kernel is held against the f64 product by wgrad_split_check.hip.
 // Operands as there: dG log-normal x 1e-3, the other operand 2 tanh x Bernoulli(0.5); ragged cases: rows >= nrows[step]
 // are zero in dG and keep their (finite, non-zero) values in the other operand.
-// One line per case; exit status 1 on a difference.  With --time: microseconds per launch of both kernels at the step's
+// One line per case (bits=: the new kernel's slabs, kmajor_check_common.h); exit status 1 on a difference.  With --time: microseconds per launch of both kernels at the step's
 // two shapes instead.  Built by the tests, or by hand from this directory:
 //     hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../include -o wgrad_split2_check wgrad_split2_check.hip
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <random>
-#include <vector>
+#include "kmajor_check_common.h"
 #include "../../novel-vqa_amd/csrc/wgrad_split2.h"
 using namespace nvqa;
-
-#define CK(x)                                                                                 \
-    do {                                                                                      \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 3; }    \
-    } while (0)
-
-// operand [K][ld] from a pool of values; rows >= nrows[k / B] of a step: zero when zero_inactive
-__global__ void k_fill(float *dst, int K, int ld, int cols, const float *pool, unsigned pool_n, const int *nrows, int B, int zero_inactive)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)K * ld) return;
-    const int k = (int)(i / ld), c = (int)(i % ld);
-    const bool on = !nrows || k % B < nrows[k / B];
-    float v = pool[(unsigned)(((size_t)k * 2053 + c) % pool_n)];
-    if (c >= cols) v = __builtin_nanf(""); // the padding between rows is never read
-    if (!on && zero_inactive) v = 0.f;
-    dst[i] = v;
-}
 
 // out[0] += words that differ, out[1] += words of b still at the prefill pattern
 __global__ void k_diff(const unsigned *a, const unsigned *b, size_t n, unsigned *out)
@@ -55,15 +30,13 @@ int main(int argc, char **argv)
     std::mt19937 rng(1);
     std::normal_distribution<float> nd(0.f, 1.f);
     std::vector<float> hA(POOL), hB(POOL);
-    for (auto &v : hA) { const float a = nd(rng), b = nd(rng); v = a * expf(b) * 1e-3f; }
-    for (auto &v : hB) { const float a = nd(rng); v = (rng() & 1u) ? 2.f * tanhf(a) : 0.f; }
+    for (auto &v : hA) v = kc_lognormal(rng, nd);
+    for (auto &v : hB) v = kc_tanh_bernoulli(rng, nd);
     float *pA, *pB;
     if (hipMalloc(&pA, POOL * 4) != hipSuccess) { printf("no device\n"); return 2; }
     CK(hipMalloc(&pB, POOL * 4));
     CK(hipMemcpy(pA, hA.data(), POOL * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(pB, hB.data(), POOL * 4, hipMemcpyHostToDevice));
-    CK(hipFuncSetAttribute((const void *)k_wgrad_split, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS_LDS_BYTES));
-    CK(hipFuncSetAttribute((const void *)k_wgrad_split2, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS2_LDS_BYTES));
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
 
@@ -116,32 +89,29 @@ int main(int argc, char **argv)
         const int *nr = cs.given ? dNr : nullptr;
         WgradSplitArgs g1{dA, dB, dS1, ks == 1 ? 0 : mn, nr, B, lda, ldb, N, M, N, K}, g2 = g1, g3 = g1;
         g2.out = dS2; g3.out = dS3;
-        const dim3 grid1((M + NVQA_WS_BM - 1) / NVQA_WS_BM, (N + NVQA_WS_BN - 1) / NVQA_WS_BN, ks);
-        const dim3 grid2(wgrad_split2_blocks(M, N, ks));
         if (!timing) {
-            hipLaunchKernelGGL(k_wgrad_split, grid1, dim3(256), NVQA_WS_LDS_BYTES, 0, g1);
-            hipLaunchKernelGGL(k_wgrad_split2, grid2, dim3(NVQA_WS2_THREADS), NVQA_WS2_LDS_BYTES, 0, g2, ks);
-            hipLaunchKernelGGL(k_wgrad_split2, grid2, dim3(NVQA_WS2_THREADS), NVQA_WS2_LDS_BYTES, 0, g3, ks);
+            CK(wgrad_split_launch(0, g1, ks));
+            CK(wgrad_split2_launch(0, g2, ks));
+            CK(wgrad_split2_launch(0, g3, ks));
             hipLaunchKernelGGL(k_diff, dim3((words + 255) / 256), dim3(256), 0, 0, (const unsigned *)dS1, (const unsigned *)dS2, words, dCnt);
             hipLaunchKernelGGL(k_diff, dim3((words + 255) / 256), dim3(256), 0, 0, (const unsigned *)dS2, (const unsigned *)dS3, words, dCnt + 2);
             CK(hipGetLastError());
             unsigned cnt[4];
             CK(hipMemcpy(cnt, dCnt, sizeof cnt, hipMemcpyDeviceToHost));
+            std::vector<unsigned> slabs(words); // the new kernel's
+            CK(hipMemcpy(slabs.data(), dS2, words * 4, hipMemcpyDeviceToHost));
             const bool ok = cnt[0] == 0 && cnt[1] == 0 && cnt[2] == 0;
             bad += ok ? 0 : 1;
-            printf("M=%d N=%d K=%d (%d x %d) splitK=%d nrows=%s lda=%d ldb=%d: slabs %s (%u of %zu words differ), unwritten %u, rerun %s %s\n",
+            printf("M=%d N=%d K=%d (%d x %d) splitK=%d nrows=%s lda=%d ldb=%d: slabs %s (%u of %zu words differ), unwritten %u, rerun %s bits=%016llx %s\n",
                    M, N, K, T, B, ks, !cs.given ? "none" : "given", lda, ldb, cnt[0] ? "DIFFER" : "identical", cnt[0], words, cnt[1],
-                   cnt[2] ? "DIFFERS" : "identical", ok ? "OK" : "MISS");
+                   cnt[2] ? "DIFFERS" : "identical", (unsigned long long)kc_fnv1a(slabs.data(), words), ok ? "OK" : "MISS");
         } else {
             float us[2];
             for (int which = 0; which < 2; ++which) {
-                auto launch = [&]() {
-                    if (which == 0) hipLaunchKernelGGL(k_wgrad_split, grid1, dim3(256), NVQA_WS_LDS_BYTES, 0, g1);
-                    else hipLaunchKernelGGL(k_wgrad_split2, grid2, dim3(NVQA_WS2_THREADS), NVQA_WS2_LDS_BYTES, 0, g2, ks);
-                };
-                for (int i = 0; i < 3; ++i) launch();
+                auto launch = [&]() { return which == 0 ? wgrad_split_launch(0, g1, ks) : wgrad_split2_launch(0, g2, ks); };
+                for (int i = 0; i < 3; ++i) CK(launch());
                 CK(hipEventRecord(e0, 0));
-                for (int i = 0; i < 20; ++i) launch();
+                for (int i = 0; i < 20; ++i) CK(launch());
                 CK(hipEventRecord(e1, 0));
                 CK(hipEventSynchronize(e1));
                 float ms = 0;

@@ -6,66 +6,12 @@
 // fmaf chain with the same split-K on the same operands.  What is measured is how v_mfma_f32_16x16x32_bf16 sums its 32
 // products: the six-term form must stay within 1.5 x of the f32 chain's L2-relative and 4 x of its max-relative error
 // (margins of tests/test_wgrad_split_numerics.py's emulation), and a second run must give the same bits.
-// One line per configuration; exit status 1 on a miss.  With --time: microseconds per launch as well.  Built by the test,
+// One line per configuration (bits=: kmajor_check_common.h); exit status 1 on a miss.  With --time: microseconds per launch as well.  Built by the test,
 // or by hand from this directory:
 //     hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../include -o wgrad_split_check wgrad_split_check.hip
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <random>
-#include <vector>
+#include "kmajor_check_common.h"
 #include "../../novel-vqa_amd/csrc/wgrad_split.h"
 using namespace nvqa;
-
-#define CK(x)                                                                                 \
-    do {                                                                                      \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 3; }    \
-    } while (0)
-
-__global__ void k_sum_slabs(const float *slabs, int ks, size_t n, float *out)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
-    for (int z = 0; z < ks; ++z) s += slabs[(size_t)z * n + i];
-    out[i] = s;
-}
-
-// the reference: f64 products of the unrounded operands, f64 accumulation
-__global__ void k_ref_f64(const float *A, const float *B, int lda, int ldb, int M, int N, int K, double *out)
-{
-    const int n = blockIdx.x * blockDim.x + threadIdx.x, m = blockIdx.y;
-    if (n >= N || m >= M) return;
-    double s = 0;
-    for (int k = 0; k < K; ++k) s += (double)A[(size_t)k * lda + m] * (double)B[(size_t)k * ldb + n];
-    out[(size_t)m * N + n] = s;
-}
-
-// the f32 form: an fmaf chain per K slice, slabs summed in z order
-__global__ void k_f32_chain(const float *A, const float *B, int lda, int ldb, int M, int N, int K, int kslice, float *slabs)
-{
-    const int n = blockIdx.x * blockDim.x + threadIdx.x, m = blockIdx.y, z = blockIdx.z;
-    if (n >= N || m >= M) return;
-    const int kend = min(K, (z + 1) * kslice);
-    float s = 0.f;
-    for (int k = z * kslice; k < kend; ++k) s = fmaf(A[(size_t)k * lda + m], B[(size_t)k * ldb + n], s);
-    slabs[(size_t)z * M * N + (size_t)m * N + n] = s;
-}
-
-static void errors(const std::vector<float> &c, const std::vector<double> &ref, double *l2, double *mx)
-{
-    double d2 = 0, r2 = 0, dm = 0, rm = 0;
-    for (size_t i = 0; i < ref.size(); ++i) {
-        const double d = (double)c[i] - ref[i];
-        if (!(d == d)) { *l2 = *mx = 1e30; return; }
-        d2 += d * d; r2 += ref[i] * ref[i];
-        dm = fmax(dm, fabs(d)); rm = fmax(rm, fabs(ref[i]));
-    }
-    *l2 = sqrt(d2 / r2); *mx = dm / rm;
-}
 
 int main(int argc, char **argv)
 {
@@ -75,8 +21,8 @@ int main(int argc, char **argv)
     std::mt19937 rng(1);
     std::normal_distribution<float> nd(0.f, 1.f);
     std::vector<float> hA((size_t)KMAX * M), hB((size_t)KMAX * NMAX);
-    for (auto &v : hA) { const float a = nd(rng), b = nd(rng); v = a * expf(b) * 1e-3f; }
-    for (auto &v : hB) { const float a = nd(rng); v = (rng() & 1u) ? 2.f * tanhf(a) : 0.f; }
+    for (auto &v : hA) v = kc_lognormal(rng, nd);
+    for (auto &v : hB) v = kc_tanh_bernoulli(rng, nd);
     float *dA, *dB, *dS, *dO;
     double *dR;
     int *dNr;
@@ -86,7 +32,6 @@ int main(int argc, char **argv)
     CK(hipMalloc(&dO, (size_t)M * NMAX * 4));
     CK(hipMalloc(&dR, (size_t)M * NMAX * 8));
     CK(hipMalloc(&dNr, TMAX * 4));
-    CK(hipFuncSetAttribute((const void *)k_wgrad_split, hipFuncAttributeMaxDynamicSharedMemorySize, NVQA_WS_LDS_BYTES));
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
 
@@ -140,10 +85,9 @@ int main(int argc, char **argv)
         CK(hipMemcpy(c32.data(), dO, mn * 4, hipMemcpyDeviceToHost));
         // six terms, twice
         WgradSplitArgs g{dA, dB, dS, mn, dNr, B, lda, ldb, N, M, N, K};
-        const dim3 grid((M + NVQA_WS_BM - 1) / NVQA_WS_BM, (N + NVQA_WS_BN - 1) / NVQA_WS_BN, cs.ks);
         for (int run = 0; run < 2; ++run) {
             CK(hipMemset(dS, 0xff, (size_t)16 * M * NMAX * 4)); // NaNs: an unwritten slab element shows
-            hipLaunchKernelGGL(k_wgrad_split, grid, dim3(256), NVQA_WS_LDS_BYTES, 0, g);
+            CK(wgrad_split_launch(0, g, cs.ks));
             hipLaunchKernelGGL(k_sum_slabs, dim3((mn + 255) / 256), dim3(256), 0, 0, dS, cs.ks, mn, dO);
             CK(hipMemcpy((run ? c6b : c6).data(), dO, mn * 4, hipMemcpyDeviceToHost));
         }
@@ -153,12 +97,12 @@ int main(int argc, char **argv)
         errors(c6, ref, &l6, &m6);
         const bool ok = same && l6 <= 1.5 * l32 && m6 <= 4.0 * m32;
         bad += ok ? 0 : 1;
-        printf("N=%d K=%d splitK=%d ragged=%d: six terms L2 %.3g max %.3g, f32 chain L2 %.3g max %.3g, ratio L2 %.3f max %.3f, rerun %s %s\n",
-               N, K, cs.ks, (int)cs.ragged, l6, m6, l32, m32, l6 / l32, m6 / m32, same ? "identical" : "DIFFERS", ok ? "OK" : "MISS");
+        printf("N=%d K=%d splitK=%d ragged=%d: six terms L2 %.3g max %.3g, f32 chain L2 %.3g max %.3g, ratio L2 %.3f max %.3f, rerun %s bits=%016llx %s\n",
+               N, K, cs.ks, (int)cs.ragged, l6, m6, l32, m32, l6 / l32, m6 / m32, same ? "identical" : "DIFFERS", (unsigned long long)kc_fnv1a(c6.data(), mn), ok ? "OK" : "MISS");
         if (timing) {
-            for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(k_wgrad_split, grid, dim3(256), NVQA_WS_LDS_BYTES, 0, g);
+            for (int i = 0; i < 3; ++i) CK(wgrad_split_launch(0, g, cs.ks));
             CK(hipEventRecord(e0, 0));
-            for (int i = 0; i < 20; ++i) hipLaunchKernelGGL(k_wgrad_split, grid, dim3(256), NVQA_WS_LDS_BYTES, 0, g);
+            for (int i = 0; i < 20; ++i) CK(wgrad_split_launch(0, g, cs.ks));
             CK(hipEventRecord(e1, 0));
             CK(hipEventSynchronize(e1));
             float ms = 0;

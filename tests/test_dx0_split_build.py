@@ -40,7 +40,7 @@ def remarks(tmp_path_factory):
     # the dynamic LDS the launch asks for: the header's function, evaluated by the compiler
     probe = tmp / "lds.cpp"
     probe.write_text('#include <stdio.h>\n#include "dx0_split.h"\n'
-                     'int main() { printf("%d %d\\n", (int)nvqa::dx0_split_lds_bytes(false), (int)NVQA_DX_THREADS); return 0; }\n')
+                     'int main() { printf("%d %d\\n", (int)nvqa::dx0_split_lds_bytes(), (int)NVQA_DX_THREADS); return 0; }\n')
     exe = str(tmp / "lds")
     p = subprocess.run([HIPCC, "-std=c++17", "--offload-arch=gfx950", "-x", "hip", "-I" + os.path.join(ROOT, "include"),
                         "-I" + os.path.join(ROOT, "novel-vqa_amd", "csrc"), "-o", exe, str(probe)], capture_output=True, text=True, timeout=900)
@@ -49,8 +49,8 @@ def remarks(tmp_path_factory):
     return r.stderr, lds, threads
 
 
-# the library's instances: 13 column tiles (N <= 208) and 16 (N <= 512), B staged through LDS
-@pytest.mark.parametrize("symbol", ["k_dx0_splitILi13ELb0E", "k_dx0_splitILi16ELb0E"], ids=["nt13", "nt16"])
+# the kernel's instances: 13 column tiles (N <= 208) and 16 (N <= 512)
+@pytest.mark.parametrize("symbol", ["k_dx0_splitILi13EE", "k_dx0_splitILi16EE"], ids=["nt13", "nt16"])
 def test_kernel_fits_one_workgroup_per_cu(remarks, symbol):
     stderr, lds, threads = remarks
     u = _usage(stderr, symbol)

@@ -9,32 +9,13 @@ additions per output, the six-term form once per term and chunk; three terms: 5.
 tests/test_gpu_dx0_split.py."""
 import torch
 
+from split_emul import err as _err, mm, six as _six, split as _split
+
 M, N, K, CHUNK = 256, 200, 2048, 32
 
 
-def _bf(x):
-    return x.to(torch.bfloat16).to(torch.float32)  # round-to-nearest-even
-
-
-def _split(x):
-    h = _bf(x)
-    r = x - h
-    m = _bf(r)
-    return h, m, _bf(r - m)
-
-
 def _mm(terms):
-    """One f32 accumulator, K in chunks of 32, the terms of a chunk in the order given."""
-    acc = torch.zeros(M, N)
-    for k in range(0, K, CHUNK):
-        for a, w in terms:
-            acc += a[:, k:k + CHUNK] @ w[k:k + CHUNK]
-    return acc
-
-
-def _six(A, W):
-    (ah, am, al), (wh, wm, wl) = _split(A), _split(W)
-    return [(al, wh), (am, wm), (ah, wl), (am, wh), (ah, wm), (ah, wh)]  # the kernel's order, smallest first
+    return mm(terms, K, CHUNK, k_major=False)
 
 
 def _chain(A, W):
@@ -43,11 +24,6 @@ def _chain(A, W):
     for k in range(K):
         acc = (acc + A[:, k:k + 1].double() * W[k:k + 1].double()).float().double()
     return acc.float()
-
-
-def _err(C, ref):
-    d = C.double() - ref
-    return float(d.abs().max() / ref.abs().max()), float(d.norm() / ref.norm())
 
 
 def _operands(seed=0):

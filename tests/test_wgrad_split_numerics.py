@@ -7,42 +7,18 @@ must stay within 1.5 x of the f32 chain's L2-relative and 4 x of its max-relativ
 the kernel pays for six.  What the hardware does inside one MFMA's K = 32 sum is measured by tests/test_gpu_wgrad_split.py."""
 import torch
 
+from split_emul import bf as _bf, err as _err, mm, six as _six, split as _split
+
 K, M, N, CHUNK = 13312, 512, 200, 512
 
 
-def _bf(x):
-    return x.to(torch.bfloat16).to(torch.float32)  # round-to-nearest-even
-
-
-def _split(x):
-    h = _bf(x)
-    r = x - h
-    m = _bf(r)
-    return h, m, _bf(r - m)
-
-
 def _mm(terms, k_total):
-    """One f32 accumulator, K in chunks, the terms of a chunk in the order given."""
-    acc = torch.zeros(terms[0][0].shape[1], terms[0][1].shape[1])
-    for k in range(0, k_total, CHUNK):
-        for a, b in terms:
-            acc += a[k:k + CHUNK].T @ b[k:k + CHUNK]
-    return acc
-
-
-def _six(A, B):
-    (ah, am, al), (bh, bm, bl) = _split(A), _split(B)
-    return [(al, bh), (am, bm), (ah, bl), (am, bh), (ah, bm), (ah, bh)]  # the kernel's order, smallest first
+    return mm(terms, k_total, CHUNK, k_major=True)
 
 
 def _three(A, B):
     (ah, am, _), (bh, bm, _) = _split(A), _split(B)
     return [(ah, bm), (am, bh), (ah, bh)]
-
-
-def _err(C, ref):
-    d = C.double() - ref
-    return float(d.abs().max() / ref.abs().max()), float(d.norm() / ref.norm())
 
 
 def _operands(seed=0):
